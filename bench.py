@@ -17,7 +17,15 @@ gradients averaged over RCCL.  Prints ONE JSON line (rank 0).
     --dtype fp8        e4m3 operands for the forward QKV / FFN products (BASELINE configs[4]); bf16 GNN + backward
     --workload c4      BASELINE configs[3]: generator only, 64 objects x 64 adjacency, batch 64, forward + backward
 
-Extra objects on the line:
+A plain run sets up, warms up, times the K steps and prints the line: `metric`, `value`, `unit`,
+`higher_is_better`, `dtype`, `ms_per_step` (milliseconds of one timed step) and the configuration.
+
+    --dump-outputs DIR after the timed steps, write what the last timed step computed (the arrays a caller of the
+                       timed path receives: losses, logits, clip norms, a fixed seeded sample of the updated weights and
+                       moments; c4: the generator's outputs and gradients) as DIR/<name>.npy in float32
+    --full             also run everything below (each leg can still be switched off by its --no-* option)
+
+Extra objects on the line (--full only; null in a plain run, as are `ms_per_step_by_branch`, `ms_per_pass`, `kernels`):
   roofline           the dominant kernel family of the step (c4: the LDS-tiled aggregate kernel), timed live with
                      HIP events on the launch stream in an instrumented (un-captured) iteration
   cpu_baseline       the CPU oracle (oracle/xggm_oracle.py, torch fp32) timed on this box's host cores on a bounded
@@ -69,6 +77,10 @@ def parse(argv=None):
                    "BertAdam on the shard -> all-gather of the weights, stage by stage beside the next forward); "
                    "default: off at every world size until an N >= 4 scaling record exists (DESIGN.md section 6)")
     p.add_argument("--seed", type=int, default=9595)
+    p.add_argument("--full", action="store_true", help="after the headline figure, also run the loader-inclusive leg, the "
+                   "reference batch, the per-branch / per-pass times, the kernel timing and the CPU baseline")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed as "
+                   "DIR/<name>.npy (float32, at most 64 MB in all)")
     a = p.parse_args(argv)
     if a.answers is None:
         a.answers = 1842 if a.order == "gqa" else 2274
@@ -218,6 +230,52 @@ def batch_of(item):
     qid, feats, boxes, sent, target, adj = item
     return dict(feats=feats, boxes=boxes, input_ids=sent[0], input_mask=sent[1], segment_ids=sent[2], target=target,
                 adj_true=adj)
+
+
+# ------------------------------------------------------------------------------------------ output dump
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SAMPLE = 1 << 20  # entries of a flat state buffer kept in the dump
+
+
+def sample_index(n, k=DUMP_SAMPLE, seed=0):
+    """a fixed, seeded, sorted sample of ``k`` positions out of ``n`` (all of them when ``n <= k``)"""
+    import numpy as np
+    if n <= k:
+        return None
+    return torch.from_numpy(np.sort(np.random.default_rng(seed).choice(n, size=k, replace=False)))
+
+
+def dump_outputs(path, arrays):
+    """``arrays``: {name: tensor}; each is written as ``path/<name>.npy`` in float32 (float64 stays float64)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    host = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        t = t.double() if t.dtype == torch.float64 else t.float()
+        host[name] = t.cpu().numpy()
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("bench.py --dump-outputs: %d bytes, more than the %d allowed" % (total, DUMP_LIMIT_BYTES))
+    for name, a in host.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    log("dumped %d arrays (%.1f MB) to %s" % (len(host), total / 1e6, path))
+
+
+def train_outputs(trainer, last):
+    """what one training iteration hands back, by pass kind, plus a seeded sample of the state it updated"""
+    a, b = last  # (plain pass, GGM pass): CapturedTrainer.iteration returns them in that order for both loop orders
+    out = {}
+    for kind, (loss, logit, norm) in (("plain", a), ("ggm", b)):
+        out[kind + "_loss"] = loss.reshape(-1)
+        out[kind + "_logit"] = logit
+        out[kind + "_grad_norm"] = norm.reshape(-1)
+    arena = trainer.rt.arena
+    idx = sample_index(arena.params.numel())
+    for name in ("params", "m", "v"):
+        buf = getattr(arena, name)
+        out["sample_" + name] = buf if idx is None else buf[idx.to(buf.device)]
+    return out
 
 
 # ------------------------------------------------------------------------------------------ kernel timing
@@ -497,6 +555,8 @@ def main_c4(args, device):
     gx = torch.randn(B, N, H, device=device, dtype=dt) / (N * H) ** 0.5
     ga = torch.randn(B, N, N, device=device) / N
 
+    out = {}
+
     def step():
         gen.zero_grad()
         rt.arena.begin_pass()
@@ -504,6 +564,7 @@ def main_c4(args, device):
         xo, ao = gen(x, adj)
         torch.autograd.backward([xo, ao], [gx, ga])
         rt.advance()
+        out.update(x_out=xo, adj_out=ao)  # a replay rewrites these in place
 
     side = torch.cuda.Stream()
     side.wait_stream(torch.cuda.current_stream())
@@ -529,12 +590,16 @@ def main_c4(args, device):
     ms_step = 1000.0 * dtm / args.steps
     value = B * args.steps / dtm
     log("c4 timed region: %.3f ms/step, %.1f samples/s" % (ms_step, value))
+    if args.dump_outputs:
+        arrays = dict(out, x_grad=x.grad, adj_grad=adj.grad)
+        arrays.update(("grad_" + k, p.grad) for k, p in gen.named_parameters() if p.grad is not None)
+        dump_outputs(args.dump_outputs, arrays)
     roofline = kernels = None
-    if not args.no_kernel_timing:
+    if args.full and not args.no_kernel_timing:
         fam = kernel_timing([step])
         roofline, kernels = roofline_of(fam, prefer="xggm_aggregate_" + ("f32" if args.dtype == "f32" else "bf16"))
     cpu = None
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline_c4(args, B, N, H)
     print(json.dumps({
         "metric": "generator fwd+bwd samples/sec (64-obj x 64 adjacency stress, BASELINE configs[3])",
@@ -633,7 +698,7 @@ def main():
         zero1 = bool(args.zero1) if args.zero1 is not None else zero1_default(world)
         enable_data_parallel(model, wire_dtype=torch.bfloat16 if args.wire == "bf16" else None, zero1=zero1)
     loader_parts = None
-    if not args.no_loader:
+    if args.full and not args.no_loader:
         loader_parts = make_loader(model, args, device)  # before the trainer: its static inputs take the loader's slot layout
     inline = loader_parts is not None and loader_parts[0].handover == "inline"
     trainer = CapturedTrainer(model, optim, batch, sigma=1.0, order=args.order, use_graph=not args.no_graph,
@@ -664,9 +729,10 @@ def main():
     log("warmup done")
     t0 = time.perf_counter()
     host_s = 0.0
+    last = None
     for _ in range(args.steps):
         h0 = time.perf_counter()
-        trainer.iteration(branch())
+        last = trainer.iteration(branch())
         host_s += time.perf_counter() - h0
     barrier()
     dt = max_over_ranks(time.perf_counter() - t0)
@@ -674,10 +740,12 @@ def main():
     ms_step = 1000.0 * dt / args.steps
     value = args.batch * world * args.steps / dt
     log("timed region: %.3f ms/step, %.1f samples/s" % (ms_step, value))
+    if args.dump_outputs and rank == 0 and last is not None:
+        dump_outputs(args.dump_outputs, train_outputs(trainer, last))
 
     # the same steps with the loader boundary inside the timed region (never `value`)
     with_loader = None
-    if not args.no_loader:
+    if loader_parts is not None:
         import shutil
         loader, host_bytes, tmp = loader_parts
         it = iter(loader)
@@ -729,7 +797,7 @@ def main():
     # that are no multiple of any GEMM tile (1840 / 3312 and 1920 / 3456 rows).  A second captured trainer on the same
     # model and optimiser; an extra key, never `value`.
     ref_batch = None
-    if world == 1 and not force_dp and not args.no_ref_batch:
+    if args.full and world == 1 and not force_dp and not args.no_ref_batch:
         from xggm_amd import synth
         Bref = 96 if args.order == "gqa" else 92
         nb = synth.vqa_batch(Bref, A=args.answers, seed=2000)
@@ -755,27 +823,29 @@ def main():
         torch.cuda.empty_cache()
 
     # per-branch step time (diagnostic; not part of the timed region)
-    per_branch = {}
-    for br in ("rel", "node"):
-        barrier()
-        t1 = time.perf_counter()
-        for _ in range(5):
-            trainer.iteration(br)
-        barrier()
-        per_branch[br] = round(1000.0 * (time.perf_counter() - t1) / 5, 3)
+    per_branch = per_pass = None
+    if args.full:
+        per_branch = {}
+        for br in ("rel", "node"):
+            barrier()
+            t1 = time.perf_counter()
+            for _ in range(5):
+                trainer.iteration(br)
+            barrier()
+            per_branch[br] = round(1000.0 * (time.perf_counter() - t1) / 5, 3)
 
-    # per-pass time: forward + backward + clip + BertAdam of ONE pass (SURVEY section 8d asks for both views)
-    per_pass = {}
-    for kind in ("plain", "rel", "node"):
-        barrier()
-        t1 = time.perf_counter()
-        for _ in range(5):
-            trainer.run_pass(kind)
-        barrier()
-        per_pass[kind] = round(1000.0 * (time.perf_counter() - t1) / 5, 3)
+        # per-pass time: forward + backward + clip + BertAdam of ONE pass (SURVEY section 8d asks for both views)
+        per_pass = {}
+        for kind in ("plain", "rel", "node"):
+            barrier()
+            t1 = time.perf_counter()
+            for _ in range(5):
+                trainer.run_pass(kind)
+            barrier()
+            per_pass[kind] = round(1000.0 * (time.perf_counter() - t1) / 5, 3)
 
     roofline, kernels = None, None
-    if not args.no_kernel_timing:
+    if args.full and not args.no_kernel_timing:
         # EVERY rank runs the instrumented passes (they contain the gradient exchange: a rank that skipped them
         # would leave the others waiting in a collective); rank 0 reports
         log("kernel timing pass")
@@ -784,7 +854,7 @@ def main():
             roofline, kernels = roofline_of(fam)
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         log("cpu baseline (oracle)")
         cpu = cpu_baseline(args)
         log("cpu baseline done: %s" % cpu["value"])

@@ -363,6 +363,29 @@ def test_sharded_update_is_opt_in():
     assert bench.parse(["--zero1", "1"]).zero1 == 1 and bench.parse(["--zero1", "0"]).zero1 == 0 and bench.parse([]).zero1 is None
 
 
+def test_bench_options_and_output_dump(tmp_path):
+    """a plain ``bench.py`` run is lean (``--full`` is off by default) and ``--dump-outputs`` writes float32 arrays
+    (float64 stays float64) from a fixed, seeded sample, refusing more than 64 MB."""
+    import importlib
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    bench = importlib.import_module("bench")
+    a = bench.parse([])
+    assert a.full is False and a.dump_outputs is None and (a.steps, a.warmup) == (20, 5)
+    a = bench.parse(["--full", "--dump-outputs", str(tmp_path), "--steps", "7"])
+    assert a.full is True and a.dump_outputs == str(tmp_path) and a.steps == 7
+    i1, i2 = bench.sample_index(10 ** 7), bench.sample_index(10 ** 7)
+    assert torch.equal(i1, i2) and i1.numel() == bench.DUMP_SAMPLE and bool((i1[1:] > i1[:-1]).all())
+    assert bench.sample_index(100) is None
+    x = torch.arange(12, dtype=torch.bfloat16).view(3, 4)
+    bench.dump_outputs(str(tmp_path), {"x": x, "y": torch.ones(2, dtype=torch.float64)})
+    assert np.load(str(tmp_path / "x.npy")).dtype == np.float32 and np.load(str(tmp_path / "y.npy")).dtype == np.float64
+    assert np.array_equal(np.load(str(tmp_path / "x.npy")), x.float().numpy())
+    with pytest.raises(SystemExit):
+        bench.dump_outputs(str(tmp_path / "big"), {"z": torch.zeros(17 << 20)})
+
+
 def test_sharded_update_bookkeeping_world2():
     """ZeRO-1 host logic over gloo (world size 2, CPU tensors): runs cut at the groups' matrix / vector borders, the
     own slices, the in-place exchange on the wire arena (matrices reduced where the GEMMs wrote them, vectors cast in

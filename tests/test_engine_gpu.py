@@ -308,7 +308,7 @@ def test_bench_on_a_one_rank_rccl_group(zero1):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, XGGM_DP_FORCE="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()))
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
                         "--no-kernel-timing", "--no-ref-batch", "--zero1", str(zero1)], capture_output=True, text=True,
                        timeout=900, env=env, cwd=root)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
@@ -343,7 +343,7 @@ def test_bench_gpus_2_spawns_two_ranks(order, zero1):
     of the real N = 2 run, only the transport differs.  ``gqa``: BASELINE configs[2]'s data-parallel workload
     (GQA-OOD-shaped: GGM pass first, KL x 12, A = 1842) in its default configuration (replicated update)."""
     extra = ["--order", "gqa"] if order == "gqa" else []
-    line = _run_bench(["--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "8", "--no-cpu-baseline",
+    line = _run_bench(["--full", "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "8", "--no-cpu-baseline",
                        "--no-kernel-timing", "--zero1", str(zero1)] + extra, {"XGGM_DIST_BACKEND": "gloo", "XGGM_SHARE_GPU": "1"})
     assert line["n_gpus"] == 2 and line["config"]["world_size"] == 2 and line["config"]["backend"] == "gloo"
     assert line["config"]["zero1"] is bool(zero1) and line["config"]["order"] == order
@@ -351,6 +351,34 @@ def test_bench_gpus_2_spawns_two_ranks(order, zero1):
     assert line["config"]["global_batch"] == 16 and line["config"]["parallelism"] == "dp2"
     assert line["value"] > 0 and line["scaling"] == "weak" and line["steps"] == 2
     assert line["value_with_loader"]["value"] > 0 and line["value_ref_batch"] is None
+
+
+def test_bench_plain_run_dumps_what_the_full_run_computes(tmp_path):
+    """A plain run times the steps and nothing else (the diagnostic legs are null on its line); ``--dump-outputs`` writes
+    the last timed step's results as float32 arrays.  A ``--full`` run (whose trainer takes the loader's slot layout)
+    computes the same timed steps on the same seeded inputs: the two dumps are equal bit for bit."""
+    import os
+    dumps = []
+    for extra in ([], ["--full", "--no-cpu-baseline", "--no-kernel-timing", "--no-ref-batch"]):
+        d = str(tmp_path / ("full" if extra else "plain"))
+        line = _run_bench(["--steps", "3", "--warmup", "1", "--dump-outputs", d] + extra)
+        assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["value"] > 0
+        assert line["unit"] == "samples/s" and line["higher_is_better"] is True and line["dtype"] == "bf16"
+        lean = ("value_with_loader", "value_ref_batch", "ms_per_step_by_branch", "ms_per_pass", "roofline", "kernels",
+                "cpu_baseline")
+        if extra:
+            assert line["value_with_loader"]["value"] > 0 and set(line["ms_per_pass"]) == {"plain", "rel", "node"}
+        else:
+            assert all(line[k] is None for k in lean), {k: line[k] for k in lean}
+        names = sorted(f for f in os.listdir(d) if f.endswith(".npy"))
+        arrays = {f: np.load(os.path.join(d, f)) for f in names}
+        assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrays.values())
+        assert arrays["plain_logit.npy"].shape == (32, 2274) and arrays["sample_params.npy"].shape == (1 << 20,)
+        dumps.append(arrays)
+    assert list(dumps[0]) == list(dumps[1])
+    for f in dumps[0]:
+        assert np.array_equal(dumps[0][f], dumps[1][f]), f
 
 
 def test_bench_rejects_a_world_size_that_contradicts_gpus():
@@ -366,7 +394,7 @@ def test_bench_rejects_a_world_size_that_contradicts_gpus():
 
 def test_bench_gqa_order_line():
     """BASELINE configs[2] per GPU: GQA-OOD-shaped workload (GGM pass first, KL x 12, A = 1842; src/gqa/gqa_ood.py:165-292)"""
-    line = _run_bench(["--gpus", "1", "--order", "gqa", "--answers", "1842", "--steps", "3", "--warmup", "1",
+    line = _run_bench(["--full", "--gpus", "1", "--order", "gqa", "--answers", "1842", "--steps", "3", "--warmup", "1",
                        "--no-cpu-baseline"])
     assert line["n_gpus"] == 1 and line["config"]["order"] == "gqa" and "A=1842" in line["config"]["workload"]
     assert "GGM pass first" in line["config"]["workload"] and line["value"] > 0
@@ -376,14 +404,15 @@ def test_bench_gqa_order_line():
 def test_bench_fp8_line():
     """BASELINE configs[4] per GPU: e4m3 operands in the forward QKV / attention-output / FFN products, bf16 GNN and
     backward (src/lxrt/modeling.py:345-347, 428-431, 441-445 are the products that change type)"""
-    line = _run_bench(["--dtype", "fp8", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-loader", "--no-ref-batch"])
+    line = _run_bench(["--full", "--dtype", "fp8", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-loader",
+                       "--no-ref-batch"])
     assert line["dtype"] == "fp8" and line["n_gpus"] == 1 and line["value"] > 0 and "fp8" in line["config"]["workload"]
     assert "xggm_gemm_grouped_fp8e4m3" in line["kernels"] or any("fp8" in k for k in line["kernels"]), line["kernels"]
 
 
 def test_bench_c4_stress_line():
     """BASELINE configs[3]: 64 objects x 64 adjacency, batch 64, aggregate kernel against the HBM roofline"""
-    line = _run_bench(["--workload", "c4", "--steps", "10", "--warmup", "2"])
+    line = _run_bench(["--full", "--workload", "c4", "--steps", "10", "--warmup", "2"])
     assert line["config"]["global_batch"] == 64 and "64 objects" in line["config"]["workload"]
     rf = line["roofline"]
     assert rf["kernel"] == "xggm_aggregate_bf16" and rf["bound"] == "hbm" and rf["unit"] == "GB/s" and rf["achieved"] > 0

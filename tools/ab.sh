@@ -6,7 +6,7 @@ ROOT="$(cd "$(dirname "$0")/.." && pwd)"
 for i in $(seq $N); do
   for v in base alt; do
     if [ $v = alt ]; then export XGGM_LIB="$ROOT/x-ggm_amd/csrc/build_alt/libxggm_hip.so"; else unset XGGM_LIB; fi
-    python "$ROOT/bench.py" --no-cpu-baseline --no-kernel-timing 2>/dev/null | python -c "
+    python "$ROOT/bench.py" --full --no-cpu-baseline --no-kernel-timing 2>/dev/null | python -c "
 import json,sys
 for l in sys.stdin:
     if l.startswith('{'):

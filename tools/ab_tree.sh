@@ -7,7 +7,7 @@ ROOT="$(cd "$(dirname "$0")/.." && pwd)"
 for i in $(seq $N); do
   for v in base new; do
     if [ $v = base ]; then D="$ROOT/_base"; else D="$ROOT"; fi
-    (cd $D && python bench.py --no-cpu-baseline --no-kernel-timing 2>/dev/null) | python -c "
+    (cd $D && python bench.py --full --no-cpu-baseline --no-kernel-timing 2>/dev/null) | python -c "
 import json,sys
 for l in sys.stdin:
     if l.startswith('{'):

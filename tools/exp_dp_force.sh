@@ -4,7 +4,7 @@ for m in plain force force_z1; do
   unset XGGM_DP_FORCE; Z=""
   if [ $m != plain ]; then export XGGM_DP_FORCE=1 MASTER_ADDR=127.0.0.1 MASTER_PORT=29577; fi
   if [ $m = force_z1 ]; then Z="--zero1 1"; fi
-  python bench.py $Z --no-cpu-baseline --no-kernel-timing --no-loader --no-ref-batch 2>/dev/null | python -c "
+  python bench.py --full $Z --no-cpu-baseline --no-kernel-timing --no-loader --no-ref-batch 2>/dev/null | python -c "
 import json,sys
 for l in sys.stdin:
     if l.startswith('{'):

@@ -1,6 +1,7 @@
 # per-shape GEMM times (eager HIP events, XGGM_DUMP_GEMMS) with the grouped tile pinned: which launches want which tile
-mkdir -p gpurun_out/r3c
+OUT=${1:?usage: tools/exp_group_tile.sh OUTPUT_DIR}
+mkdir -p "$OUT"
 for t in 0 1 2 4; do
-  XGGM_DUMP_GEMMS=1 XGGM_GROUP_TILE=$t python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-loader --no-ref-batch > /dev/null 2> gpurun_out/r3c/dump_tile$t.txt
+  XGGM_DUMP_GEMMS=1 XGGM_GROUP_TILE=$t python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-loader --no-ref-batch > /dev/null 2> "$OUT/dump_tile$t.txt"
 done
-grep -c gemm gpurun_out/r3c/dump_tile0.txt
+grep -c gemm "$OUT/dump_tile0.txt"

@@ -2,7 +2,7 @@
 for i in 1 2 3; do
 for v in off on; do
   if [ $v = off ]; then export XGGM_PREFETCH=0; else unset XGGM_PREFETCH; fi
-  python bench.py --no-cpu-baseline --no-kernel-timing --no-loader --no-ref-batch "$@" 2>/dev/null | python -c "
+  python bench.py --full --no-cpu-baseline --no-kernel-timing --no-loader --no-ref-batch "$@" 2>/dev/null | python -c "
 import json,sys
 for l in sys.stdin:
     if l.startswith('{'):
