@@ -16,7 +16,9 @@
  *    [B,N,N], losses and optimiser state are always fp32.
  *  - Return value: 0 = ok; non-zero = error, message via xggm_last_error() (thread-local).
  *    Reentrant and thread-safe: called from the host thread in forward and from the
- *    autograd thread in backward.
+ *    autograd thread in backward.  All launch state travels in the arguments; the only
+ *    process-wide state are the A/B hooks xggm_gemm_set_tile, xggm_gemm_set_group_tile,
+ *    xggm_gemm_set_generic, xggm_attn_set_scalar and the instrumented build's stamp / ablation hooks.
  *  - Randomness: `rng` points to two device uint64 {seed, offset}; dropout masks and
  *    Gaussian draws are pure functions of (seed, offset, stream id `sid`, element index), so
  *    backward regenerates the forward mask.  xggm_rng_advance() bumps the offset once per
@@ -50,12 +52,12 @@ typedef struct ihipStream_t* xggm_stream_t; /* == hipStream_t */
 
 int xggm_version(void);
 const char* xggm_last_error(void);
-/* HOST: queue a byte range (16-byte aligned; at most four per launch) that the NEXT xggm_ln_fwd_grouped_* /
- * xggm_ln_bwd_grouped_* / bf16 xggm_attn_fwd_grouped / xggm_attn_bwd_grouped launch reads beside its own work and
- * discards: the weights of the Linear products that follow (src/lxrt/modeling.py:344-347, 384-388, 428-445) are then in
- * the Infinity Cache when those products ask for them.  Speed only -- nothing is written, no result depends on it;
- * XGGM_PREFETCH=0 in the environment makes this a no-op. */
-int xggm_prefetch_next(const void* ptr, size_t bytes);
+/* Weight prefetch: up to four byte ranges (each non-null, 16-byte aligned, >= 16 bytes) that the FIRST carrier kernel
+ * launched by an xggm_ln_fwd_grouped_* / xggm_ln_bwd_grouped_* / xggm_attn_*_grouped_* call (argument `prefetch`, NULL =
+ * none) reads beside its own work and discards: the weights of the Linear products that follow
+ * (src/lxrt/modeling.py:344-347, 384-388, 428-445) are then in the Infinity Cache.  Speed only -- no result depends on
+ * it.  The scalar attention kernels (fp32 storage, unaligned bf16 operands) read none. */
+typedef struct xggm_prefetch { const void* ptr[4]; size_t bytes[4]; int n; } xggm_prefetch;
 
 /* ---- dense products --------------------------------------------------------------------
  * C[z][m][n] = epilogue( alpha * sum_k A(z,m,k) * B(z,k,n) ),
@@ -232,10 +234,14 @@ typedef struct xggm_attn_problem {
     float* amax;
     int amax_slots; /* see xggm_gemm_problem.amax_slots */
 } xggm_attn_problem;
-int xggm_attn_fwd_grouped_f32(const xggm_attn_problem* probs, int n, int head_dim, const uint64_t* rng, xggm_stream_t stream);
-int xggm_attn_fwd_grouped_bf16(const xggm_attn_problem* probs, int n, int head_dim, const uint64_t* rng, xggm_stream_t stream);
-int xggm_attn_bwd_grouped_f32(const xggm_attn_problem* probs, int n, int head_dim, const uint64_t* rng, xggm_stream_t stream);
-int xggm_attn_bwd_grouped_bf16(const xggm_attn_problem* probs, int n, int head_dim, const uint64_t* rng, xggm_stream_t stream);
+int xggm_attn_fwd_grouped_f32(const xggm_attn_problem* probs, int n, int head_dim, const uint64_t* rng,
+                              const xggm_prefetch* prefetch, xggm_stream_t stream);
+int xggm_attn_fwd_grouped_bf16(const xggm_attn_problem* probs, int n, int head_dim, const uint64_t* rng,
+                               const xggm_prefetch* prefetch, xggm_stream_t stream);
+int xggm_attn_bwd_grouped_f32(const xggm_attn_problem* probs, int n, int head_dim, const uint64_t* rng,
+                              const xggm_prefetch* prefetch, xggm_stream_t stream);
+int xggm_attn_bwd_grouped_bf16(const xggm_attn_problem* probs, int n, int head_dim, const uint64_t* rng,
+                               const xggm_prefetch* prefetch, xggm_stream_t stream);
 
 /* HOST: 1 = run bf16 attention on the scalar kernels (A/B tests), 0 = matrix-core kernels */
 int xggm_attn_set_scalar(int on);
@@ -309,13 +315,15 @@ typedef struct xggm_ln_bwd_problem {
     int accumulate_dres;
 } xggm_ln_bwd_problem;
 int xggm_ln_fwd_grouped_f32(const xggm_ln_fwd_problem* probs, int n, int H, float eps, float p_pre, float p_post,
-                            const uint64_t* rng, int accumulate, float out_scale, xggm_stream_t stream);
+                            const uint64_t* rng, int accumulate, float out_scale, const xggm_prefetch* prefetch,
+                            xggm_stream_t stream);
 int xggm_ln_fwd_grouped_bf16(const xggm_ln_fwd_problem* probs, int n, int H, float eps, float p_pre, float p_post,
-                             const uint64_t* rng, int accumulate, float out_scale, xggm_stream_t stream);
+                             const uint64_t* rng, int accumulate, float out_scale, const xggm_prefetch* prefetch,
+                             xggm_stream_t stream);
 int xggm_ln_bwd_grouped_f32(const xggm_ln_bwd_problem* probs, int n, int H, float p_pre, float p_post,
-                            const uint64_t* rng, float out_scale, xggm_stream_t stream);
+                            const uint64_t* rng, float out_scale, const xggm_prefetch* prefetch, xggm_stream_t stream);
 int xggm_ln_bwd_grouped_bf16(const xggm_ln_bwd_problem* probs, int n, int H, float p_pre, float p_post,
-                             const uint64_t* rng, float out_scale, xggm_stream_t stream);
+                             const uint64_t* rng, float out_scale, const xggm_prefetch* prefetch, xggm_stream_t stream);
 /* out = sum over n <= 4 terms of dropout_p_post(LayerNorm(in[k]; gamma[k], beta[k], eps)) in ONE launch: the
  * jump-knowledge read-out of the graph blocks (src/module/gcn.py:70-77, src/module/gin.py:80-87).  The sum is held in
  * fp32 and rounded once.  stats[k] (or NULL): [M][2] (mean, rstd) of term k for xggm_ln_bwd_* (whose `z` is in[k] itself:

@@ -47,6 +47,20 @@ def test_argument_validation_fails_before_launch():
     assert rc != 0 and b"64" in L.xggm_last_error()
     rc = L.xggm_adj_init_fwd(None, None, None, None, 2, 36, 0.0, None, 0, None)
     assert rc != 0
+    # weight-prefetch ranges of the row / attention launches: at most four, each non-null, 16-byte aligned, >= 16 bytes
+    from xggm_amd import ops
+    ln_f, ln_b, at = (ops.LnFwdProblem * 1)(), (ops.LnBwdProblem * 1)(), (ops.AttnProblem * 1)()
+    carriers = [lambda pf: L.xggm_ln_fwd_grouped_bf16(ctypes.addressof(ln_f), 1, 768, 1e-12, 0.0, 0.0, None, 0, 1.0, pf, None),
+                lambda pf: L.xggm_ln_bwd_grouped_f32(ctypes.addressof(ln_b), 1, 768, 0.0, 0.0, None, 1.0, pf, None),
+                lambda pf: L.xggm_attn_fwd_grouped_bf16(ctypes.addressof(at), 1, 64, None, pf, None),
+                lambda pf: L.xggm_attn_bwd_grouped_f32(ctypes.addressof(at), 1, 64, None, pf, None)]
+    for n, p0, nb in ((5, 4096, 4096), (1, 4096 + 8, 4096), (1, 4096, 0), (1, None, 4096)):
+        pf = ops.Prefetch()
+        pf.n = n
+        for i in range(4):
+            pf.ptr[i], pf.bytes[i] = p0, nb
+        for launch in carriers:
+            assert launch(ctypes.byref(pf)) != 0 and b"prefetch range" in L.xggm_last_error(), (n, p0, nb)
 
 
 def test_triu_index_map_is_the_reference_enumeration():

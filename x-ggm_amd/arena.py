@@ -227,7 +227,7 @@ class ParamArena:
     def after(self, p, n, use8=False, skip=0):
         """the (up to) ``n`` weight elements that FOLLOW parameter ``p`` in the buffer the products read (bf16 shadow, or
         the e4m3 copies with ``use8``), inside its group's matrix region: matrices are laid out in forward order within a
-        backward-stage region, so this is what the next products of the forward will ask for (``ops.prefetch_next``).
+        backward-stage region, so this is what the next products of the forward will ask for (``ops.prefetch_ranges``).
         None without a shadow (fp32 mode) or at the end of the region."""
         buf = (self.fp8.shadow8 if (use8 and self.fp8 is not None) else self.shadow)
         if buf is None:

@@ -11,8 +11,8 @@
 #include "xggm.h"
 
 // bf16 matrix-core versions (attention_mfma.hip): one or two validated problems per launch
-int xggm_attn_fwd_mfma_group(const xggm_attn_problem* probs, int n, const uint64_t* rng, hipStream_t st);
-int xggm_attn_bwd_mfma_group(const xggm_attn_problem* probs, int n, const uint64_t* rng, hipStream_t st);
+int xggm_attn_fwd_mfma_group(const xggm_attn_problem* probs, int n, const uint64_t* rng, const PrefetchArgs& pf, hipStream_t st);
+int xggm_attn_bwd_mfma_group(const xggm_attn_problem* probs, int n, const uint64_t* rng, const PrefetchArgs& pf, hipStream_t st);
 
 namespace {
 
@@ -252,10 +252,13 @@ inline AttnArgs args_of(const xggm_attn_problem& q, const uint64_t* rng) {
     return AttnArgs{q.q, q.k, q.v, q.mask, q.q_rs, q.k_rs, q.v_rs, q.o_rs, q.B, q.heads, q.Sq, q.Sk, q.scale, q.p, rng, q.sid};
 }
 
-// problems that can run on the matrix-core kernels are launched in pairs, the rest one by one
+// problems that can run on the matrix-core kernels are launched in pairs (the first pair carries `prefetch`), the rest one by one
 template <typename T>
-int attn_fwd_grouped(const xggm_attn_problem* probs, int n, int head_dim, const uint64_t* rng, hipStream_t st) {
+int attn_fwd_grouped(const xggm_attn_problem* probs, int n, int head_dim, const uint64_t* rng, const xggm_prefetch* prefetch,
+                     hipStream_t st) {
     XGGM_REQUIRE(probs && n > 0, "xggm_attn_fwd: no problems");
+    PrefetchArgs pf;
+    if (int e = xggm_prefetch_args(prefetch, &pf, "xggm_attn_fwd")) return e;
     xggm_attn_problem pend[2];
     int np = 0;
     for (int i = 0; i < n; ++i) {
@@ -268,8 +271,9 @@ int attn_fwd_grouped(const xggm_attn_problem* probs, int n, int head_dim, const 
         if (sizeof(T) == 2 && mfma_ok(q.q, q.k, q.v, q.out, q.q_rs, q.k_rs, q.v_rs, q.o_rs)) {
             pend[np++] = q;
             if (np == 2 || i == n - 1) {
-                if (int e = xggm_attn_fwd_mfma_group(pend, np, rng, st)) return e;
+                if (int e = xggm_attn_fwd_mfma_group(pend, np, rng, pf, st)) return e;
                 np = 0;
+                pf = PrefetchArgs{};
             }
             continue;
         }
@@ -279,13 +283,16 @@ int attn_fwd_grouped(const xggm_attn_problem* probs, int n, int head_dim, const 
         hipLaunchKernelGGL((attn_fwd_kernel<T>), dim3(q.B * q.heads), dim3(NT), lds, st, a, (T*)q.out);
         if (int e = xggm_check_launch("xggm_attn_fwd")) return e;
     }
-    if (np) return xggm_attn_fwd_mfma_group(pend, np, rng, st);
+    if (np) return xggm_attn_fwd_mfma_group(pend, np, rng, pf, st);
     return XGGM_OK;
 }
 
 template <typename T>
-int attn_bwd_grouped(const xggm_attn_problem* probs, int n, int head_dim, const uint64_t* rng, hipStream_t st) {
+int attn_bwd_grouped(const xggm_attn_problem* probs, int n, int head_dim, const uint64_t* rng, const xggm_prefetch* prefetch,
+                     hipStream_t st) {
     XGGM_REQUIRE(probs && n > 0, "xggm_attn_bwd: no problems");
+    PrefetchArgs pf;
+    if (int e = xggm_prefetch_args(prefetch, &pf, "xggm_attn_bwd")) return e;
     xggm_attn_problem pend[2];
     int np = 0;
     for (int i = 0; i < n; ++i) {
@@ -302,8 +309,9 @@ int attn_bwd_grouped(const xggm_attn_problem* probs, int n, int head_dim, const 
         if (sizeof(T) == 2 && grads8 && mfma_ok(q.q, q.k, q.v, q.d_out, q.q_rs, q.k_rs, q.v_rs, q.o_rs)) {  // 8-byte gradient stores
             pend[np++] = q;
             if (np == 2 || i == n - 1) {
-                if (int e = xggm_attn_bwd_mfma_group(pend, np, rng, st)) return e;
+                if (int e = xggm_attn_bwd_mfma_group(pend, np, rng, pf, st)) return e;
                 np = 0;
+                pf = PrefetchArgs{};
             }
             continue;
         }
@@ -312,7 +320,7 @@ int attn_bwd_grouped(const xggm_attn_problem* probs, int n, int head_dim, const 
                            (T*)q.dv, q.dq_rs, q.dk_rs, q.dv_rs, q.dbq, q.dbk, q.dbv, q.db_bs);
         if (int e = xggm_check_launch("xggm_attn_bwd")) return e;
     }
-    if (np) return xggm_attn_bwd_mfma_group(pend, np, rng, st);
+    if (np) return xggm_attn_bwd_mfma_group(pend, np, rng, pf, st);
     return XGGM_OK;
 }
 
@@ -325,7 +333,7 @@ int attn_fwd(const void* q, const void* k, const void* v, const float* mask, voi
     pr.B = B; pr.heads = heads; pr.Sq = Sq; pr.Sk = Sk;
     pr.q_rs = q_rs; pr.k_rs = k_rs; pr.v_rs = v_rs; pr.o_rs = o_rs;
     pr.scale = scale; pr.p = p; pr.sid = sid;
-    return attn_fwd_grouped<T>(&pr, 1, head_dim, rng, st);
+    return attn_fwd_grouped<T>(&pr, 1, head_dim, rng, nullptr, st);
 }
 
 template <typename T>
@@ -341,7 +349,7 @@ int attn_bwd(const void* q, const void* k, const void* v, const float* mask, con
     pr.d_out = d_out; pr.dq = dq; pr.dk = dk; pr.dv = dv;
     pr.dq_rs = dq_rs; pr.dk_rs = dk_rs; pr.dv_rs = dv_rs;
     pr.dbq = dbq; pr.dbk = dbk; pr.dbv = dbv; pr.db_bs = db_bs;
-    return attn_bwd_grouped<T>(&pr, 1, head_dim, rng, st);
+    return attn_bwd_grouped<T>(&pr, 1, head_dim, rng, nullptr, st);
 }
 
 }  // namespace
@@ -363,12 +371,12 @@ int attn_bwd(const void* q, const void* k, const void* v, const float* mask, con
                            dk_rs, dv_rs, scale, p, rng, sid, dbq, dbk, dbv, db_bs, st);                                    \
     }                                                                                                                      \
     extern "C" int xggm_attn_fwd_grouped_##SUF(const xggm_attn_problem* probs, int n, int head_dim, const uint64_t* rng,   \
-                                               hipStream_t st) {                                                          \
-        return attn_fwd_grouped<T>(probs, n, head_dim, rng, st);                                                           \
+                                               const xggm_prefetch* prefetch, hipStream_t st) {                           \
+        return attn_fwd_grouped<T>(probs, n, head_dim, rng, prefetch, st);                                                 \
     }                                                                                                                      \
     extern "C" int xggm_attn_bwd_grouped_##SUF(const xggm_attn_problem* probs, int n, int head_dim, const uint64_t* rng,   \
-                                               hipStream_t st) {                                                          \
-        return attn_bwd_grouped<T>(probs, n, head_dim, rng, st);                                                           \
+                                               const xggm_prefetch* prefetch, hipStream_t st) {                           \
+        return attn_bwd_grouped<T>(probs, n, head_dim, rng, prefetch, st);                                                 \
     }
 
 ATTN_API(f32, float)

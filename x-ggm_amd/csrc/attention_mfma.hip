@@ -50,7 +50,7 @@ struct MSeg {
 struct MGroup {
     MSeg s[2];
     int start1;
-    int total;        // workgroups of the two segments; the ones behind them read the queued weight ranges (common.h)
+    int total;        // workgroups of the two segments; the ones behind them read the weight ranges of `pf` (common.h)
     PrefetchArgs pf;
 #ifdef XGGM_STAMP
     long long* stamp;
@@ -528,10 +528,6 @@ __global__ __launch_bounds__(NT) void attn_bwd_mfma_kernel(MGroup G) {
     }
 }
 
-template <typename K> void allow_big_lds(K kernel, size_t lds) {
-    if (lds > 48 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-}
-
 }  // namespace
 
 // called by attention.hip for bf16 storage (arguments already validated there): n = 1 or 2 problems
@@ -551,9 +547,26 @@ MSeg make_seg(const xggm_attn_problem& q, const uint64_t* rng) {
     g.dbq = q.dbq; g.dbk = q.dbk; g.dbv = q.dbv; g.db_bs = q.db_bs;
     return g;
 }
+
+// one launch of G's one or two segments (`total` workgroups), the ranges of `pf` on top
+template <typename K>
+int launch_group(K kernel, MGroup& G, int n, int total, size_t lds, const PrefetchArgs& pf, hipStream_t st, const char* who) {
+    if (n == 1) {
+        G.s[1] = G.s[0];
+        G.start1 = total;
+    }
+#ifdef XGGM_STAMP
+    G.stamp = g_attn_stamp;
+#endif
+    if (int e = xggm_reserve_lds(reinterpret_cast<const void*>(kernel), lds, who)) return e;
+    G.total = total;
+    G.pf = pf;
+    hipLaunchKernelGGL(kernel, dim3(total + pf.blocks), dim3(NT), lds, st, G);
+    return xggm_check_launch(who);
+}
 }  // namespace
 
-int xggm_attn_fwd_mfma_group(const xggm_attn_problem* probs, int n, const uint64_t* rng, hipStream_t st) {
+int xggm_attn_fwd_mfma_group(const xggm_attn_problem* probs, int n, const uint64_t* rng, const PrefetchArgs& pf, hipStream_t st) {
     MGroup G;
     size_t lds = 0;
     int total = 0;
@@ -565,21 +578,10 @@ int xggm_attn_fwd_mfma_group(const xggm_attn_problem* probs, int n, const uint64
         if (i == 1) G.start1 = total;
         total += q.B * q.heads;
     }
-    if (n == 1) {
-        G.s[1] = G.s[0];
-        G.start1 = total;
-    }
-#ifdef XGGM_STAMP
-    G.stamp = g_attn_stamp;
-#endif
-    allow_big_lds(attn_fwd_mfma_kernel, lds);
-    G.total = total;
-    G.pf = xggm_take_prefetch();
-    hipLaunchKernelGGL(attn_fwd_mfma_kernel, dim3(total + G.pf.blocks), dim3(NT), lds, st, G);
-    return xggm_check_launch("xggm_attn_fwd(mfma)");
+    return launch_group(attn_fwd_mfma_kernel, G, n, total, lds, pf, st, "xggm_attn_fwd(mfma)");
 }
 
-int xggm_attn_bwd_mfma_group(const xggm_attn_problem* probs, int n, const uint64_t* rng, hipStream_t st) {
+int xggm_attn_bwd_mfma_group(const xggm_attn_problem* probs, int n, const uint64_t* rng, const PrefetchArgs& pf, hipStream_t st) {
     MGroup G;
     size_t lds = 0;
     int total = 0;
@@ -593,18 +595,7 @@ int xggm_attn_bwd_mfma_group(const xggm_attn_problem* probs, int n, const uint64
         if (i == 1) G.start1 = total;
         total += q.B * q.heads;
     }
-    if (n == 1) {
-        G.s[1] = G.s[0];
-        G.start1 = total;
-    }
-#ifdef XGGM_STAMP
-    G.stamp = g_attn_stamp;
-#endif
-    allow_big_lds(attn_bwd_mfma_kernel, lds);
-    G.total = total;
-    G.pf = xggm_take_prefetch();
-    hipLaunchKernelGGL(attn_bwd_mfma_kernel, dim3(total + G.pf.blocks), dim3(NT), lds, st, G);
-    return xggm_check_launch("xggm_attn_bwd(mfma)");
+    return launch_group(attn_bwd_mfma_kernel, G, n, total, lds, pf, st, "xggm_attn_bwd(mfma)");
 }
 
 #ifdef XGGM_STAMP

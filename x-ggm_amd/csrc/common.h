@@ -8,6 +8,7 @@
 #include <math.h>
 #include <algorithm>
 #include <type_traits>
+struct xggm_prefetch;  // xggm.h
 
 #define XGGM_OK 0
 #define XGGM_ERR_ARG 1
@@ -18,6 +19,8 @@ typedef __hip_bfloat16 bf16;
 // ---------------------------------------------------------------- error reporting
 void xggm_set_error(const char* fmt, ...);
 int xggm_check_launch(const char* what);
+// host: `bytes` of dynamic LDS for `kernel` on the current device (past 48 KB: the driver's opt-in, once per size and device)
+int xggm_reserve_lds(const void* kernel, size_t bytes, const char* who);
 
 #define XGGM_REQUIRE(cond, ...)            \
     do {                                   \
@@ -289,9 +292,9 @@ static inline int64_t ceil_div64(int64_t a, int64_t b) { return (a + b - 1) / b;
 // The step's products wait for weights nobody has touched since the previous pass: tools/exp_weight_prefetch.py puts a
 // launch whose weights already sit in the Infinity Cache 0.3 ... 1.5 us ahead of one that fetches them from HBM.  The
 // kernels between those products -- attention cores, LayerNorm forward / backward -- leave most workgroup slots of the
-// chip empty for microseconds of latency: xggm_prefetch_next() queues up to four byte ranges on the host, the next such
-// launch takes them, appends `blocks` workgroups to its grid, and those read the ranges with plain loads (which
-// allocate on the way) and discard them.  No result depends on it; XGGM_PREFETCH=0 turns the queue into a no-op.
+// chip empty for microseconds of latency: such a launch takes up to four byte ranges as an argument (xggm_prefetch),
+// appends `blocks` workgroups to its grid, and those read the ranges with plain loads (which allocate on the way) and
+// discard them.  No result depends on it.
 // What a carrier can take without becoming longer itself was measured (profiles/r04_experiments/prefetch.txt): 19 MB
 // in one LayerNorm launch made the launch 1.8-2.3 us longer and gave back what the products had gained; the same reads
 // on a side stream cost 0.9 ms per iteration in graph branches.  Hence <= ~9 MB per LayerNorm launch, the rest on the
@@ -300,10 +303,11 @@ struct PrefetchArgs {
     const void* p[4];
     unsigned long long n[4];  // bytes (whole 16-byte chunks are read)
     int k;                    // ranges
-    int blocks;               // workgroups appended to the grid (0: nothing queued)
+    int blocks;               // workgroups appended to the grid (0: no ranges)
     int* sink;                // never written in practice: keeps the loads alive
 };
-PrefetchArgs xggm_take_prefetch();  // host: the queued ranges (the queue is cleared)
+// host: the kernel arguments of the ranges `r` (NULL: none), XGGM_ERR_ARG for ranges that break the rules of xggm.h
+int xggm_prefetch_args(const xggm_prefetch* r, PrefetchArgs* a, const char* who);
 
 __device__ __forceinline__ void prefetch_role(const PrefetchArgs& pf, int b) {
     typedef int i4 __attribute__((ext_vector_type(4)));

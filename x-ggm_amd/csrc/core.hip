@@ -1,6 +1,8 @@
-// error reporting + version for libxggm_hip.so
+// error reporting, version and host-side launch helpers for libxggm_hip.so
 #include "common.h"
 #include "xggm.h"
+#include <map>
+#include <mutex>
 
 static thread_local char g_err[512] = "";
 
@@ -23,31 +25,39 @@ int xggm_check_launch(const char* what) {
 extern "C" int xggm_version(void) { return XGGM_VERSION; }
 extern "C" const char* xggm_last_error(void) { return g_err; }
 
-// ---- prefetch queue (common.h: PrefetchArgs)
-static PrefetchArgs g_prefetch = {{nullptr, nullptr, nullptr, nullptr}, {0, 0, 0, 0}, 0, 0, nullptr};
-static int g_prefetch_on = -1;
-
-extern "C" int xggm_prefetch_next(const void* ptr, size_t bytes) {
-    if (g_prefetch_on < 0) {
-        const char* e = getenv("XGGM_PREFETCH");
-        g_prefetch_on = (e && atoi(e) == 0) ? 0 : 1;
+int xggm_prefetch_args(const xggm_prefetch* r, PrefetchArgs* a, const char* who) {
+    *a = PrefetchArgs{};
+    if (!r) return XGGM_OK;
+    XGGM_REQUIRE(r->n >= 0 && r->n <= 4, "%s: %d prefetch ranges (0..4)", who, r->n);
+    unsigned long long total = 0;
+    for (int i = 0; i < r->n; ++i) {
+        XGGM_REQUIRE(r->ptr[i] && reinterpret_cast<uintptr_t>(r->ptr[i]) % 16 == 0 && r->bytes[i] >= 16,
+                     "%s: prefetch range %d must be non-null, start on a 16-byte border and hold at least 16 bytes", who, i);
+        a->p[i] = r->ptr[i]; a->n[i] = r->bytes[i];
+        total += a->n[i];
     }
-    if (!g_prefetch_on || !ptr || bytes < 16) return XGGM_OK;
-    XGGM_REQUIRE(reinterpret_cast<uintptr_t>(ptr) % 16 == 0, "xggm_prefetch_next: the range must start on a 16-byte border");
-    if (g_prefetch.k < 4) {
-        g_prefetch.p[g_prefetch.k] = ptr;
-        g_prefetch.n[g_prefetch.k] = bytes;
-        ++g_prefetch.k;
-    }  // a fifth range is dropped: the queue belongs to the next launch, which has room for four
+    a->k = r->n;
+    a->blocks = (int)std::min<unsigned long long>(256, (total + 49151) / 49152);  // ~48 KB per workgroup, at most one per CU
     return XGGM_OK;
 }
 
-PrefetchArgs xggm_take_prefetch() {
-    PrefetchArgs a = g_prefetch;
-    unsigned long long total = 0;
-    for (int i = 0; i < a.k; ++i) total += a.n[i];
-    // ~48 KB per workgroup, at most one workgroup per CU
-    a.blocks = a.k ? (int)std::min<unsigned long long>(256, (total + 49151) / 49152) : 0;
-    g_prefetch.k = 0;
-    return a;
+int xggm_reserve_lds(const void* kernel, size_t bytes, const char* who) {
+    if (bytes <= 48 * 1024) return XGGM_OK;
+    static std::mutex mu;
+    static std::map<std::pair<const void*, int>, size_t> granted;  // (kernel, device) -> largest reservation so far
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e == hipSuccess) {
+        std::lock_guard<std::mutex> lock(mu);
+        size_t& have = granted[{kernel, dev}];
+        if (bytes > have) {
+            e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+            if (e == hipSuccess) have = bytes;
+        }
+    }
+    if (e != hipSuccess) {
+        xggm_set_error("%s: cannot reserve %zu bytes of LDS: %s", who, bytes, hipGetErrorString(e));
+        return XGGM_ERR_LAUNCH;
+    }
+    return XGGM_OK;
 }

@@ -1493,12 +1493,7 @@ __global__ __launch_bounds__(NT, (min_waves<BM, BN>())) void gemm_fp8_kernel(Gem
 
 template <int BM, int BN, int D> int launch_fp8_tile(const GemmArgs& g, const float* sa, const float* sb, hipStream_t stream) {
     constexpr size_t lds = 2 * sizeof(bf16) * (OpLds<BM, true>::ELEMS + OpLds<BN, true>::ELEMS);
-    static bool attr_set = false;
-    if (lds > 48 * 1024 && !attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_fp8_kernel<BM, BN, D>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_set = true;
-    }
+    if (int e = xggm_reserve_lds(reinterpret_cast<const void*>(&gemm_fp8_kernel<BM, BN, D>), lds, "xggm_gemm_fp8e4m3")) return e;
     hipLaunchKernelGGL((gemm_fp8_kernel<BM, BN, D>), dim3(ceil_div(g.N, BN), ceil_div(g.M, BM), 1), dim3(NT), lds, stream, g,
                        sa, sb);
     return xggm_check_launch("xggm_gemm_fp8e4m3");
@@ -1587,14 +1582,7 @@ template <int BM, int BN, int W = 4> int launch_grouped_tile(GroupArgs& ga, hipS
         const size_t b = ga.p[i].b_mode == 1 ? OpLds<BN, true>::ELEMS : OpLds<BN, false>::ELEMS;
         lds = std::max(lds, glds_ok<false>(ga.p[i]) ? ga.stages * sizeof(bf16) * (BM + BN) * 64 : 2 * sizeof(bf16) * (a + b));
     }
-    constexpr size_t lds_max = std::max<size_t>(2 * sizeof(bf16) * (OpLds<BM, false>::ELEMS + OpLds<BN, false>::ELEMS),
-                                                std::min<size_t>(160 * 1024, 4 * sizeof(bf16) * (BM + BN) * 64));
-    static bool attr_set = false;
-    if (lds_max > 48 * 1024 && !attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_grouped_kernel<BM, BN, W>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max);
-        attr_set = true;
-    }
+    if (int e = xggm_reserve_lds(reinterpret_cast<const void*>(&gemm_grouped_kernel<BM, BN, W>), lds, "xggm_gemm_grouped")) return e;
     hipLaunchKernelGGL((gemm_grouped_kernel<BM, BN, W>), dim3(total), dim3(64 * W), lds, stream, ga);
     return xggm_check_launch("xggm_gemm_grouped");
 }
@@ -1650,12 +1638,8 @@ template <int BM, int BN> int launch_grouped_role(GroupArgs& ga, hipStream_t str
     ga.stages = ROLE_NS;
     // the stages, or the staged epilogue's (BM / 2) x (BN + 4) floats of the same memory
     constexpr size_t lds = std::max(ROLE_NS * sizeof(bf16) * (BM + BN) * 64, sizeof(float) * (BM / 2) * (BN + 4));
-    static bool attr_set = false;
-    if (lds > 48 * 1024 && !attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_grouped_role_kernel<BM, BN>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_set = true;
-    }
+    if (int e = xggm_reserve_lds(reinterpret_cast<const void*>(&gemm_grouped_role_kernel<BM, BN>), lds, "xggm_gemm_grouped(role)"))
+        return e;
     hipLaunchKernelGGL((gemm_grouped_role_kernel<BM, BN>), dim3(total), dim3(512), lds, stream, ga);
     return xggm_check_launch("xggm_gemm_grouped(role)");
 }
@@ -1703,14 +1687,8 @@ template <int BM, int BN, int W = 4> int launch_grouped_fp8_tile(GroupArgs& ga, 
     for (int i = 0; i < ga.nprob; ++i) glds = glds && glds_ok<true>(ga.p[i]);
     const size_t lds = std::max((glds ? ga.stages : 2) * sizeof(bf16) * (OpLds<BM, true>::ELEMS + OpLds<BN, true>::ELEMS),
                                 sizeof(float) * (BM / 2) * (BN + 4));
-    constexpr size_t lds_max = std::max(3 * sizeof(bf16) * (OpLds<BM, true>::ELEMS + OpLds<BN, true>::ELEMS),
-                                        sizeof(float) * (BM / 2) * (BN + 4));
-    static bool attr_set = false;
-    if (lds_max > 48 * 1024 && !attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_grouped_fp8_kernel<BM, BN, W>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max);
-        attr_set = true;
-    }
+    if (int e = xggm_reserve_lds(reinterpret_cast<const void*>(&gemm_grouped_fp8_kernel<BM, BN, W>), lds, "xggm_gemm_grouped_fp8e4m3"))
+        return e;
     hipLaunchKernelGGL((gemm_grouped_fp8_kernel<BM, BN, W>), dim3(total), dim3(64 * W), lds, stream, ga);
     return xggm_check_launch("xggm_gemm_grouped_fp8e4m3");
 }
@@ -1721,12 +1699,8 @@ template <int BM, int BN, int D> int launch_fast_tile(const GemmArgs& g, int bat
 #define XGGM_FAST(AKv, BKv)                                                                                           \
     do {                                                                                                              \
         constexpr size_t lds = 2 * sizeof(bf16) * (OpLds<BM, AKv>::ELEMS + OpLds<BN, BKv>::ELEMS);                   \
-        static bool attr_set = false;                                                                                 \
-        if (lds > 48 * 1024 && !attr_set) {                                                                           \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_fast_kernel<BM, BN, AKv, BKv, D>),          \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                          \
-            attr_set = true;                                                                                          \
-        }                                                                                                             \
+        if (int e = xggm_reserve_lds(reinterpret_cast<const void*>(&gemm_fast_kernel<BM, BN, AKv, BKv, D>), lds,      \
+                                     "xggm_gemm(fast)")) return e;                                                    \
         hipLaunchKernelGGL((gemm_fast_kernel<BM, BN, AKv, BKv, D>), grid, dim3(NT), lds, stream, g);                  \
     } while (0)
     if (ak && bk) XGGM_FAST(true, true);
@@ -1905,29 +1879,28 @@ GemmArgs from_problem(const xggm_gemm_problem& p) {
 // `kt`: reduction elements per k-tile (64 bf16, 128 e4m3: the same bytes).
 int pick_group_tile(const GroupArgs& ga, int n, int kt) {
     struct TileModel { int bm, bn; float a, b, s, f, k; };
-    static const TileModel models[3] = {{64, 64, 3.3f, 1.2f, 0.19f, 5.0f, 0.28f},
-                                        {128, 64, 4.2f, 2.0f, 0.37f, 5.6f, 0.56f},
-                                        {128, 128, 2.3f, 6.1f, 0.71f, 8.4f, 0.75f}};
-    static TileModel tuned[3];
-    static bool tuned_init = false;
-    if (!tuned_init) {  // A/B hook: XGGM_TILE_MODEL="a,b,s,f,k;a,b,s,f,k;a,b,s,f,k" overrides the fitted constants
-        for (int c = 0; c < 3; ++c) tuned[c] = models[c];
+    struct TileModels { TileModel m[3]; };
+    // the fitted constants; A/B hook: XGGM_TILE_MODEL="a,b,s,f,k;a,b,s,f,k;a,b,s,f,k" overrides them
+    static const TileModels tuned = [] {
+        TileModels t{{{64, 64, 3.3f, 1.2f, 0.19f, 5.0f, 0.28f},
+                      {128, 64, 4.2f, 2.0f, 0.37f, 5.6f, 0.56f},
+                      {128, 128, 2.3f, 6.1f, 0.71f, 8.4f, 0.75f}}};
         if (const char* e = getenv("XGGM_TILE_MODEL")) {
             float q[15];
             if (sscanf(e, "%f,%f,%f,%f,%f;%f,%f,%f,%f,%f;%f,%f,%f,%f,%f", q, q + 1, q + 2, q + 3, q + 4, q + 5, q + 6, q + 7,
                        q + 8, q + 9, q + 10, q + 11, q + 12, q + 13, q + 14) == 15)
                 for (int c = 0; c < 3; ++c) {
-                    tuned[c].a = q[5 * c]; tuned[c].b = q[5 * c + 1]; tuned[c].s = q[5 * c + 2];
-                    tuned[c].f = q[5 * c + 3]; tuned[c].k = q[5 * c + 4];
+                    t.m[c].a = q[5 * c]; t.m[c].b = q[5 * c + 1]; t.m[c].s = q[5 * c + 2];
+                    t.m[c].f = q[5 * c + 3]; t.m[c].k = q[5 * c + 4];
                 }
         }
-        tuned_init = true;
-    }
+        return t;
+    }();
     int v = g_group_tile;
     if (v == 0) {
         float best = 0.f;
         for (int c = 0; c < 3; ++c) {
-            const TileModel& tm = tuned[c];
+            const TileModel& tm = tuned.m[c];
             double tiles = 0, work = 0;
             int nkmax = 0;
             for (int i = 0; i < n; ++i) {

@@ -613,11 +613,7 @@ int launch_agg_res_ln(const float* M, const bf16* y, const bf16* res, const floa
                       float* stats, int B, int N, float eps, hipStream_t st) {
     constexpr int H = CG * 64;
     constexpr size_t lds = sizeof(bf16) * (64 * (H + 8) + 2 * 16 * 72) + sizeof(float) * (64 + 2 * H);
-    static bool once = [] {  // more than the default 64 KB of dynamic LDS: opt in once per instantiation
-        return hipFuncSetAttribute(reinterpret_cast<const void*>(agg_res_ln_kernel<CG>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)lds) == hipSuccess;
-    }();
-    XGGM_REQUIRE(once, "xggm_agg_residual_ln_bf16: cannot reserve %zu bytes of LDS", lds);
+    if (int e = xggm_reserve_lds(reinterpret_cast<const void*>(agg_res_ln_kernel<CG>), lds, "xggm_agg_residual_ln_bf16")) return e;
     const int grid = ceil_div(B, 8) * 8 * ceil_div(N, 16);
     hipLaunchKernelGGL((agg_res_ln_kernel<CG>), dim3(grid), dim3(NT), lds, st, M, y, res, gamma, beta, out, z_out, stats, B, N, eps);
     return xggm_check_launch("xggm_agg_residual_ln_bf16");

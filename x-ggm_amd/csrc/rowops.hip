@@ -1183,8 +1183,10 @@ inline int check_row_shape(const char* who, int M, int H) {
 
 template <typename T>
 int ln_fwd_grouped(const xggm_ln_fwd_problem* probs, int n, int H, float eps, float p_pre, float p_post, const uint64_t* rng,
-                   int accumulate, float out_scale, hipStream_t st) {
+                   int accumulate, float out_scale, const xggm_prefetch* prefetch, hipStream_t st) {
     XGGM_REQUIRE(probs && n > 0, "xggm_ln_fwd: no problems");
+    PrefetchArgs pf;  // read by the first launch only
+    if (int e = xggm_prefetch_args(prefetch, &pf, "xggm_ln_fwd")) return e;
     XGGM_REQUIRE((p_pre == 0.f && p_post == 0.f) || rng, "xggm_ln_fwd: dropout needs an rng state");
     XGGM_REQUIRE(p_pre >= 0.f && p_pre < 1.f && p_post >= 0.f && p_post < 1.f, "xggm_ln_fwd: bad dropout p");
     for (int i0 = 0; i0 < n; i0 += MAX_SEG) {
@@ -1202,10 +1204,10 @@ int ln_fwd_grouped(const xggm_ln_fwd_problem* probs, int n, int H, float eps, fl
             total += std::min(ceil_div(q.M, LN_FWD_W), 4096);
         }
         G.start[G.n] = total;
-        const PrefetchArgs pf = xggm_take_prefetch();
         DISPATCH_NV(H, hipLaunchKernelGGL((ln_fwd_kernel<T, NV>), dim3(total + pf.blocks), dim3(LN_FWD_W * 64), 0, st, G, H, eps, p_pre,
                                            p_post, rng, accumulate, out_scale, pf));
         if (int e = xggm_check_launch("xggm_ln_fwd")) return e;
+        pf = PrefetchArgs{};
     }
     return XGGM_OK;
 }
@@ -1240,7 +1242,7 @@ int ln_fwd(const void* in, const float* bias, const void* residual, const float*
            void* z_out, float* stats, int M, int H, float eps, float p_pre, float p_post, const uint64_t* rng,
            uint32_t s_pre, uint32_t s_post, int accumulate, float out_scale, hipStream_t st) {
     const xggm_ln_fwd_problem q{in, bias, residual, gamma, beta, out, z_out, stats, M, s_pre, s_post, 0, nullptr, nullptr, nullptr};
-    return ln_fwd_grouped<T>(&q, 1, H, eps, p_pre, p_post, rng, accumulate, out_scale, st);
+    return ln_fwd_grouped<T>(&q, 1, H, eps, p_pre, p_post, rng, accumulate, out_scale, nullptr, st);
 }
 
 inline size_t bwd_ws_bytes(int M, int H, int K) { return sizeof(float) * (size_t)rows_grid(M, 512) * K * H; }
@@ -1260,8 +1262,10 @@ inline void launch_reduce(const float* ws, int nblk, int K, int H, const ReduceT
 
 template <typename T>
 int ln_bwd_grouped(const xggm_ln_bwd_problem* probs, int n, int H, float p_pre, float p_post, const uint64_t* rng,
-                   float out_scale, hipStream_t st) {
+                   float out_scale, const xggm_prefetch* prefetch, hipStream_t st) {
     XGGM_REQUIRE(probs && n > 0, "xggm_ln_bwd: no problems");
+    PrefetchArgs pf;  // read by the first launch only
+    if (int e = xggm_prefetch_args(prefetch, &pf, "xggm_ln_bwd")) return e;
     XGGM_REQUIRE((p_pre == 0.f && p_post == 0.f) || rng, "xggm_ln_bwd: dropout needs an rng state");
     for (int i0 = 0; i0 < n; i0 += MAX_SEG) {
         LnBwdGroup G;
@@ -1278,19 +1282,14 @@ int ln_bwd_grouped(const xggm_ln_bwd_problem* probs, int n, int H, float p_pre, 
             total += ln_bwd_grid(q.M);
         }
         G.start[G.n] = total;
+        const size_t lds = sizeof(float) * LN_BWD_W * H * (ln_bwd_fused_tail(H) ? 3 : 1);  // past the 48 KB default above H = 512
         DISPATCH_NV(H, {
-            static bool big_lds = false;  // rows of up to 2048 floats x 8 waves exceed the 48 KB default
-            if (!big_lds) {
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&ln_bwd_kernel<T, NV>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize,
-                                          (int)std::min<size_t>(sizeof(float) * LN_BWD_W * 256 * NV * 3, 144 * 1024));
-                big_lds = true;
-            }
+            if (int e = xggm_reserve_lds(reinterpret_cast<const void*>(&ln_bwd_kernel<T, NV>), lds, "xggm_ln_bwd")) return e;
+            hipLaunchKernelGGL((ln_bwd_kernel<T, NV>), dim3(total + pf.blocks), dim3(LN_BWD_W * 64), lds, st, G, H, p_pre, p_post,
+                               rng, out_scale, pf);
         });
-        const PrefetchArgs pf = xggm_take_prefetch();
-        DISPATCH_NV(H, hipLaunchKernelGGL((ln_bwd_kernel<T, NV>), dim3(total + pf.blocks), dim3(LN_BWD_W * 64), sizeof(float) * LN_BWD_W * H * (ln_bwd_fused_tail(H) ? 3 : 1), st, G, H,
-                                           p_pre, p_post, rng, out_scale, pf));
         if (int e = xggm_check_launch("xggm_ln_bwd")) return e;
+        pf = PrefetchArgs{};
         for (int i = 0; i < G.n; ++i) {
             const xggm_ln_bwd_problem& q = G.s[i];
             if (q.dgamma || q.dbeta || q.dbias) {
@@ -1312,7 +1311,7 @@ int ln_bwd(const void* dy, const void* z, const float* stats, const float* gamma
            hipStream_t st) {
     const xggm_ln_bwd_problem q{dy, z, stats, gamma, d_in, d_res, dgamma, dbeta, dbias, gelu_aux, ws, ws_bytes, M, s_pre, s_post,
                                 accumulate_dres};
-    return ln_bwd_grouped<T>(&q, 1, H, p_pre, p_post, rng, out_scale, st);
+    return ln_bwd_grouped<T>(&q, 1, H, p_pre, p_post, rng, out_scale, nullptr, st);
 }
 
 template <typename T>
@@ -1464,12 +1463,13 @@ size_t ws_colsum(int M, int N) { return sizeof(float) * (size_t)ceil_div(M, CS_R
     }                                                                                                                       \
     extern "C" int xggm_ln_fwd_grouped_##SUF(const xggm_ln_fwd_problem* probs, int n, int H, float eps, float p_pre,       \
                                              float p_post, const uint64_t* rng, int accumulate, float out_scale,          \
-                                             hipStream_t st) {                                                            \
-        return ln_fwd_grouped<T>(probs, n, H, eps, p_pre, p_post, rng, accumulate, out_scale, st);                         \
+                                             const xggm_prefetch* prefetch, hipStream_t st) {                             \
+        return ln_fwd_grouped<T>(probs, n, H, eps, p_pre, p_post, rng, accumulate, out_scale, prefetch, st);               \
     }                                                                                                                       \
     extern "C" int xggm_ln_bwd_grouped_##SUF(const xggm_ln_bwd_problem* probs, int n, int H, float p_pre, float p_post,    \
-                                             const uint64_t* rng, float out_scale, hipStream_t st) {                      \
-        return ln_bwd_grouped<T>(probs, n, H, p_pre, p_post, rng, out_scale, st);                                          \
+                                             const uint64_t* rng, float out_scale, const xggm_prefetch* prefetch,         \
+                                             hipStream_t st) {                                                            \
+        return ln_bwd_grouped<T>(probs, n, H, p_pre, p_post, rng, out_scale, prefetch, st);                                \
     }                                                                                                                       \
     extern "C" int xggm_ln_sum_fwd_##SUF(const xggm_ln_sum_args* args, hipStream_t st) { return ln_sum_fwd<T>(args, st); }  \
     extern "C" int xggm_embed_fwd_##SUF(const int64_t* ids, const int64_t* seg, const void* word, const void* pos,         \

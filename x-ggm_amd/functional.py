@@ -333,7 +333,7 @@ def g_attn_fwd(rt, att, outm, xq, xkv, mask, B, Sq, Sk, salt):
     p_att, p_hid = rt.p(rt.p_attn), rt.p(rt.p_hidden)
     e_ctx = f8.emit(("ctx", id(att), salt)) if emit else (None, None)
     core = ops.AttnFwdReq(q, k, v, mask, B, heads, Sq, Sk, p_att, rt.rng, att._sid + salt, emit8=e_ctx[0])
-    # weight prefetch beside the attention core (ops.prefetch_next): behind W_v in the arena lie W_o (H^2 elements) and
+    # weight prefetch beside the attention core (ops.prefetch_ranges): behind W_v in the arena lie W_o (H^2 elements) and
     # this layer's W_1 and W_2 (4 H^2 each) -- the operands of the next three products.  The attention launches are
     # the long ones of the chain; the LayerNorm launches, half as long, take half a next layer's W_q / W_k / W_v each
     core.prefetch = (a.after(wv, 9 * H * H, use8),)

@@ -705,44 +705,52 @@ def ln_bwd_group(items, p_pre=0.0, p_post=0.0, rng=None, out_scale=1.0):
         keep.append(ws)
     arr = (LnBwdProblem * len(probs))(*probs)
     call("xggm_ln_bwd_grouped_" + sfx(dt), _ct.cast(arr, _ct.c_void_p), len(probs), H, float(p_pre), float(p_post), ptr(rng),
-         float(out_scale), stream())
+         float(out_scale), None, stream())
     return outs
 
 
-def prefetch_next(t):
-    """queue the bytes of tensor ``t`` (a contiguous slice of a weight buffer) for the next LayerNorm / attention launch to
-    read beside its own work and discard (xggm_prefetch_next): the products behind that launch then find their weights
-    in the Infinity Cache"""
-    if t is not None and t.numel():
-        a, n = t.data_ptr(), t.numel() * t.element_size()
+class Prefetch(_ct.Structure):
+    """mirror of ``xggm_prefetch`` (include/xggm.h)"""
+    _fields_ = [("ptr", _ct.c_void_p * 4), ("bytes", _ct.c_size_t * 4), ("n", _ct.c_int)]
+
+
+PREFETCH = os.environ.get("XGGM_PREFETCH") != "0"  # read once; 0: no launch carries weight ranges
+
+
+def prefetch_ranges(tensors):
+    """the ``xggm_prefetch`` argument (or None) of a row launch that reads ``tensors`` (weight slices, or None) beside its
+    work: each range from its first 16-byte border, those of 16 bytes or less after it skipped, four at most"""
+    pf = Prefetch()
+    for t in tensors if PREFETCH else ():
+        a, n = (t.data_ptr(), t.numel() * t.element_size()) if t is not None else (0, 0)
         pad = (-a) % 16
-        if n > pad + 16:
-            call("xggm_prefetch_next", a + pad, n - pad)
+        if n > pad + 16 and pf.n < 4:
+            pf.ptr[pf.n], pf.bytes[pf.n] = a + pad, n - pad
+            pf.n += 1
+    return _ct.byref(pf) if pf.n else None
 
 
 def launch_row_requests(reqs):
-    """launch LnFwdReq / LnBwdReq objects, grouping those with equal key (same kind, dtype, H, eps, p)."""
+    """launch LnFwdReq / LnBwdReq / Attn*Req objects with their ``prefetch`` ranges, grouping those with equal key."""
     groups = {}
     for r in reqs:
         groups.setdefault(r.key, []).append(r)
     for key, rs in groups.items():
-        for r in rs:
-            for t in getattr(r, "prefetch", ()):
-                prefetch_next(t)
+        pf = prefetch_ranges([t for r in rs for t in getattr(r, "prefetch", ())])
         if key[0] in ("attn_fwd", "attn_bwd"):
             arr = (AttnProblem * len(rs))(*[r.prob for r in rs])
-            call("xggm_%s_grouped_%s" % (key[0], sfx(key[1])), _ct.cast(arr, _ct.c_void_p), len(rs), 64, ptr(rs[0].rng),
+            call("xggm_%s_grouped_%s" % (key[0], sfx(key[1])), _ct.cast(arr, _ct.c_void_p), len(rs), 64, ptr(rs[0].rng), pf,
                  stream())
             reduce_batch([r.post for r in rs if getattr(r, "post", None) is not None])
         elif key[0] == "ln_fwd":
             _, dt, H, eps, p = key
             arr = (LnFwdProblem * len(rs))(*[r.prob for r in rs])
             call("xggm_ln_fwd_grouped_" + sfx(dt), _ct.cast(arr, _ct.c_void_p), len(rs), H, eps, p, 0.0, ptr(rs[0].rng), 0,
-                 1.0, stream())
+                 1.0, pf, stream())
         else:
             _, dt, H, p = key
             arr = (LnBwdProblem * len(rs))(*[r.prob for r in rs])
-            call("xggm_ln_bwd_grouped_" + sfx(dt), _ct.cast(arr, _ct.c_void_p), len(rs), H, p, 0.0, ptr(rs[0].rng), 1.0,
+            call("xggm_ln_bwd_grouped_" + sfx(dt), _ct.cast(arr, _ct.c_void_p), len(rs), H, p, 0.0, ptr(rs[0].rng), 1.0, pf,
                  stream())
 
 
