@@ -16,9 +16,12 @@
  *    [B,N,N], losses and optimiser state are always fp32.
  *  - Return value: 0 = ok; non-zero = error, message via xggm_last_error() (thread-local).
  *    Reentrant and thread-safe: called from the host thread in forward and from the
- *    autograd thread in backward.  All launch state travels in the arguments; the only
- *    process-wide state are the A/B hooks xggm_gemm_set_tile, xggm_gemm_set_group_tile,
- *    xggm_gemm_set_generic, xggm_attn_set_scalar and the instrumented build's stamp / ablation hooks.
+ *    autograd thread in backward.  All launch state travels in the arguments, the tile of a
+ *    grouped GEMM launch included (argument `tile`).  The only process-wide state are the A/B
+ *    hooks xggm_gemm_set_tile, xggm_gemm_set_group_tile, xggm_gemm_set_generic,
+ *    xggm_attn_set_scalar and the instrumented build's stamp / ablation hooks: tests, tools and
+ *    the bench's A/B variables write them, the product never does.  A GEMM entry point reads
+ *    its hooks once per call, so one launch sees one consistent set of values.
  *  - Randomness: `rng` points to two device uint64 {seed, offset}; dropout masks and
  *    Gaussian draws are pure functions of (seed, offset, stream id `sid`, element index), so
  *    backward regenerates the forward mask.  xggm_rng_advance() bumps the offset once per
@@ -124,8 +127,14 @@ typedef struct xggm_gemm_problem {
      * launch, +3.9 us per attention launch, 0.25 ms per iteration of the fp8 step). */
     int amax_slots;
 } xggm_gemm_problem;
-int xggm_gemm_grouped_f32(const xggm_gemm_problem* probs, int n, xggm_stream_t stream);
-int xggm_gemm_grouped_bf16(const xggm_gemm_problem* probs, int n, xggm_stream_t stream);
+/* `tile` of the three grouped entry points: 0 = the library chooses (cost model, the 8-wave rule, the four-wave
+ * 128 x 128 rule); 1: 64 x 64, 2: 128 x 64, 3: 128 x 128, 4: 128 x 128 on 8 waves; 7 / 8 / 9: 128 x 128 / 128 x 64 /
+ * 64 x 64 on the role k-loop (four loader + four compute waves; a group with a ragged k-tile takes the four-wave
+ * tile of the same shape).  Any other value is an error and nothing is enqueued.  Precedence: a non-zero `tile` wins;
+ * otherwise the process-wide hook xggm_gemm_set_group_tile; otherwise the library's choice.  The tile changes speed,
+ * never products or column sums; the `sqsum` slots add their squares in a tile-dependent, fixed order. */
+int xggm_gemm_grouped_f32(const xggm_gemm_problem* probs, int n, int tile, xggm_stream_t stream);
+int xggm_gemm_grouped_bf16(const xggm_gemm_problem* probs, int n, int tile, xggm_stream_t stream);
 /* fp8 forward product of the mixed-precision configuration (BASELINE.json configs[4]: "fp8 MFMA path for LXMERT
  * QKV/FFN GEMMs"; the Linear layers of src/lxrt/modeling.py:345-347 (query/key/value), :429 (intermediate),
  * :442 (output) -- the reference itself is fp32 only, `--fp16` is unused):
@@ -141,8 +150,9 @@ int xggm_gemm_fp8e4m3(const void* A, const void* B, void* C, int M, int N, int K
  * directions of a cross-attention layer): every problem has e4m3 operands A [M, K] / B [N, K], k contiguous (a_ks =
  * b_ks = 1, strides in elements = bytes, multiples of 16 like K), its own scale_a / scale_b, and the bf16 epilogue of
  * xggm_gemm_grouped_bf16 (bias, GELU + pre-activation, residual, fp32 split-K slabs through batch / c_f32, c8).  Not
- * for the backward: dgrad / wgrad stay bf16. */
-int xggm_gemm_grouped_fp8e4m3(const xggm_gemm_problem* probs, int n, xggm_stream_t stream);
+ * for the backward: dgrad / wgrad stay bf16.  `tile` as above, except that there is no role k-loop for e4m3 operands:
+ * 7 / 8 / 9 are accepted and all run the 64 x 64 tile. */
+int xggm_gemm_grouped_fp8e4m3(const xggm_gemm_problem* probs, int n, int tile, xggm_stream_t stream);
 /* Delayed per-tensor scaling of the e4m3 operands: one table (amax, history, qscale, dscale = 1 / qscale) whose
  * entries are weight operands and activation sites.  Protocol of the producers (LayerNorm / GELU epilogue /
  * attention output / BertAdam): an entry with qscale <= 0 is uncalibrated -- they quantise with 1 and record every
@@ -165,7 +175,9 @@ int xggm_fp8_scale_update(float* amax, float* hist, float* qscale, float* dscale
  * step's scale without another pass over x. */
 int xggm_quantize_fp8e4m3_f32(const void* x, void* y, int64_t n, const float* qscale, float* amax, xggm_stream_t stream);
 int xggm_quantize_fp8e4m3_bf16(const void* x, void* y, int64_t n, const float* qscale, float* amax, xggm_stream_t stream);
-/* HOST: tile of grouped launches (0 heuristic, 1: 64x64, 2: 128x64, 3: 128x128, 4: 128x128 on 8 waves) */
+/* HOST, A/B hook: tile of the grouped launches whose `tile` argument is 0 (values as that argument; 0: the library
+ * chooses).  Process-wide and unordered against launches on other threads: for tests, tools and the bench's
+ * XGGM_GROUP_TILE only. */
 int xggm_gemm_set_group_tile(int v);
 /* HOST: 1 = run bf16 GEMMs on the generic 64x64 kernel, 0 = tuned kernels (default); A/B tests */
 int xggm_gemm_set_generic(int on);

@@ -315,3 +315,24 @@ def test_measured_tile_table_is_well_formed():
         assert dtp in ("bf16", "f32", "e4m3")
         for p in probs.split("+"):
             assert re.fullmatch(r"\d+x\d+x\d+(b\d+)?:[01][01][a-zA-Z]*", p), p
+
+
+def test_grouped_gemm_tile_travels_with_the_launch():
+    """the tile of a grouped GEMM launch is an argument (`int tile` in front of the stream), a value the library does
+    not have is refused before anything is enqueued, and the product never writes the process-wide GEMM hooks"""
+    from xggm_amd import _lib, ops
+    src = re.sub(r"/\*.*?\*/", " ", open(_lib.HEADER_PATH).read(), flags=re.S)
+    for name in ("xggm_gemm_grouped_f32", "xggm_gemm_grouped_bf16", "xggm_gemm_grouped_fp8e4m3"):
+        m = re.search(r"\bint\s+%s\s*\(([^)]*)\)\s*;" % name, src)
+        args = [" ".join(a.split()) for a in m.group(1).split(",")]
+        assert args[-2:] == ["int tile", "xggm_stream_t stream"], (name, args)
+        probs = (ops.GemmProblem * 1)()
+        for tile in (-1, 5, 6, 10):
+            rc = getattr(_lib.lib, name)(ctypes.addressof(probs), 1, tile, None)
+            assert rc != 0 and b"tile %d" % tile in _lib.lib.xggm_last_error(), (name, tile)
+    pkg = os.path.dirname(os.path.abspath(_lib.__file__))
+    for d, dirs, files in os.walk(pkg):
+        dirs[:] = [x for x in dirs if x not in ("csrc", "__pycache__")]
+        for f in files:
+            with open(os.path.join(d, f), errors="ignore") as fh:
+                assert "xggm_gemm_set_" not in fh.read(), os.path.join(d, f)

@@ -124,55 +124,50 @@ def test_linear_backward_padded_odd_width(ops, M, N, K):
 @pytest.mark.parametrize("group_tile", [0, 1, 2, 3, 4, 7, 8, 9])
 def test_grouped_gemm(ops, dt, group_tile):
     """forward (two modalities) + dgrad + wgrad in ONE launch == the four products done alone"""
-    from xggm_amd import _lib
-    _lib.lib.xggm_gemm_set_group_tile(group_tile)
-    try:
-        xl, xlr = rnd((640, 768), dt, 1)
-        xv, xvr = rnd((1152, 768), dt, 2)
-        w1, w1r = rnd((3072, 768), dt, 3, 0.05)
-        w2, w2r = rnd((768, 768), dt, 4, 0.05)
-        b1 = torch.randn(3072, generator=torch.Generator().manual_seed(5)).to(DEV)
-        dy, dyr = rnd((1152, 768), dt, 6)
-        res, resr = rnd((1152, 768), dt, 7)
-        gw = torch.full((768, 768), 3.0, device=DEV)
-        p1, y1, pre1 = ops.p_fwd(xl, w1, b1, act=ops.ACT_GELU, want_preact=True)
-        p2, y2, _ = ops.p_fwd(xv, w2, None)
-        p3, dx = ops.p_dgrad(dy, w2, residual=res)
-        p4 = ops.p_wgrad(dy, xv, gw, accumulate=True)
-        ops.gemm_group(dt, [p1, p2, p3, p4])
-        pr = pre1.double().cpu()
-        assert rel_err(pre1, xlr @ w1r.t() + b1.double().cpu()) < tol(dt)
-        assert rel_err(y1, pr * 0.5 * (1 + torch.erf(pr / math.sqrt(2)))) < tol(dt)
-        assert rel_err(y2, xvr @ w2r.t()) < tol(dt)
-        assert rel_err(dx, dyr @ w2r + resr) < tol(dt)
-        assert rel_err(gw, 3.0 + dyr.t() @ xvr) < tol(dt, 2e-5, 1e-4)
-        # six problems in ONE launch (the cross-attention backward's five, the graph blocks' six read-out problems) give
-        # the bits of the same problems launched alone
-        def six():
-            ps, outs = [], []
-            for k in range(3):
-                p, y, _ = ops.p_fwd(xv if k else xl, w2, None)
-                pd, d = ops.p_dgrad(dy, w2)
-                ps += [p, pd]
-                outs += [y, d]
-            return ps, outs
-        ps, together = six()
-        assert len(ps) == ops.GROUP_MAX
-        ops.gemm_group(dt, ps)
-        ps, alone = six()
-        for p in ps:
-            ops.gemm_group(dt, [p])
-        for a_, b_ in zip(together, alone):
-            assert torch.equal(a_, b_)
-        # odd shapes fall back to single launches and still agree
-        xo, xor_ = rnd((37, 100), dt, 8)
-        wo, wor = rnd((50, 100), dt, 9, 0.1)
-        p5, y5, _ = ops.p_fwd(xo, wo, None)
-        p6, y6, _ = ops.p_fwd(xv, w2, None)
-        ops.gemm_group(dt, [p5, p6])
-        assert rel_err(y5, xor_ @ wor.t()) < tol(dt) and rel_err(y6, xvr @ w2r.t()) < tol(dt)
-    finally:
-        _lib.lib.xggm_gemm_set_group_tile(0)
+    xl, xlr = rnd((640, 768), dt, 1)
+    xv, xvr = rnd((1152, 768), dt, 2)
+    w1, w1r = rnd((3072, 768), dt, 3, 0.05)
+    w2, w2r = rnd((768, 768), dt, 4, 0.05)
+    b1 = torch.randn(3072, generator=torch.Generator().manual_seed(5)).to(DEV)
+    dy, dyr = rnd((1152, 768), dt, 6)
+    res, resr = rnd((1152, 768), dt, 7)
+    gw = torch.full((768, 768), 3.0, device=DEV)
+    p1, y1, pre1 = ops.p_fwd(xl, w1, b1, act=ops.ACT_GELU, want_preact=True)
+    p2, y2, _ = ops.p_fwd(xv, w2, None)
+    p3, dx = ops.p_dgrad(dy, w2, residual=res)
+    p4 = ops.p_wgrad(dy, xv, gw, accumulate=True)
+    ops.gemm_group(dt, [p1, p2, p3, p4], tile=group_tile)
+    pr = pre1.double().cpu()
+    assert rel_err(pre1, xlr @ w1r.t() + b1.double().cpu()) < tol(dt)
+    assert rel_err(y1, pr * 0.5 * (1 + torch.erf(pr / math.sqrt(2)))) < tol(dt)
+    assert rel_err(y2, xvr @ w2r.t()) < tol(dt)
+    assert rel_err(dx, dyr @ w2r + resr) < tol(dt)
+    assert rel_err(gw, 3.0 + dyr.t() @ xvr) < tol(dt, 2e-5, 1e-4)
+    # six problems in ONE launch (the cross-attention backward's five, the graph blocks' six read-out problems) give
+    # the bits of the same problems launched alone
+    def six():
+        ps, outs = [], []
+        for k in range(3):
+            p, y, _ = ops.p_fwd(xv if k else xl, w2, None)
+            pd, d = ops.p_dgrad(dy, w2)
+            ps += [p, pd]
+            outs += [y, d]
+        return ps, outs
+    ps, together = six()
+    assert len(ps) == ops.GROUP_MAX
+    ops.gemm_group(dt, ps, tile=group_tile)
+    ps, alone = six()
+    for p in ps:
+        ops.gemm_group(dt, [p], tile=group_tile)
+    for a_, b_ in zip(together, alone):
+        assert torch.equal(a_, b_)
+    # odd shapes fall back to single launches and still agree
+    xo, xor_ = rnd((37, 100), dt, 8)
+    wo, wor = rnd((50, 100), dt, 9, 0.1)
+    p5, y5, _ = ops.p_fwd(xo, wo, None)
+    p6, y6, _ = ops.p_fwd(xv, w2, None)
+    ops.gemm_group(dt, [p5, p6], tile=group_tile)
+    assert rel_err(y5, xor_ @ wor.t()) < tol(dt) and rel_err(y6, xvr @ w2r.t()) < tol(dt)
 
 
 @pytest.mark.parametrize("dt", DTS)
@@ -907,37 +902,32 @@ def test_wgrad_norm_slots(ops, group_tile):
     its slot -- for every tile size of the grouped kernels (a 128-wide tile writes 2 or 4 slots), with ``accumulate``
     (the slot holds the sum of the ACCUMULATED values), for ragged edges (2274 rows: the last block is partial), in a
     group with a problem that has no slots; the fixed-order total is the squared norm of the gradients."""
-    from xggm_amd import _lib
     BF = torch.bfloat16
     shapes_ = [(1152, 768, 3072), (640, 2274, 1536), (1152, 768, 768)]  # (M tokens, N out, K in)
-    _lib.lib.xggm_gemm_set_group_tile(group_tile)
-    try:
-        for accumulate in (False, True):
-            probs, checks = [], []
-            for i, (M, N, K) in enumerate(shapes_):
-                Np = (N + 7) // 8 * 8  # odd widths: rows padded to a multiple of 8 elements, as the heads do
-                dy = rnd((M, Np), BF, 10 + i, 0.5)[0][:, :N]
-                x, _ = rnd((M, K), BF, 20 + i)
-                gw = torch.randn(N, K, device=DEV) if accumulate else torch.empty(N, K, device=DEV)
-                prev = gw.clone()
-                nr, nc = (N + 63) // 64, (K + 63) // 64
-                slots = torch.full((nr * nc,), float("nan"), device=DEV) if i != 2 else None
-                probs.append(ops.p_wgrad(dy, x, gw, accumulate, slots))
-                checks.append((dy, x, gw, prev, slots, nr, nc, N, K))
-            ops.gemm_group(BF, probs)
-            for dy, x, gw, prev, slots, nr, nc, N, K in checks:
-                want = dy.double().t() @ x.double() + (prev.double() if accumulate else 0)
-                assert rel_err(gw, want) < 1e-5
-                if slots is None:
-                    continue
-                pad = torch.zeros(nr * 64, nc * 64, device=DEV, dtype=torch.float64)
-                pad[:N, :K] = gw.double() ** 2
-                blocks = pad.view(nr, 64, nc, 64).sum(dim=(1, 3)).reshape(-1)
-                assert torch.isfinite(slots).all()
-                assert float((slots.double() - blocks).abs().max()) < 1e-5 * float(blocks.max())
-                assert abs(float(slots.double().sum()) - float((gw.double() ** 2).sum())) < 1e-6 * float(blocks.sum())
-    finally:
-        _lib.lib.xggm_gemm_set_group_tile(0)
+    for accumulate in (False, True):
+        probs, checks = [], []
+        for i, (M, N, K) in enumerate(shapes_):
+            Np = (N + 7) // 8 * 8  # odd widths: rows padded to a multiple of 8 elements, as the heads do
+            dy = rnd((M, Np), BF, 10 + i, 0.5)[0][:, :N]
+            x, _ = rnd((M, K), BF, 20 + i)
+            gw = torch.randn(N, K, device=DEV) if accumulate else torch.empty(N, K, device=DEV)
+            prev = gw.clone()
+            nr, nc = (N + 63) // 64, (K + 63) // 64
+            slots = torch.full((nr * nc,), float("nan"), device=DEV) if i != 2 else None
+            probs.append(ops.p_wgrad(dy, x, gw, accumulate, slots))
+            checks.append((dy, x, gw, prev, slots, nr, nc, N, K))
+        ops.gemm_group(BF, probs, tile=group_tile)
+        for dy, x, gw, prev, slots, nr, nc, N, K in checks:
+            want = dy.double().t() @ x.double() + (prev.double() if accumulate else 0)
+            assert rel_err(gw, want) < 1e-5
+            if slots is None:
+                continue
+            pad = torch.zeros(nr * 64, nc * 64, device=DEV, dtype=torch.float64)
+            pad[:N, :K] = gw.double() ** 2
+            blocks = pad.view(nr, 64, nc, 64).sum(dim=(1, 3)).reshape(-1)
+            assert torch.isfinite(slots).all()
+            assert float((slots.double() - blocks).abs().max()) < 1e-5 * float(blocks.max())
+            assert abs(float(slots.double().sum()) - float((gw.double() ** 2).sum())) < 1e-6 * float(blocks.sum())
     # fp32 storage runs on the generic kernel, which has no such epilogue: refused, not silently skipped
     dy, _ = rnd((64, 64), torch.float32, 1)
     p = ops.p_wgrad(dy, dy, torch.empty(64, 64, device=DEV), False, torch.zeros(1, device=DEV))
@@ -1066,7 +1056,6 @@ def test_gemm_grouped_fp8_matches_dequantised_products(ops, tile):
     """xggm_gemm_grouped_fp8e4m3: the four forward products of one cross-attention round (two Q, two fused KV) and an
     FFN pair incl. GELU + pre-activation + e4m3 copy of the result and the split-K fp32 slabs, against the fp64
     product of the SAME e4m3 operands; every tile of the grouped kernel."""
-    from xggm_amd import _lib
     BF = torch.bfloat16
     g = torch.Generator().manual_seed(11)
 
@@ -1076,64 +1065,60 @@ def test_gemm_grouped_fp8_matches_dequantised_products(ops, tile):
         q, s = ops.fp8_scale_for(a)
         return ops.quantize_fp8(x.to(BF).to(DEV), q).view(torch.uint8), s
 
-    _lib.lib.xggm_gemm_set_group_tile(tile)
-    try:
-        # cross-attention round: lang queries, vision keys/values, vision queries, lang keys/values
-        xl, sl = operand(640, 768, 1.0)
-        xv, sv = operand(1152, 768, 1.5)
-        wq, sq = operand(768, 768, 0.03)
-        wkv, skv = operand(1536, 768, 0.03)
-        bq = torch.randn(768, generator=g).to(DEV)
-        bkv = torch.randn(1536, generator=g).to(DEV)
-        probs, outs = [], []
-        for x8, sx, w8, sw, b in ((xl, sl, wq, sq, bq), (xv, sv, wkv, skv, bkv), (xv, sv, wq, sq, bq), (xl, sl, wkv, skv, bkv)):
-            p, y, _ = ops.p_fwd8(x8, w8, sx, sw, b)
-            probs.append(p)
-            outs.append((y, x8, sx, w8, sw, b))
-        ops.gemm_group8(probs)
-        for y, x8, sx, w8, sw, b in outs:
-            ref = _deq(x8).double() @ _deq(w8).double().t() * float(sx) * float(sw) + b.double()
-            assert rel_err(y, ref) < 4e-3
-        # FFN pair: intermediate product with GELU, pre-activation and the e4m3 copy of the activation
-        w1, s1 = operand(3072, 768, 0.03)
-        b1 = torch.randn(3072, generator=g).to(DEV)
-        res = []
-        probs = []
-        for x8, sx in ((xl, sl), (xv, sv)):
-            act8 = torch.empty((x8.shape[0], 3072), device=DEV, dtype=torch.uint8)
-            qa = torch.tensor([37.0], device=DEV)
-            amax = torch.zeros(1, device=DEV)
-            p, act, u = ops.p_fwd8(x8, w1, sx, s1, b1, act=ops.ACT_GELU, want_preact=True, emit8=(act8, qa, amax))
-            probs.append(p)
-            res.append((x8, sx, act, u, act8, qa, amax))
-        ops.gemm_group8(probs)
-        for x8, sx, act, u, act8, qa, amax in res:
-            pre = _deq(x8).double() @ _deq(w1).double().t() * float(sx) * float(s1) + b1.double()
-            assert rel_err(u, pre) < 4e-3
-            want = torch.nn.functional.gelu(u.float())
-            assert rel_err(act, want) < 4e-3
-            # the e4m3 copy is the quantised fp32 activation (before its bf16 rounding): compare through the values
-            assert rel_err(_deq(act8) / 37.0, want) < 5e-2  # 3 mantissa bits: <= 6.25 % per element, ~3 % rms
-            a = float(want.abs().max())
-            assert float(amax) == 0.0 or abs(float(amax) - a) < 1e-2 * a  # recorded only beyond half the range 448/37
-            assert (a > 0.5 * 448 / 37) == (float(amax) > 0)
-        # an uncalibrated entry (qscale <= 0): quantised with 1, maximum always recorded
-        act8 = torch.empty((640, 3072), device=DEV, dtype=torch.uint8)
-        qa, amax = torch.tensor([-1.0], device=DEV), torch.zeros(1, device=DEV)
-        p, act, u = ops.p_fwd8(xl, w1, sl, s1, b1, act=ops.ACT_GELU, want_preact=True, emit8=(act8, qa, amax))
-        ops.gemm_group8([p])
+    # cross-attention round: lang queries, vision keys/values, vision queries, lang keys/values
+    xl, sl = operand(640, 768, 1.0)
+    xv, sv = operand(1152, 768, 1.5)
+    wq, sq = operand(768, 768, 0.03)
+    wkv, skv = operand(1536, 768, 0.03)
+    bq = torch.randn(768, generator=g).to(DEV)
+    bkv = torch.randn(1536, generator=g).to(DEV)
+    probs, outs = [], []
+    for x8, sx, w8, sw, b in ((xl, sl, wq, sq, bq), (xv, sv, wkv, skv, bkv), (xv, sv, wq, sq, bq), (xl, sl, wkv, skv, bkv)):
+        p, y, _ = ops.p_fwd8(x8, w8, sx, sw, b)
+        probs.append(p)
+        outs.append((y, x8, sx, w8, sw, b))
+    ops.gemm_group8(probs, tile)
+    for y, x8, sx, w8, sw, b in outs:
+        ref = _deq(x8).double() @ _deq(w8).double().t() * float(sx) * float(sw) + b.double()
+        assert rel_err(y, ref) < 4e-3
+    # FFN pair: intermediate product with GELU, pre-activation and the e4m3 copy of the activation
+    w1, s1 = operand(3072, 768, 0.03)
+    b1 = torch.randn(3072, generator=g).to(DEV)
+    res = []
+    probs = []
+    for x8, sx in ((xl, sl), (xv, sv)):
+        act8 = torch.empty((x8.shape[0], 3072), device=DEV, dtype=torch.uint8)
+        qa = torch.tensor([37.0], device=DEV)
+        amax = torch.zeros(1, device=DEV)
+        p, act, u = ops.p_fwd8(x8, w1, sx, s1, b1, act=ops.ACT_GELU, want_preact=True, emit8=(act8, qa, amax))
+        probs.append(p)
+        res.append((x8, sx, act, u, act8, qa, amax))
+    ops.gemm_group8(probs, tile)
+    for x8, sx, act, u, act8, qa, amax in res:
+        pre = _deq(x8).double() @ _deq(w1).double().t() * float(sx) * float(s1) + b1.double()
+        assert rel_err(u, pre) < 4e-3
         want = torch.nn.functional.gelu(u.float())
-        assert abs(float(amax) - float(want.abs().max())) < 1e-2 * float(want.abs().max())
-        assert rel_err(_deq(act8), want) < 5e-2
-        # FFN output product as 3 split-K slabs
-        a8, sa = operand(1152, 3072, 0.5)
-        w2, s2 = operand(768, 3072, 0.03)
-        p, part, _ = ops.p_fwd8(a8, w2, sa, s2, None, split=3)
-        ops.gemm_group8([p])
-        ref = _deq(a8).double() @ _deq(w2).double().t() * float(sa) * float(s2)
-        assert part.shape == (3, 1152, 768) and rel_err(part.sum(0), ref) < 1e-4
-    finally:
-        _lib.lib.xggm_gemm_set_group_tile(0)
+        assert rel_err(act, want) < 4e-3
+        # the e4m3 copy is the quantised fp32 activation (before its bf16 rounding): compare through the values
+        assert rel_err(_deq(act8) / 37.0, want) < 5e-2  # 3 mantissa bits: <= 6.25 % per element, ~3 % rms
+        a = float(want.abs().max())
+        assert float(amax) == 0.0 or abs(float(amax) - a) < 1e-2 * a  # recorded only beyond half the range 448/37
+        assert (a > 0.5 * 448 / 37) == (float(amax) > 0)
+    # an uncalibrated entry (qscale <= 0): quantised with 1, maximum always recorded
+    act8 = torch.empty((640, 3072), device=DEV, dtype=torch.uint8)
+    qa, amax = torch.tensor([-1.0], device=DEV), torch.zeros(1, device=DEV)
+    p, act, u = ops.p_fwd8(xl, w1, sl, s1, b1, act=ops.ACT_GELU, want_preact=True, emit8=(act8, qa, amax))
+    ops.gemm_group8([p], tile)
+    want = torch.nn.functional.gelu(u.float())
+    assert abs(float(amax) - float(want.abs().max())) < 1e-2 * float(want.abs().max())
+    assert rel_err(_deq(act8), want) < 5e-2
+    # FFN output product as 3 split-K slabs
+    a8, sa = operand(1152, 3072, 0.5)
+    w2, s2 = operand(768, 3072, 0.03)
+    p, part, _ = ops.p_fwd8(a8, w2, sa, s2, None, split=3)
+    ops.gemm_group8([p], tile)
+    ref = _deq(a8).double() @ _deq(w2).double().t() * float(sa) * float(s2)
+    assert part.shape == (3, 1152, 768) and rel_err(part.sum(0), ref) < 1e-4
     with pytest.raises(RuntimeError, match="multiples of 16"):
         p, _, _ = ops.p_fwd8(xl[:, :760], wq[:, :760], sl, sq, None)
         ops.gemm_group8([p])
@@ -1572,7 +1557,6 @@ def test_tile_choice_changes_speed_only(ops):
     step -- FFN2 backward: dgrad * gelu'(u) + column sums, weight gradient -- gives the SAME BITS under every tile; the
     64 x 64 norm slots are the same numbers summed in a tile-dependent (but fixed) order: equal to fp32 rounding.  The
     table is part of the configuration: one table, one set of bits.  And the table really steers the launch."""
-    from xggm_amd import _lib
     dt = torch.bfloat16
     M, H, I = 640, 768, 3072
     d_h, _ = rnd((M, H), dt, 1)
@@ -1581,34 +1565,27 @@ def test_tile_choice_changes_speed_only(ops):
     act, _ = rnd((M, I), dt, 4)
 
     def run(pin):
-        _lib.lib.xggm_gemm_set_group_tile(pin)
-        try:
-            cs = torch.zeros(I, device=DEV)
-            gw = torch.empty(H, I, device=DEV)
-            sq = torch.zeros((H // 64) * (I // 64), device=DEV)
-            pd, dx = ops.p_dgrad(d_h, w2, gelu_aux=u, colsum=cs)
-            pw = ops.p_wgrad(d_h, act, gw, False, sqsum=sq)
-            saved, ops.TILE_TABLE = ops.TILE_TABLE, {}  # the explicit pin, not the table, chooses here
-            try:
-                ops.gemm_group(dt, [pw, pd])
-            finally:
-                ops.TILE_TABLE = saved
-            torch.cuda.synchronize()
-            return dx, cs, gw, sq
-        finally:
-            _lib.lib.xggm_gemm_set_group_tile(0)
+        cs = torch.zeros(I, device=DEV)
+        gw = torch.empty(H, I, device=DEV)
+        sq = torch.zeros((H // 64) * (I // 64), device=DEV)
+        pd, dx = ops.p_dgrad(d_h, w2, gelu_aux=u, colsum=cs)
+        pw = ops.p_wgrad(d_h, act, gw, False, sqsum=sq)
+        ops.gemm_group(dt, [pw, pd], tile=pin)
+        torch.cuda.synchronize()
+        return dx, cs, gw, sq
 
-    ref = run(1)
-    for pin in (0, 2, 3, 4, 7, 8, 9):
-        got = run(pin)
-        for a, b in zip(ref[:3], got[:3]):  # dx, column sums, weight gradient
-            assert torch.equal(a, b), pin
-        assert torch.allclose(ref[3], got[3], rtol=2e-6, atol=0), pin  # 4096 fp32 squares per slot, another order
-        assert torch.equal(got[3], run(pin)[3]), pin                   # ... and the same order every time
-    # the table: a signature that is in it reaches the library as a pin (seen through the hook), others do not
-    sig_seen = []
     saved_t, saved_h = ops.TILE_TABLE, ops.TILE_HOOK
     try:
+        ops.TILE_TABLE = {}  # tile 0 below is the library's own choice, not the table's (this launch is in the table)
+        ref = run(1)
+        for pin in (0, 2, 3, 4, 7, 8, 9):
+            got = run(pin)
+            for a, b in zip(ref[:3], got[:3]):  # dx, column sums, weight gradient
+                assert torch.equal(a, b), pin
+            assert torch.allclose(ref[3], got[3], rtol=2e-6, atol=0), pin  # 4096 fp32 squares per slot, another order
+            assert torch.equal(got[3], run(pin)[3]), pin                   # ... and the same order every time
+        # the table: a signature that is in it reaches the library as a pin (seen through the hook), others do not
+        sig_seen = []
         cs = torch.zeros(I, device=DEV)
         pd, _ = ops.p_dgrad(d_h, w2, gelu_aux=u, colsum=cs)
         pw = ops.p_wgrad(d_h, act, torch.empty(H, I, device=DEV), False)
@@ -1619,4 +1596,46 @@ def test_tile_choice_changes_speed_only(ops):
         ops.gemm_group(dt, [pw, pd])
         assert sig_seen == [(sig, 1)]
     finally:
+        ops.TILE_TABLE, ops.TILE_HOOK = saved_t, saved_h
+
+
+def test_launch_tile_wins_and_leaves_the_hook_alone(ops):
+    """The tile travels with the launch: a table hit (or ``tile=``) wins over the process-wide A/B hook
+    (xggm_gemm_set_group_tile) for that launch and does not touch it -- the next launch without a hit still runs under
+    the hook's tile.  Seen through the 64 x 64 norm slots, whose bits depend on the tile (and on nothing else).  The
+    group is large enough (528 tiles of 128 x 128) that the library's own choice is tile 3, not the hook's tile 1."""
+    from xggm_amd import _lib
+    dt = torch.bfloat16
+    M, H, I = 2048, 768, 3072
+    d_h, _ = rnd((M, H), dt, 1)
+    w2, _ = rnd((H, I), dt, 2, 0.05)
+    u, _ = rnd((M, I), dt, 3)
+    act, _ = rnd((M, I), dt, 4)
+
+    def run(tile=0):
+        sq = torch.zeros((H // 64) * (I // 64), device=DEV)
+        pd, _ = ops.p_dgrad(d_h, w2, gelu_aux=u, colsum=torch.zeros(I, device=DEV))
+        pw = ops.p_wgrad(d_h, act, torch.empty(H, I, device=DEV), False, sqsum=sq)
+        ops.gemm_group(dt, [pw, pd], tile=tile)
+        torch.cuda.synchronize()
+        return sq, ops.gemm_signature(dt, [pw, pd])
+
+    saved_t, saved_h = ops.TILE_TABLE, ops.TILE_HOOK
+    seen = []
+    try:
+        ops.TILE_TABLE = {}
+        sq1, sig = run(tile=1)
+        sq3, _ = run(tile=3)
+        assert not torch.equal(sq1, sq3)  # otherwise the slots could not tell the two tiles apart
+        ops.TILE_HOOK = lambda dt_, chunk, s, arr: seen.append((s, ops.TILE_TABLE.get(s, 0))) or 0
+        _lib.lib.xggm_gemm_set_group_tile(1)
+        ops.TILE_TABLE = {sig: 3}
+        hit, _ = run()
+        assert seen == [(sig, 3)] and torch.equal(hit, sq3)  # the launch was given 3, and 3 won over the hook's 1
+        assert torch.equal(run(tile=3)[0], sq3)
+        ops.TILE_TABLE = {}
+        for _ in range(2):  # no hit: the hook still holds 1, every time
+            assert torch.equal(run()[0], sq1)
+    finally:
+        _lib.lib.xggm_gemm_set_group_tile(0)
         ops.TILE_TABLE, ops.TILE_HOOK = saved_t, saved_h

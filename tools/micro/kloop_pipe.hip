@@ -553,8 +553,7 @@ typedef struct xggm_gemm_problem {
     const float* scale_a; const float* scale_b; void* c8; const float* c8_qscale; float* c8_amax;
     int amax_slots;
 } xggm_gemm_problem;
-typedef int (*grouped_fn)(const xggm_gemm_problem*, int, void*);
-typedef int (*settile_fn)(int);
+typedef int (*grouped_fn)(const xggm_gemm_problem*, int, int, void*);  // (probs, n, tile, stream)
 
 struct Shape { const char* name; int N, K; };
 
@@ -613,7 +612,6 @@ int main(int argc, char** argv) {
     const char* libpath = argc > 1 ? argv[1] : "x-ggm_amd/csrc/libxggm_hip.so";
     void* lib = dlopen(libpath, RTLD_NOW);
     grouped_fn lib_grouped = lib ? (grouped_fn)dlsym(lib, "xggm_gemm_grouped_bf16") : nullptr;
-    settile_fn lib_tile = lib ? (settile_fn)dlsym(lib, "xggm_gemm_set_group_tile") : nullptr;
     if (!lib_grouped) printf("(library not loaded: %s)\n", dlerror());
 
     // ---- L2 -> LDS rate
@@ -688,15 +686,12 @@ int main(int argc, char** argv) {
         if (lib_grouped) {
             for (int tile = 0; tile <= 8; ++tile) {
                 if (tile == 5 || tile == 6) continue;
-                lib_tile(tile);
-                const float us = time_graph([&](hipStream_t s) { lib_grouped(lp, 2, s); });
+                const float us = time_graph([&](hipStream_t s) { lib_grouped(lp, 2, tile, s); });
                 static const char* tn[] = {"heuristic", "64x64", "128x64", "128x128/4w", "128x128/8w", "", "", "role 128x128", "role 128x64"};
                 printf("  library %-11s %7.2f us\n", tn[tile], us);
             }
-            lib_tile(3);
-            lib_grouped(lp, 2, nullptr);
+            lib_grouped(lp, 2, 3, nullptr);
             CHECK(hipDeviceSynchronize());
-            lib_tile(0);
         }
         auto check = [&](const char* what) {
             double worst = 0;

@@ -45,15 +45,13 @@ def main():
         st = ops.stream()
         rec = times.setdefault(sig, {p: [] for p in PINS})
         for pin in PINS:
-            _lib.lib.xggm_gemm_set_group_tile(pin)
             e = [torch.cuda.Event(enable_timing=True) for _ in range(REPS + 1)]
             e[0].record()
             for r in range(REPS):
-                rc = fn(ct.cast(arr, ct.c_void_p), len(chunk), st)
+                rc = fn(ct.cast(arr, ct.c_void_p), len(chunk), pin, st)
                 assert rc == 0, _lib.last_error()
                 e[r + 1].record()
             rec[pin].append(e)
-        _lib.lib.xggm_gemm_set_group_tile(0)
         return 0
 
     ops.TILE_HOOK = hook

@@ -21,47 +21,49 @@ namespace {
 typedef __attribute__((ext_vector_type(8))) short short8_t;
 typedef __attribute__((ext_vector_type(4))) float float4_t;
 
+// A kernel argument.  The defaults are "nothing asked for": make_args fills in what a problem sets, so a field added here
+// is initialised on every path.
 struct GemmArgs {
-    const void* A;
-    const void* B;
-    void* C;
-    int M, N, K;
-    int64_t a_rs, a_ks, b_ns, b_ks, ldc;
-    int64_t a_bs, b_bs, c_bs;
-    const float* bias;     // [N] or null
-    const void* residual;  // T, layout of C (same ldc / batch stride), or null
-    void* preact;          // T, layout of C, or null: alpha*acc + bias before the activation
-    const void* aux;       // T, layout of C: pre-activation u for act == GELU_GRAD
-    float* colsum;         // or null: [batch][ceil(M/32)][N] partial column sums of the stored result, one row per block of 32
-                           // output rows, every element written once by exactly one workgroup (no atomics: see xggm.h)
-    float* sqsum;          // or null: [ceil(M/64)][ceil(N/64)] sums of squares of the STORED fp32 values per 64 x 64 block
-    unsigned char* c8;     // or null: e4m3 copy of the stored result (layout of C), scaled by *c8_qscale
-    const float* c8_qscale;
-    float* c8_amax;        // or null: raised to max |stored value|
-    int amax_slots;        // floats the entry is spread over (xggm_gemm_problem.amax_slots)
-    const float* scale_a;  // fp8 operands: reciprocal quantisation scales (device scalars, null = 1)
-    const float* scale_b;
-    int act;
-    int c_f32;         // store C as float regardless of T
-    int accumulate;    // C += result
-    float alpha;
-    int a_mode, b_mode;  // 0 scalar, 1 vector along k, 2 vector along rows
+    const void* A = nullptr;
+    const void* B = nullptr;
+    void* C = nullptr;
+    int M = 0, N = 0, K = 0;
+    int64_t a_rs = 0, a_ks = 0, b_ns = 0, b_ks = 0, ldc = 0;
+    int64_t a_bs = 0, b_bs = 0, c_bs = 0;
+    const float* bias = nullptr;     // [N] or null
+    const void* residual = nullptr;  // T, layout of C (same ldc / batch stride), or null
+    void* preact = nullptr;          // T, layout of C, or null: alpha*acc + bias before the activation
+    const void* aux = nullptr;       // T, layout of C: pre-activation u for act == GELU_GRAD
+    float* colsum = nullptr;         // or null: [batch][ceil(M/32)][N] partial column sums of the stored result, one row per block of 32
+                                     // output rows, every element written once by exactly one workgroup (no atomics: see xggm.h)
+    float* sqsum = nullptr;          // or null: [ceil(M/64)][ceil(N/64)] sums of squares of the STORED fp32 values per 64 x 64 block
+    unsigned char* c8 = nullptr;     // or null: e4m3 copy of the stored result (layout of C), scaled by *c8_qscale
+    const float* c8_qscale = nullptr;
+    float* c8_amax = nullptr;        // or null: raised to max |stored value|
+    int amax_slots = 1;              // floats the entry is spread over (xggm_gemm_problem.amax_slots)
+    const float* scale_a = nullptr;  // fp8 operands: reciprocal quantisation scales (device scalars, null = 1)
+    const float* scale_b = nullptr;
+    int act = 0;
+    int c_f32 = 0;       // store C as float regardless of T
+    int accumulate = 0;  // C += result
+    float alpha = 1.f;
+    int a_mode = 0, b_mode = 0;  // 0 scalar, 1 vector along k, 2 vector along rows
     // tuned path on shapes that are not 8-aligned (A = 2274 answers, 630 edges), see pick_mode:
-    int a_tail, b_tail;  // k-contiguous operand with K % 8 != 0: the last chunk's elements >= K are zeroed on the way to LDS
-    int a_rows, b_rows;  // rows an operand may be READ at (row-contiguous operands: padded up to a multiple of 8)
-    int xcd_swizzle;
-    int batch;
-    int use_glds;  // k-major operand pairs take the LDS-DMA k-loop (gemm_kloop_glds)
+    int a_tail = 0, b_tail = 0;  // k-contiguous operand with K % 8 != 0: the last chunk's elements >= K are zeroed on the way to LDS
+    int a_rows = 0, b_rows = 0;  // rows an operand may be READ at (row-contiguous operands: padded up to a multiple of 8)
+    int xcd_swizzle = 1;
+    int batch = 1;
+    int use_glds = 1;  // k-major operand pairs take the LDS-DMA k-loop (gemm_kloop_glds)
     // block -> tile map of the grouped kernels, constants computed on the host per (problem, tile shape): see tile_from_map
     struct TileMap {
         int gx, gy, gxy;              // tile grid; tiles per batch entry
         int xr, xc, rh, rw;           // XCD rectangles: xr bands of rh tile rows x xc column groups of rw tiles
         int ncg, wb_last;             // non-empty column groups, width of the last one
         unsigned m_rw, m_wbl, m_gxy;  // ceil(2^32 / d) for d = rw, wb_last, gxy (unused where d == 1)
-    } tm;
+    } tm = {};
 #ifdef XGGM_STAMP
-    long long* stamp;  // instrumented build (make stamp): 8 cycle-counter slots per workgroup
-    int ablate;        // instrumented build: 1 skips the chunk loop of the epilogue, 2 the whole epilogue
+    long long* stamp = nullptr;  // instrumented build (make stamp): 8 cycle-counter slots per workgroup
+    int ablate = 0;              // instrumented build: 1 skips the chunk loop of the epilogue, 2 the whole epilogue
 #endif
 };
 
@@ -134,14 +136,22 @@ template <> struct Tile<float> {
 };
 
 constexpr int BM = 64, BN = 64, NT = 256;
-bool g_force_generic = false;  // test hook: xggm_gemm_set_generic
-int g_xcd_swizzle = 1;         // test hook: xggm_gemm_set_tile(variant | 0x100) disables it
-int g_glds_stages = 0;        // test hook: xggm_gemm_set_tile(variant | 0x800 / 0x1000) pins 2 / 3 LDS stages
-int g_single_grouped = 1;      // single problems with whole k-tiles also take the grouped (LDS-DMA) kernel: -0.05 ms per iteration
-                               // (same-box A/B 11.33 / 11.05 / 11.06 vs 11.01 / 11.00 / 11.03); xggm_gemm_set_tile(variant | 0x8000) turns it off
-int g_no_8w = 0;               // test hook: xggm_gemm_set_tile(variant | 0x4000): no 8-wave 128 x 128 tile
-int g_glds = 1;                // test hook: xggm_gemm_set_tile(variant | 0x400) keeps k-major pairs on the register-staged k-loop
-int g_group_tile = 0;          // test hook: 0 heuristic, 1: 64x64, 2: 128x64, 3: 128x128, 4: 128x128 on 8 waves
+// The process-wide test / A-B hooks (xggm_gemm_set_generic, xggm_gemm_set_tile, xggm_gemm_set_group_tile).  Only tests,
+// tools and the bench's A/B variables write them.  Every extern "C" entry point copies g_hooks ONCE and hands the copy
+// down: nothing below the entry points reads g_hooks, so one launch sees one consistent set of values.
+struct GemmHooks {
+    bool force_generic = false;  // xggm_gemm_set_generic
+    int tile_override = 0;       // xggm_gemm_set_tile(variant): single launches, 1 = 64x64 D2, 2 = 64x64 D4, 3 = 128x64 D2,
+                                 // 5 = 128x128 D2, 6-8 = depth 1; 0 = heuristic (see launch_fast)
+    int xcd_swizzle = 1;         // xggm_gemm_set_tile(variant | 0x100) disables it
+    int glds_stages = 0;         // xggm_gemm_set_tile(variant | 0x800 / 0x1000) pins 2 / 3 LDS stages
+    int single_grouped = 1;      // single problems with whole k-tiles also take the grouped (LDS-DMA) kernel: -0.05 ms per iteration
+                                 // (same-box A/B 11.33 / 11.05 / 11.06 vs 11.01 / 11.00 / 11.03); xggm_gemm_set_tile(variant | 0x8000) turns it off
+    int no_8w = 0;               // xggm_gemm_set_tile(variant | 0x4000): no 8-wave 128 x 128 tile
+    int glds = 1;                // xggm_gemm_set_tile(variant | 0x400) keeps k-major pairs on the register-staged k-loop
+    int group_tile = 0;          // xggm_gemm_set_group_tile: tile of grouped launches whose `tile` argument is 0
+};
+GemmHooks g_hooks;
 
 // stage a [64 rows][BK] operand tile into LDS (k contiguous).  elem(r,k) = base[r*rs + k*ks]
 template <typename T>
@@ -1436,11 +1446,17 @@ __device__ __forceinline__ void tile_from_map(const GemmArgs& g, int local, int 
 }
 
 inline unsigned magic_of(int d) { return d <= 1 ? 0u : (unsigned)(((1ull << 32) + (unsigned)d - 1) / (unsigned)d); }
-inline void set_tile_map(GemmArgs& g, int bm, int bn) {
+inline int set_tile_map(GemmArgs& g, int bm, int bn) {
     GemmArgs::TileMap& tm = g.tm;
     tm.gx = ceil_div(g.N, bn);
     tm.gy = ceil_div(g.M, bm);
-    tm.gxy = tm.gx * tm.gy;
+    // div_magic(n, d) is exact while n * d < 2^32.  tile_from_map takes L / gxy with L < gxy * batch (batched problems
+    // only), and r / rw or r / wb_last with r < rw * rh and wb_last <= rw: rw * rw * rh <= gx * gx * gy bounds both.
+    // (checked in an order that keeps every product below 2^64: gx, gy <= 2^25)
+    const uint64_t gx = tm.gx, gxy = gx * tm.gy, lim = 1ull << 32;
+    XGGM_REQUIRE(gxy <= INT32_MAX && gx * gxy < lim && (g.batch == 1 || gxy * gxy <= (lim - 1) / g.batch),
+                 "xggm_gemm_grouped: %d x %d tiles x batch %d: too many for the exact block -> tile map", tm.gy, tm.gx, g.batch);
+    tm.gxy = (int)gxy;
     // minimise xc * |A| + xr * |B| ~ xc * M + xr * N over xr * xc = 8
     int xr = 1;
     long best = 8l * g.M + g.N;
@@ -1457,6 +1473,7 @@ inline void set_tile_map(GemmArgs& g, int bm, int bn) {
     tm.m_rw = magic_of(tm.rw);
     tm.m_wbl = magic_of(tm.wb_last);
     tm.m_gxy = magic_of(tm.gxy);
+    return XGGM_OK;
 }
 
 // waves per SIMD the register allocation must leave room for: a second (third, fourth) resident
@@ -1513,6 +1530,19 @@ struct GroupArgs {
     int stages;  // LDS stages of the LDS-DMA k-loop (2 or 3), chosen per launch: see launch_grouped_tile
 };
 
+// lays the group out for bm x bn tiles: the block -> tile map of every problem and the tile prefix sums; *total: blocks
+int layout_group(GroupArgs& ga, int bm, int bn, int* total) {
+    int64_t t = 0;
+    for (int i = 0; i < ga.nprob; ++i) {
+        ga.tile_start[i] = (int)t;
+        if (int e = set_tile_map(ga.p[i], bm, bn)) return e;
+        t += (int64_t)ga.p[i].tm.gxy * ga.p[i].batch;
+        XGGM_REQUIRE(t <= INT32_MAX, "xggm_gemm_grouped: more than 2^31 - 1 tiles in one launch");
+    }
+    ga.tile_start[ga.nprob] = *total = (int)t;
+    return XGGM_OK;
+}
+
 template <int BM, int BN, int W = 4>
 __global__ __launch_bounds__(64 * W, (W == 8 ? 2 : min_waves<BM, BN>())) void gemm_grouped_kernel(GroupArgs ga) {
     extern __shared__ __attribute__((aligned(16))) bf16 fsm[];
@@ -1556,14 +1586,9 @@ __global__ __launch_bounds__(64 * W, (W == 8 ? 2 : min_waves<BM, BN>())) void ge
     gemm_finish<BM, BN, W>(g, tile_m, tile_n, bz, fsm, acc);
 }
 
-template <int BM, int BN, int W = 4> int launch_grouped_tile(GroupArgs& ga, hipStream_t stream) {
-    int total = 0;
-    for (int i = 0; i < ga.nprob; ++i) {
-        ga.tile_start[i] = total;
-        set_tile_map(ga.p[i], BM, BN);
-        total += ga.p[i].tm.gxy * ga.p[i].batch;
-    }
-    ga.tile_start[ga.nprob] = total;
+template <int BM, int BN, int W = 4> int launch_grouped_tile(GroupArgs& ga, const GemmHooks& h, hipStream_t stream) {
+    int total;
+    if (int e = layout_group(ga, BM, BN, &total)) return e;
     // Stages of the LDS-DMA k-loop (NS - 1 k-tiles in flight per workgroup).  On L2-hot operands (a micro-benchmark
     // that relaunches the same problem) two stages win wherever a third costs a resident workgroup (72 KB per 128 x 64
     // workgroup = two per CU; FFN forward pair, 672 tiles: 18.8 us with two stages, 21.4 with three).  Inside the
@@ -1573,7 +1598,7 @@ template <int BM, int BN, int W = 4> int launch_grouped_tile(GroupArgs& ga, hipS
     // 128 x 128 on 8 waves: 18.1 | 20.6 | 17.4 | 17.5.  Three everywhere except the 4-wave 128 x 128 tile (3 x 64 KB
     // would leave one workgroup per CU where two fit).
     // four-wave tiles whose three stages would leave ONE workgroup per CU take two (128 x 128: 2 x 64 KB; 192 x 128: 2 x 80 KB)
-    ga.stages = g_glds_stages ? g_glds_stages : (W == 4 && 2 * 3 * sizeof(bf16) * (BM + BN) * 64 > 160 * 1024) ? 2 : 3;
+    ga.stages = h.glds_stages ? h.glds_stages : (W == 4 && 2 * 3 * sizeof(bf16) * (BM + BN) * 64 > 160 * 1024) ? 2 : 3;
     while (ga.stages > 2 && ga.stages * sizeof(bf16) * (BM + BN) * 64 > 160 * 1024) --ga.stages;
     // LDS of the largest operand images this group actually uses (r-major images carry padding)
     size_t lds = 0;
@@ -1628,13 +1653,8 @@ __global__ __launch_bounds__(512, (role_min_waves<BM, BN>())) void gemm_grouped_
 }
 
 template <int BM, int BN> int launch_grouped_role(GroupArgs& ga, hipStream_t stream) {
-    int total = 0;
-    for (int i = 0; i < ga.nprob; ++i) {
-        ga.tile_start[i] = total;
-        set_tile_map(ga.p[i], BM, BN);
-        total += ga.p[i].tm.gxy * ga.p[i].batch;
-    }
-    ga.tile_start[ga.nprob] = total;
+    int total;
+    if (int e = layout_group(ga, BM, BN, &total)) return e;
     ga.stages = ROLE_NS;
     // the stages, or the staged epilogue's (BM / 2) x (BN + 4) floats of the same memory
     constexpr size_t lds = std::max(ROLE_NS * sizeof(bf16) * (BM + BN) * 64, sizeof(float) * (BM / 2) * (BN + 4));
@@ -1672,17 +1692,12 @@ __global__ __launch_bounds__(64 * W, (W == 8 ? 2 : min_waves<BM, BN>())) void ge
     gemm_finish<BM, BN, W>(g, tile_m, tile_n, bz, fsm, acc);
 }
 
-template <int BM, int BN, int W = 4> int launch_grouped_fp8_tile(GroupArgs& ga, hipStream_t stream) {
-    int total = 0;
-    for (int i = 0; i < ga.nprob; ++i) {
-        ga.tile_start[i] = total;
-        set_tile_map(ga.p[i], BM, BN);
-        total += ga.p[i].tm.gxy * ga.p[i].batch;
-    }
-    ga.tile_start[ga.nprob] = total;
+template <int BM, int BN, int W = 4> int launch_grouped_fp8_tile(GroupArgs& ga, const GemmHooks& h, hipStream_t stream) {
+    int total;
+    if (int e = layout_group(ga, BM, BN, &total)) return e;
     // k-major images of 128 bytes per row (128 e4m3 values), double buffered; the staged epilogue needs
     // (BM / 2) x (BN + 4) floats of the same memory
-    ga.stages = g_glds_stages ? std::min(g_glds_stages, 3) : (BM * BN == 128 * 128 && W == 4) ? 2 : 3;
+    ga.stages = h.glds_stages ? std::min(h.glds_stages, 3) : (BM * BN == 128 * 128 && W == 4) ? 2 : 3;
     bool glds = true;
     for (int i = 0; i < ga.nprob; ++i) glds = glds && glds_ok<true>(ga.p[i]);
     const size_t lds = std::max((glds ? ga.stages : 2) * sizeof(bf16) * (OpLds<BM, true>::ELEMS + OpLds<BN, true>::ELEMS),
@@ -1711,19 +1726,13 @@ template <int BM, int BN, int D> int launch_fast_tile(const GemmArgs& g, int bat
     return xggm_check_launch("xggm_gemm(fast)");
 }
 
-// tile / depth choice.  g_tile_override (xggm_gemm_set_tile) pins one variant for A/B tests:
+// tile / depth choice.  `v` (GemmHooks::tile_override, xggm_gemm_set_tile) pins one variant for A/B tests:
 // 1 = 64x64 D2, 2 = 64x64 D4, 3 = 128x64 D2, 5 = 128x128 D2, 6-8 = depth 1; 0 = heuristic.
-int g_tile_override = 0;
-inline int launch_fast(const GemmArgs& g, int batch, hipStream_t stream) {
-    auto tiles = [&](int bm, int bn) { return (int64_t)ceil_div(g.M, bm) * ceil_div(g.N, bn) * batch; };
-    int v = g_tile_override;
-    if (v == 0) {
-        // measured on MI355X at the step's shapes (tools/bench_gemm.py): 64x64 tiles win everywhere
-        // (these GEMMs need many workgroups more than big tiles); depth 4 helps when an operand is
-        // k-major, depth 2 is better for the all-transposed wgrad form
-        (void)tiles;
-        v = (g.a_mode == 2 && g.b_mode == 2) ? 1 : 2;
-    }
+inline int launch_fast(const GemmArgs& g, int batch, int v, hipStream_t stream) {
+    // measured on MI355X at the step's shapes (tools/bench_gemm.py): 64x64 tiles win everywhere
+    // (these GEMMs need many workgroups more than big tiles); depth 4 helps when an operand is
+    // k-major, depth 2 is better for the all-transposed wgrad form
+    if (v == 0) v = (g.a_mode == 2 && g.b_mode == 2) ? 1 : 2;
     switch (v) {
         case 6: return launch_fast_tile<64, 64, 1>(g, batch, stream);
         case 7: return launch_fast_tile<128, 64, 1>(g, batch, stream);
@@ -1763,7 +1772,23 @@ template <typename T> int pick_mode(const void* base, int64_t rs, int64_t ks, in
     return 0;
 }
 
-template <typename T> int launch(GemmArgs g, int batch, hipStream_t stream) {
+// The one place a GemmArgs is filled from what the caller asked for; the operand modes (pick_mode) and the tile map
+// (set_tile_map) are added on the way to the launch.
+GemmArgs from_problem(const xggm_gemm_problem& p, const GemmHooks& h) {
+    GemmArgs g;
+    g.A = p.A; g.B = p.B; g.C = p.C; g.M = p.M; g.N = p.N; g.K = p.K;
+    g.a_rs = p.a_rs; g.a_ks = p.a_ks; g.b_ns = p.b_ns; g.b_ks = p.b_ks; g.ldc = p.ldc;
+    g.a_bs = p.a_bs; g.b_bs = p.b_bs; g.c_bs = p.c_bs;
+    g.bias = p.bias; g.residual = p.residual; g.preact = p.preact; g.aux = p.aux; g.colsum = p.colsum; g.sqsum = p.sqsum;
+    g.c8 = reinterpret_cast<unsigned char*>(p.c8); g.c8_qscale = p.c8_qscale; g.c8_amax = p.c8_amax;
+    g.amax_slots = p.amax_slots > 1 ? p.amax_slots : 1;
+    g.scale_a = p.scale_a; g.scale_b = p.scale_b;
+    g.act = p.act; g.c_f32 = p.c_f32; g.accumulate = p.accumulate; g.alpha = p.alpha;
+    g.xcd_swizzle = h.xcd_swizzle; g.batch = p.batch; g.use_glds = h.glds; SET_STAMP(g);
+    return g;
+}
+
+template <typename T> int launch(GemmArgs g, int batch, const GemmHooks& h, hipStream_t stream) {
     XGGM_REQUIRE(g.M > 0 && g.N > 0 && g.K > 0 && batch > 0, "xggm_gemm: empty problem M=%d N=%d K=%d batch=%d", g.M, g.N,
                  g.K, batch);
     XGGM_REQUIRE(g.A && g.B && g.C, "xggm_gemm: null operand");
@@ -1776,7 +1801,7 @@ template <typename T> int launch(GemmArgs g, int batch, hipStream_t stream) {
     dim3 grid(ceil_div(g.N, BN), ceil_div(g.M, BM), batch);
     XGGM_REQUIRE(grid.y <= 65535 && grid.z <= 65535, "xggm_gemm: grid too large");
     if constexpr (sizeof(T) == 2) {
-        if (g.a_mode != 0 && g.b_mode != 0 && !g_force_generic) return launch_fast(g, batch, stream);
+        if (g.a_mode != 0 && g.b_mode != 0 && !h.force_generic) return launch_fast(g, batch, h.tile_override, stream);
     }
     XGGM_REQUIRE(!g.sqsum, "xggm_gemm: sqsum needs the tuned bf16 kernels (8-aligned operands); this problem runs on the "
                            "generic kernel");
@@ -1794,15 +1819,14 @@ template <typename T> int launch(GemmArgs g, int batch, hipStream_t stream) {
                         int64_t b_ns, int64_t b_ks, int64_t ldc, int batch, int64_t a_bs, int64_t b_bs, int64_t c_bs, \
                         const float* bias, const void* residual, void* preact, const void* aux, float* colsum,       \
                         int act, int c_f32, int accumulate, float alpha, hipStream_t stream) {                        \
-        GemmArgs g;                                                                                                    \
-        g.A = A; g.B = B; g.C = C; g.M = M; g.N = N; g.K = K;                                                          \
-        g.a_rs = a_rs; g.a_ks = a_ks; g.b_ns = b_ns; g.b_ks = b_ks; g.ldc = ldc;                                       \
-        g.a_bs = a_bs; g.b_bs = b_bs; g.c_bs = c_bs;                                                                   \
-        g.bias = bias; g.residual = residual; g.preact = preact; g.aux = aux; g.colsum = colsum; g.sqsum = nullptr;   \
-        g.c8 = nullptr; g.c8_qscale = nullptr; g.c8_amax = nullptr; g.scale_a = g.scale_b = nullptr; g.amax_slots = 1;  \
-        g.act = act; g.c_f32 = c_f32; g.accumulate = accumulate; g.alpha = alpha;                                     \
-        g.a_mode = g.b_mode = 0; g.xcd_swizzle = g_xcd_swizzle; g.batch = batch; g.use_glds = g_glds; SET_STAMP(g); \
-        return launch<T>(g, batch, stream);                                                                            \
+        const GemmHooks h = g_hooks;                                                                                   \
+        xggm_gemm_problem p = {};                                                                                      \
+        p.A = A; p.B = B; p.C = C; p.M = M; p.N = N; p.K = K;                                                          \
+        p.a_rs = a_rs; p.a_ks = a_ks; p.b_ns = b_ns; p.b_ks = b_ks; p.ldc = ldc;                                       \
+        p.batch = batch; p.a_bs = a_bs; p.b_bs = b_bs; p.c_bs = c_bs;                                                  \
+        p.bias = bias; p.residual = residual; p.preact = preact; p.aux = aux; p.colsum = colsum;                      \
+        p.act = act; p.c_f32 = c_f32; p.accumulate = accumulate; p.alpha = alpha;                                     \
+        return launch<T>(from_problem(p, h), batch, h, stream);                                                        \
     }
 
 XGGM_GEMM_IMPL(xggm_gemm_f32, float)
@@ -1822,16 +1846,14 @@ extern "C" int xggm_gemm_fp8e4m3(const void* A, const void* B, void* C, int M, i
     XGGM_REQUIRE(ldc >= N, "xggm_gemm_fp8e4m3: ldc %lld < N %d", (long long)ldc, N);
     XGGM_REQUIRE((int64_t)(M - 1) * a_rs + K < OOB_OFFSET && (int64_t)(N - 1) * b_ns + K < OOB_OFFSET,
                  "xggm_gemm_fp8e4m3: operand larger than 2 GiB");
-    GemmArgs g;
-    g.A = A; g.B = B; g.C = C; g.M = M; g.N = N; g.K = K;
-    g.a_rs = a_rs; g.a_ks = 1; g.b_ns = b_ns; g.b_ks = 1; g.ldc = ldc;
-    g.a_bs = g.b_bs = g.c_bs = 0;
-    g.bias = bias; g.residual = residual; g.preact = preact; g.aux = nullptr; g.colsum = nullptr; g.sqsum = nullptr;
-    g.c8 = nullptr; g.c8_qscale = nullptr; g.c8_amax = nullptr; g.scale_a = g.scale_b = nullptr; g.amax_slots = 1;
-    g.act = act; g.c_f32 = c_f32; g.accumulate = 0; g.alpha = 1.0f;
-    g.a_mode = g.b_mode = 1; g.a_tail = g.b_tail = 0; g.a_rows = M; g.b_rows = N;
-    g.xcd_swizzle = g_xcd_swizzle; g.batch = 1; g.use_glds = g_glds; SET_STAMP(g);
-    switch (g_tile_override) {  // same pins as the bf16 kernels (xggm_gemm_set_tile); default 64 x 64, depth 4
+    const GemmHooks h = g_hooks;
+    xggm_gemm_problem p = {};
+    p.A = A; p.B = B; p.C = C; p.M = M; p.N = N; p.K = K;
+    p.a_rs = a_rs; p.a_ks = 1; p.b_ns = b_ns; p.b_ks = 1; p.ldc = ldc; p.batch = 1;
+    p.bias = bias; p.residual = residual; p.preact = preact; p.act = act; p.c_f32 = c_f32; p.alpha = 1.0f;
+    GemmArgs g = from_problem(p, h);  // the scales travel as kernel arguments of their own
+    g.a_mode = g.b_mode = 1; g.a_rows = M; g.b_rows = N;
+    switch (h.tile_override) {  // same pins as the bf16 kernels (xggm_gemm_set_tile); default 64 x 64, depth 4
         case 3: return launch_fp8_tile<128, 64, 2>(g, scale_a, scale_b, stream);
         case 5: return launch_fp8_tile<128, 128, 2>(g, scale_a, scale_b, stream);
         case 1: return launch_fp8_tile<64, 64, 2>(g, scale_a, scale_b, stream);
@@ -1841,43 +1863,29 @@ extern "C" int xggm_gemm_fp8e4m3(const void* A, const void* B, void* C, int M, i
 
 // test/diagnostic hook: route bf16 GEMMs through the generic kernel (1) or the tuned one (0)
 extern "C" int xggm_gemm_set_generic(int on) {
-    g_force_generic = on != 0;
+    g_hooks.force_generic = on != 0;
     return XGGM_OK;
 }
 
 extern "C" int xggm_gemm_set_tile(int variant) {
-    g_tile_override = variant & 0xff;
-    g_xcd_swizzle = (variant & 0x100) ? 0 : 1;
-    g_glds = (variant & 0x400) ? 0 : 1;
-    g_no_8w = (variant & 0x4000) ? 1 : 0;
-    g_single_grouped = (variant & 0x8000) ? 0 : 1;
-    g_glds_stages = (variant & 0x800) ? 2 : (variant & 0x1000) ? 3 : (variant & 0x2000) ? 4 : 0;
+    g_hooks.tile_override = variant & 0xff;
+    g_hooks.xcd_swizzle = (variant & 0x100) ? 0 : 1;
+    g_hooks.glds = (variant & 0x400) ? 0 : 1;
+    g_hooks.no_8w = (variant & 0x4000) ? 1 : 0;
+    g_hooks.single_grouped = (variant & 0x8000) ? 0 : 1;
+    g_hooks.glds_stages = (variant & 0x800) ? 2 : (variant & 0x1000) ? 3 : (variant & 0x2000) ? 4 : 0;
     return XGGM_OK;
 }
 
 // ---- grouped entry point -------------------------------------------------------------------------
 namespace {
-GemmArgs from_problem(const xggm_gemm_problem& p) {
-    GemmArgs g;
-    g.A = p.A; g.B = p.B; g.C = p.C; g.M = p.M; g.N = p.N; g.K = p.K;
-    g.a_rs = p.a_rs; g.a_ks = p.a_ks; g.b_ns = p.b_ns; g.b_ks = p.b_ks; g.ldc = p.ldc;
-    g.a_bs = p.a_bs; g.b_bs = p.b_bs; g.c_bs = p.c_bs;
-    g.bias = p.bias; g.residual = p.residual; g.preact = p.preact; g.aux = p.aux; g.colsum = p.colsum; g.sqsum = p.sqsum;
-    g.c8 = reinterpret_cast<unsigned char*>(p.c8); g.c8_qscale = p.c8_qscale; g.c8_amax = p.c8_amax;
-    g.amax_slots = p.amax_slots > 1 ? p.amax_slots : 1;
-    g.scale_a = p.scale_a; g.scale_b = p.scale_b;
-    g.act = p.act; g.c_f32 = p.c_f32; g.accumulate = p.accumulate; g.alpha = p.alpha;
-    g.a_mode = g.b_mode = 0; g.xcd_swizzle = g_xcd_swizzle; g.batch = p.batch; g.use_glds = g_glds; SET_STAMP(g);
-    return g;
-}
-
 // tile choice from a launch-time model fitted to tools/gemm_ktime.py and tools/bench_gemm.py on
 // MI355X (microseconds): T = max(a + b r + s W, f + k nk_max), with r = tiles per CU,
 // W = k-tiles per CU and the second term the longest single tile (one CU's critical
 // path: long-K problems need small tiles).  Big tiles run the k-loop ~1.3x more efficiently
 // per flop, small ones have the shorter critical path and fill the CUs of a small group.
-// `kt`: reduction elements per k-tile (64 bf16, 128 e4m3: the same bytes).
-int pick_group_tile(const GroupArgs& ga, int n, int kt) {
+// `kt`: reduction elements per k-tile (64 bf16, 128 e4m3: the same bytes).  `tile`: the launch's pin, 0 = the model chooses.
+int pick_group_tile(const GroupArgs& ga, int n, int kt, int tile) {
     struct TileModel { int bm, bn; float a, b, s, f, k; };
     struct TileModels { TileModel m[3]; };
     // the fitted constants; A/B hook: XGGM_TILE_MODEL="a,b,s,f,k;a,b,s,f,k;a,b,s,f,k" overrides them
@@ -1896,7 +1904,7 @@ int pick_group_tile(const GroupArgs& ga, int n, int kt) {
         }
         return t;
     }();
-    int v = g_group_tile;
+    int v = tile;
     if (v == 0) {
         float best = 0.f;
         for (int c = 0; c < 3; ++c) {
@@ -1921,13 +1929,21 @@ int pick_group_tile(const GroupArgs& ga, int n, int kt) {
     return v;
 }
 
-template <typename T> int grouped(const xggm_gemm_problem* probs, int n, hipStream_t stream) {
+// The `tile` argument of the grouped entry points: 0 = no pin, 1-4 and 7-9 as in xggm.h.  A non-zero argument wins over
+// the process-wide hook (xggm_gemm_set_group_tile: not validated, experiment builds reach their tiles 5 / 6 through it),
+// which wins over the library's choice.
+inline bool group_tile_ok(int tile) { return (tile >= 0 && tile <= 4) || (tile >= 7 && tile <= 9); }
+
+// `h` by value: the entry points' one copy of the hooks
+template <typename T> int grouped(const xggm_gemm_problem* probs, int n, int tile, const GemmHooks h, hipStream_t stream) {
     XGGM_REQUIRE(probs && n > 0, "xggm_gemm_grouped: no problems");
-    bool fast = sizeof(T) == 2 && !g_force_generic && n <= MAX_GROUP;
+    XGGM_REQUIRE(group_tile_ok(tile), "xggm_gemm_grouped: tile %d (0: the library chooses; 1-4, 7-9: see xggm.h)", tile);
+    const int pin = tile ? tile : h.group_tile;
+    bool fast = sizeof(T) == 2 && !h.force_generic && n <= MAX_GROUP;
     GroupArgs ga;
     ga.nprob = n;
     for (int i = 0; i < n && fast; ++i) {
-        GemmArgs g = from_problem(probs[i]);
+        GemmArgs g = from_problem(probs[i], h);
         if (!(g.M > 0 && g.N > 0 && g.K > 0 && g.batch > 0 && g.A && g.B && g.C)) fast = false;
         g.a_mode = pick_mode<T>(g.A, g.a_rs, g.a_ks, g.a_bs, g.M, g.K, &g.a_tail, &g.a_rows);
         g.b_mode = pick_mode<T>(g.B, g.b_ns, g.b_ks, g.b_bs, g.N, g.K, &g.b_tail, &g.b_rows);
@@ -1937,13 +1953,13 @@ template <typename T> int grouped(const xggm_gemm_problem* probs, int n, hipStre
     // longest k-loops first: their tiles start early and the short ones fill the tail
     for (int i = 1; i < n && fast; ++i)
         for (int j = i; j > 0 && ga.p[j].K > ga.p[j - 1].K; --j) std::swap(ga.p[j], ga.p[j - 1]);
-    if (!fast || (n == 1 && !(g_single_grouped && glds_ok<false>(ga.p[0])))) {  // odd shapes, fp32 mode or a single problem: one launch each
+    if (!fast || (n == 1 && !(h.single_grouped && glds_ok<false>(ga.p[0])))) {  // odd shapes, fp32 mode or a single problem: one launch each
         for (int i = 0; i < n; ++i)
-            if (int e = launch<T>(from_problem(probs[i]), probs[i].batch, stream)) return e;
+            if (int e = launch<T>(from_problem(probs[i], h), probs[i].batch, h, stream)) return e;
         return XGGM_OK;
     }
-    int v = pick_group_tile(ga, n, 64);
-    if (g_group_tile == 0 && sizeof(T) == 2) {
+    int v = pick_group_tile(ga, n, 64, pin);
+    if (pin == 0 && sizeof(T) == 2) {
         // 128 x 128 on eight waves (two per SIMD inside one workgroup, a third fewer LDS bytes per flop than two
         // 128 x 64 tiles): measured faster exactly where one round of such tiles covers the chip and the k-loop is
         // long enough to matter -- the fused QKV forward pair, 17.6 -> 15.5 us; slower where the tiles need a second
@@ -1956,7 +1972,7 @@ template <typename T> int grouped(const xggm_gemm_problem* probs, int n, hipStre
             kmaj = kmaj && ga.p[i].a_mode == 1 && ga.p[i].b_mode == 1;
             nkmin = std::min(nkmin, ceil_div(ga.p[i].K, 64));
         }
-        if (kmaj && t128 > 200 && t128 <= 256 && nkmin >= 12 && !g_no_8w) v = 4;
+        if (kmaj && t128 > 200 && t128 <= 256 && nkmin >= 12 && !h.no_8w) v = 4;
         // From 1.75 128 x 128 tiles per CU: the four-wave 128 x 128 tile (two workgroups per CU, 64 x 64 per wave = half the
         // LDS fragment bytes per MFMA of the other tiles).  The cost model above was fitted at 32 samples, where only the
         // FFN2 backward group is this large (and the in-step tuner pinned it to this tile); at 64 samples and at the
@@ -1971,8 +1987,8 @@ template <typename T> int grouped(const xggm_gemm_problem* probs, int n, hipStre
     // forward pair in isolation, never the fastest inside the step, 91 spilled registers.  The epilogues above stay
     // general in the tile shape: whole 64-row blocks, 32-row column-sum blocks.)
 #ifdef XGGM_BIG_TILES  // experiment builds only (make alt ALT=-DXGGM_BIG_TILES): 128 x 256 / 256 x 128 on eight waves
-    if (v == 5) return launch_grouped_tile<128, 256, 8>(ga, stream);
-    if (v == 6) return launch_grouped_tile<256, 128, 8>(ga, stream);
+    if (v == 5) return launch_grouped_tile<128, 256, 8>(ga, h, stream);
+    if (v == 6) return launch_grouped_tile<256, 128, 8>(ga, h, stream);
 #endif
     if (v >= 7 && v <= 9) {  // role k-loop: whole k-tiles in every problem, otherwise the four-wave tile of the same shape
         bool ok = true;
@@ -1982,19 +1998,22 @@ template <typename T> int grouped(const xggm_gemm_problem* probs, int n, hipStre
                           : v == 8 ? launch_grouped_role<128, 64>(ga, stream) : launch_grouped_role<64, 64>(ga, stream);
         v = v == 7 ? 3 : v == 8 ? 2 : 1;
     }
-    if (v == 4) return launch_grouped_tile<128, 128, 8>(ga, stream);
-    if (v == 3) return launch_grouped_tile<128, 128>(ga, stream);
-    if (v == 2) return launch_grouped_tile<128, 64>(ga, stream);
-    return launch_grouped_tile<64, 64>(ga, stream);
+    if (v == 4) return launch_grouped_tile<128, 128, 8>(ga, h, stream);
+    if (v == 3) return launch_grouped_tile<128, 128>(ga, h, stream);
+    if (v == 2) return launch_grouped_tile<128, 64>(ga, h, stream);
+    return launch_grouped_tile<64, 64>(ga, h, stream);
 }
 }  // namespace
 
-extern "C" int xggm_gemm_grouped_fp8e4m3(const xggm_gemm_problem* probs, int n, hipStream_t stream) {
+extern "C" int xggm_gemm_grouped_fp8e4m3(const xggm_gemm_problem* probs, int n, int tile, hipStream_t stream) {
     XGGM_REQUIRE(probs && n > 0 && n <= MAX_GROUP, "xggm_gemm_grouped_fp8e4m3: 1..%d problems per launch (n = %d)", MAX_GROUP, n);
+    XGGM_REQUIRE(group_tile_ok(tile), "xggm_gemm_grouped_fp8e4m3: tile %d (0: the library chooses; 1-4, 7-9: see xggm.h)", tile);
+    const GemmHooks h = g_hooks;
+    const int pin = tile ? tile : h.group_tile;
     GroupArgs ga;
     ga.nprob = n;
     for (int i = 0; i < n; ++i) {
-        GemmArgs g = from_problem(probs[i]);
+        GemmArgs g = from_problem(probs[i], h);
         XGGM_REQUIRE(g.M > 0 && g.N > 0 && g.K > 0 && g.batch > 0 && g.A && g.B && g.C,
                      "xggm_gemm_grouped_fp8e4m3: empty problem or null operand (%d)", i);
         XGGM_REQUIRE(g.a_ks == 1 && g.b_ks == 1, "xggm_gemm_grouped_fp8e4m3: e4m3 operands are k-contiguous");
@@ -2012,32 +2031,31 @@ extern "C" int xggm_gemm_grouped_fp8e4m3(const xggm_gemm_problem* probs, int n, 
                          (int64_t)(g.N - 1) * g.b_ns + (int64_t)(g.batch - 1) * g.b_bs + g.K < OOB_OFFSET,
                      "xggm_gemm_grouped_fp8e4m3: operand larger than 2 GiB");
         g.a_mode = g.b_mode = 1;
-        g.a_tail = g.b_tail = 0;
         g.a_rows = g.M;
         g.b_rows = g.N;
         ga.p[i] = g;
     }
     for (int i = 1; i < n; ++i)  // longest k-loops first
         for (int j = i; j > 0 && ga.p[j].K > ga.p[j - 1].K; --j) std::swap(ga.p[j], ga.p[j - 1]);
-    int v = pick_group_tile(ga, n, 128);
-    if (g_group_tile == 0) {
+    int v = pick_group_tile(ga, n, 128, pin);
+    if (pin == 0) {
         // 128 x 128 on eight waves where ONE round of such tiles covers the chip (the fused QKV pair: 252 tiles), as
         // for the bf16 products -- but unlike there it buys nothing (k-loops of 6 e4m3 k-tiles): XGGM_FP8_8W=1 turns it on
         static const bool use8 = getenv("XGGM_FP8_8W") && atoi(getenv("XGGM_FP8_8W")) == 1;  // measured: 11.18 vs 11.16 ms per iteration without it -- off
         int64_t t128 = 0;
         for (int i = 0; i < n; ++i) t128 += (int64_t)ceil_div(ga.p[i].M, 128) * ceil_div(ga.p[i].N, 128) * ga.p[i].batch;
-        if (use8 && t128 > 200 && t128 <= 256 && !g_no_8w) v = 4;
+        if (use8 && t128 > 200 && t128 <= 256 && !h.no_8w) v = 4;
     }
-    if (v == 4) return launch_grouped_fp8_tile<128, 128, 8>(ga, stream);
-    if (v == 3) return launch_grouped_fp8_tile<128, 128>(ga, stream);
-    if (v == 2) return launch_grouped_fp8_tile<128, 64>(ga, stream);
-    return launch_grouped_fp8_tile<64, 64>(ga, stream);
+    if (v == 4) return launch_grouped_fp8_tile<128, 128, 8>(ga, h, stream);
+    if (v == 3) return launch_grouped_fp8_tile<128, 128>(ga, h, stream);
+    if (v == 2) return launch_grouped_fp8_tile<128, 64>(ga, h, stream);
+    return launch_grouped_fp8_tile<64, 64>(ga, h, stream);  // 1, and 7-9: there is no role k-loop for e4m3 operands
 }
-extern "C" int xggm_gemm_grouped_bf16(const xggm_gemm_problem* probs, int n, hipStream_t stream) {
-    return grouped<bf16>(probs, n, stream);
+extern "C" int xggm_gemm_grouped_bf16(const xggm_gemm_problem* probs, int n, int tile, hipStream_t stream) {
+    return grouped<bf16>(probs, n, tile, g_hooks, stream);
 }
-extern "C" int xggm_gemm_grouped_f32(const xggm_gemm_problem* probs, int n, hipStream_t stream) {
-    return grouped<float>(probs, n, stream);
+extern "C" int xggm_gemm_grouped_f32(const xggm_gemm_problem* probs, int n, int tile, hipStream_t stream) {
+    return grouped<float>(probs, n, tile, g_hooks, stream);
 }
 #ifdef XGGM_STAMP
 // what the runtime thinks: resident workgroups per CU of the grouped kernels at a given dynamic LDS size
@@ -2067,6 +2085,6 @@ extern "C" int xggm_gemm_set_stamp(long long* buf) {
 }
 #endif
 extern "C" int xggm_gemm_set_group_tile(int v) {
-    g_group_tile = v;
+    g_hooks.group_tile = v;
     return XGGM_OK;
 }

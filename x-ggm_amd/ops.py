@@ -249,25 +249,9 @@ def p_fwd8(x8, w8, sx, sw, bias=None, act=ACT_NONE, want_preact=False, emit8=Non
 GROUP_MAX = 6  # MAX_GROUP of gemm.hip: problems one grouped launch takes
 
 
-def gemm_group8(problems):
-    """launch up to GROUP_MAX e4m3 forward products in one grid (more: consecutive groups); the measured tile table
-    applies as for the bf16 groups (signatures start with ``e4m3|``)."""
-    for i in range(0, len(problems), GROUP_MAX):
-        chunk = problems[i:i + GROUP_MAX]
-        arr = (GemmProblem * len(chunk))(*chunk)
-        pin = 0
-        if TILE_TABLE or TILE_HOOK is not None:
-            sig = gemm_signature("e4m3", chunk)
-            pin = TILE_TABLE.get(sig, 0)
-            if TILE_HOOK is not None:
-                pin = TILE_HOOK("e4m3", chunk, sig, arr) or pin
-        if pin:
-            _lib.lib.xggm_gemm_set_group_tile(pin)
-        try:
-            call("xggm_gemm_grouped_fp8e4m3", _ct.cast(arr, _ct.c_void_p), len(chunk), stream())
-        finally:
-            if pin:
-                _lib.lib.xggm_gemm_set_group_tile(0)
+def gemm_group8(problems, tile=0):
+    """``gemm_group`` for e4m3 forward products (p_fwd8)."""
+    gemm_group("e4m3", problems, tile)
 
 
 def p_dgrad(dy, w, residual=None, gelu_aux=None, colsum=None, into=None, defer=None):
@@ -341,7 +325,7 @@ def _load_tile_table():
 
 
 TILE_TABLE = _load_tile_table()
-TILE_HOOK = None  # tools/tune_gemm.py: callable(dt, chunk, signature) -> tile pin (or None) run in front of every launch
+TILE_HOOK = None  # tools/tune_gemm.py: callable(dt, chunk, signature, problem array) -> tile pin (or None) run in front of every launch
 
 
 def gemm_signature(dt, chunk):
@@ -356,24 +340,21 @@ def gemm_signature(dt, chunk):
     return (dt if isinstance(dt, str) else sfx(dt)) + "|" + "+".join(parts)
 
 
-def gemm_group(dt, problems):
-    """launch up to GROUP_MAX independent products in one grid (more: consecutive groups)."""
+def gemm_group(dt, problems, tile=0):
+    """launch up to GROUP_MAX independent products in one grid (more: consecutive groups).  ``dt``: the storage type, or
+    "e4m3" for forward products with e4m3 operands (p_fwd8).  The tile travels with the launch: ``tile`` if given, else
+    the measured table's entry for the launch's signature, else 0 = the library chooses (xggm.h: argument ``tile``)."""
+    name = "xggm_gemm_grouped_" + ("fp8e4m3" if dt == "e4m3" else sfx(dt))
     for i in range(0, len(problems), GROUP_MAX):
         chunk = problems[i:i + GROUP_MAX]
         arr = (GemmProblem * len(chunk))(*chunk)
-        pin = 0
+        pin = tile
         if TILE_TABLE or TILE_HOOK is not None:
             sig = gemm_signature(dt, chunk)
-            pin = TILE_TABLE.get(sig, 0)
+            pin = tile or TILE_TABLE.get(sig, 0)
             if TILE_HOOK is not None:
                 pin = TILE_HOOK(dt, chunk, sig, arr) or pin
-        if pin:
-            _lib.lib.xggm_gemm_set_group_tile(pin)
-        try:
-            call("xggm_gemm_grouped_" + sfx(dt), _ct.cast(arr, _ct.c_void_p), len(chunk), stream())
-        finally:
-            if pin:
-                _lib.lib.xggm_gemm_set_group_tile(0)
+        call(name, _ct.cast(arr, _ct.c_void_p), len(chunk), pin, stream())
         reduce_batch([p.post for p in chunk if getattr(p, "post", None) is not None])  # column sums nobody deferred
 
 
