@@ -688,6 +688,42 @@ int xggm_tanh_bwd_bf16(const void* dy, const void* y, void* out, int64_t n, xggm
 int xggm_cast_from_f32_f32(const float* x, void* out, int64_t n, xggm_stream_t stream);
 int xggm_cast_from_f32_bf16(const float* x, void* out, int64_t n, xggm_stream_t stream);
 
+/* ---- replica drift guard -----------------------------------------------------------------
+ * 64-bit fingerprints of byte ranges of device memory.  The reference keeps ONE set of weights under nn.DataParallel
+ * (src/lxrt/entry.py:183-184), so its replicas are identical for free; here every rank owns a copy that a collective
+ * could let drift, and dist.ReplicaGuard compares one word per (buffer, arena group) across the ranks.
+ *
+ * THE CONTRACT (restated in numpy by xggm_amd.fingerprint.fingerprint_host; the tests compare the two bit for bit).
+ * For the little-endian 32-bit words w[0 .. W) of a range, W = bytes / 4, and a 32-bit salt, all arithmetic wrapping:
+ *     k(i) = (i * 0x9E3779B9 + salt)        mod 2^32
+ *     x(i) = (w[i] ^ k(i)) * 0x7FEB352D     mod 2^32;      x(i) ^= x(i) >> 15
+ *     fp   = sum over i of   x(i) * (2 * (i mod 2^31) + 1)      mod 2^64;      fp of no words = 0
+ *  - a pure function of (bytes, salt): a sum mod 2^64 has no order, so grid shape, workgroup count, device and
+ *    address do not enter;
+ *  - w -> x(i) is a bijection of the 32-bit words for every i (xor with a constant, multiplication by an odd number,
+ *    xor-shift), and the factor of x(i) is odd and below 2^32: changing ONE word moves fp by a non-zero product below
+ *    2^64, i.e. with certainty; exchanging two unequal words changes it except by accident, because both k(i) and the
+ *    factor depend on the index;
+ *  - the salt separates buffers whose bits could coincide (params / m / v / shadow).
+ * One multiply in the mix, not the two of a full avalanche hash: 32-bit integer multiplies are quarter rate on gfx950
+ * and the kernel has to stay bound by HBM.
+ *
+ * out[i] (DEVICE, n_spans words, 8-byte aligned) = fp of spans[i] (HOST array, copied); every word is written, empty
+ * ranges give 0.  ptr 4-byte aligned (non-null when bytes > 0), bytes a non-negative multiple of 4.  All ranges of a
+ * call share one grid (64 ranges per grid beyond that) of about max_workgroups workgroups (0: the library chooses; at
+ * least one per non-empty range) plus one small finishing launch; `ws`: caller-owned DEVICE scratch of
+ * xggm_fingerprint_workspace_bytes(n_spans, max_workgroups) bytes, 8-byte aligned, contents irrelevant before and
+ * undefined after.  No host synchronisation, no allocation: legal inside a stream capture. */
+typedef struct xggm_fp_span {
+    const void* ptr;
+    int64_t bytes;
+    uint32_t salt;
+    uint32_t pad;
+} xggm_fp_span;
+size_t xggm_fingerprint_workspace_bytes(int n_spans, int max_workgroups);
+int xggm_fingerprint_spans(const xggm_fp_span* spans, int n_spans, uint64_t* out, void* ws, size_t ws_bytes,
+                           int max_workgroups, xggm_stream_t stream);
+
 /* ---- utilities ---------------------------------------------------------------------------*/
 int xggm_rng_advance(uint64_t* rng, uint64_t by, xggm_stream_t stream);
 int xggm_cast_f32_to_bf16(const float* x, void* out, int64_t n, xggm_stream_t stream);

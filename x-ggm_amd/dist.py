@@ -347,6 +347,29 @@ class GradSync:
                 self.g[s:e].div_(self.world)
 
 
+def _meet(owner, what, timeout, complaint):
+    """host-side rendezvous in front of a collective that user code might enter on ONE rank (``if rank == 0: save(...)``):
+    every rank of ``owner.group`` counts itself in under the same key of the default store (``owner._calls`` numbers the
+    calls) and waits for the others; RuntimeError(``complaint`` % (arrived, world, what, call, timeout)) after ``timeout``
+    seconds (XGGM_COLLECTIVE_TIMEOUT, default 120) instead of a hung group."""
+    import time
+    timeout = float(os.environ.get("XGGM_COLLECTIVE_TIMEOUT", "120")) if timeout is None else float(timeout)
+    try:
+        store = dist.distributed_c10d._get_default_store()
+    except Exception:
+        return  # no store to ask (not the default initialisation): the collective is entered as it always was
+    ranks = dist.get_process_group_ranks(owner.group) if owner.group is not None else list(range(dist.get_world_size()))
+    owner._calls = getattr(owner, "_calls", 0) + 1
+    key = "xggm/%s/%s/%d" % (what, "-".join(str(r) for r in ranks), owner._calls)
+    n = store.add(key, 1)
+    t0 = time.time()
+    while n < owner.world:
+        if time.time() - t0 > timeout:
+            raise RuntimeError(complaint % (n, owner.world, what, owner._calls, timeout))
+        time.sleep(0.005)
+        n = store.add(key, 0)
+
+
 class ShardedUpdate(GradSync):
     """ZeRO-1 on the wire arena: the update of the MATRIX ranges is sharded over the data-parallel ranks.
 
@@ -548,26 +571,11 @@ class ShardedUpdate(GradSync):
     def _rendezvous(self, what, timeout=None):
         """every rank of the group has reached the same collective call, or RuntimeError after ``timeout`` seconds
         (XGGM_COLLECTIVE_TIMEOUT, default 120): host side, through the default store, whatever the backend"""
-        import time
-        timeout = float(os.environ.get("XGGM_COLLECTIVE_TIMEOUT", "120")) if timeout is None else float(timeout)
-        try:
-            store = dist.distributed_c10d._get_default_store()
-        except Exception:
-            return  # no store to ask (not the default initialisation): the collective is entered as it always was
-        ranks = dist.get_process_group_ranks(self.group) if self.group is not None else list(range(dist.get_world_size()))
-        self._calls = getattr(self, "_calls", 0) + 1
-        key = "xggm/%s/%s/%d" % (what, "-".join(str(r) for r in ranks), self._calls)
-        n = store.add(key, 1)
-        t0 = time.time()
-        while n < self.world:
-            if time.time() - t0 > timeout:
-                raise RuntimeError(
-                    "sharded update: only %d of %d ranks reached %s (call %d) within %.0f s.  Under the sharded update the "
-                    "fp32 masters and moments are spread over the ranks, so model.state_dict(), BertAdam.state_dict(), "
-                    "save_training_state(), VQA.save() and sync_weights() are COLLECTIVE calls: make them on every rank "
-                    "(and keep rank 0's result), not inside `if rank == 0:`" % (n, self.world, what, self._calls, timeout))
-            time.sleep(0.005)
-            n = store.add(key, 0)
+        _meet(self, what, timeout,
+              "sharded update: only %d of %d ranks reached %s (call %d) within %.0f s.  Under the sharded update the "
+              "fp32 masters and moments are spread over the ranks, so model.state_dict(), BertAdam.state_dict(), "
+              "save_training_state(), VQA.save() and sync_weights() are COLLECTIVE calls: make them on every rank "
+              "(and keep rank 0's result), not inside `if rank == 0:`")
 
     @torch.no_grad()
     def gather_state(self):
@@ -686,3 +694,151 @@ def broadcast_params(arena, group=None):
     if dist.is_initialized() and dist.get_world_size(group) > 1:
         dist.broadcast(arena.params, src=0, group=group)
         arena.sync_shadow()
+
+
+# ---------------------------------------------------------------------------------------------- replica drift guard
+class ReplicaDrift(RuntimeError):
+    """the data-parallel replicas no longer hold the same bits.  ``buffer`` / ``group``: the first differing entry of the
+    guard's table; ``elements`` = (start, end) of the first differing block of that range in arena elements; ``param``:
+    the first parameter the block touches (``params``: all of them); ``ranks``: the ranks whose block differs from rank
+    0's; ``iteration``: the guard's iteration count when the check ran."""
+
+    def __init__(self, msg, buffer, group, params, elements, ranks, iteration):
+        super().__init__(msg)
+        self.buffer, self.group, self.params, self.elements = buffer, group, list(params), tuple(elements)
+        self.param = self.params[0] if self.params else None
+        self.ranks, self.iteration = list(ranks), iteration
+
+
+class ReplicaGuard:
+    """Run-time check of the assumption data parallelism rests on: after an update every rank holds the same bits.
+    Every rank takes one 64-bit fingerprint (xggm_fingerprint_spans; fingerprint.py) per (buffer, arena group) -- one
+    launch pair over the whole table -- and ONE all-reduce (MAX over ``[t, ~t]``: maximum and, as ``~max(~t)``,
+    minimum of every word on every rank) says whether they agree.  The reference has nothing to guard: one set of
+    weights under nn.DataParallel (src/lxrt/entry.py:183-184).
+
+    ``level`` "weights": what the next forward reads and every rank must agree on whatever the update mode -- the bf16
+    shadow of every group (fp32 mode: ``params``) and the fp32 ``params`` of the vector regions.  "state": also ``m``,
+    ``v`` and the fp32 masters of the matrix regions -- where every rank is supposed to hold them: while a sharded
+    update has left the other ranks' matrix slices stale (``ShardedUpdate.stale``) the three are compared over the vector
+    regions only (``check`` returns the words it compared, so the difference shows).  The Philox state is rank-specific
+    on purpose and never compared.
+
+    On a mismatch every rank sees the same MIN / MAX table and walks the same path: first differing (buffer, group) ->
+    that range cut into at most ``FAN`` power-of-two blocks, fingerprinted and MAX-reduced again, down to blocks of
+    ``BLOCK`` elements -> parameter names from ``arena.info`` -> an all-gather of the block's word names the ranks that
+    differ from rank 0 -> ``ReplicaDrift`` on EVERY rank.
+
+    ``every`` None: ``tick`` does nothing at all.  world size 1: nothing to compare (XGGM_DP_FORCE=1 runs the whole
+    check on the one-rank group, as ``GradSync`` does)."""
+    BLOCK = 256  # elements: arena.ALIGN_MAT, so a block of a matrix region lies inside one matrix
+    FAN = 64     # blocks per refinement step (one grid of the kernel)
+
+    def __init__(self, arena, group=None, every=None, level="weights"):
+        if level not in ("weights", "state"):
+            raise ValueError("ReplicaGuard: level must be 'weights' or 'state'")
+        if every is not None and int(every) < 1:
+            raise ValueError("ReplicaGuard: every must be a positive number of iterations (or None)")
+        self.arena, self.group, self.level = arena, group, level
+        self.every = None if every is None else int(every)
+        on = dist.is_initialized()
+        self.world = dist.get_world_size(group) if on else 1
+        self.rank = dist.get_rank(group) if on else 0
+        self.backend = dist.get_backend(group) if on else None
+        self.force = bool(os.environ.get("XGGM_DP_FORCE")) and on
+        self.iteration = 0  # iterations counted by tick()
+        self.checks = 0     # collective checks made
+        self.wait_streams = []  # side streams whose work the check has to see (the engine's communication stream)
+
+    # ---- what is compared
+    def plan(self, level=None):
+        """[(buffer, group, start, end)] in table order"""
+        a = self.arena
+        level = level or self.level
+        w = "shadow" if getattr(a, "shadow", None) is not None else "params"
+        z = getattr(a, "zero1", None)
+        sharded = z is not None and z.stale
+        lo = {(w, g): G.start for g, G in a.groups.items()}
+        if w != "params":
+            for g, G in a.groups.items():
+                lo[("params", g)] = G.vec_start
+        if level == "state":
+            for buf in ("params", "m", "v"):
+                for g, G in a.groups.items():
+                    lo[(buf, g)] = min(lo.get((buf, g), G.end), G.vec_start if sharded else G.start)
+        return [(buf, g, s, a.groups[g].end) for (buf, g), s in lo.items()]
+
+    def _agree(self, t):
+        """(min, max) of every word of the int64 table ``t`` over the ranks, as CPU tensors: one all-reduce"""
+        n = t.numel()
+        both = torch.cat([t, ~t])
+        if self.backend != "nccl":
+            both = both.cpu()  # gloo: a host transport
+        dist.all_reduce(both, op=dist.ReduceOp.MAX, group=self.group)
+        both = both.cpu()
+        return ~both[n:], both[:n]
+
+    def _table(self, buf, ranges):
+        from .fingerprint import SALT, fingerprint
+        return fingerprint(getattr(self.arena, buf), ranges, SALT[buf])
+
+    def check(self, what="", level=None, rendezvous=False):
+        """COLLECTIVE (every rank of the group calls it).  Returns the number of 32-bit words compared; raises
+        ``ReplicaDrift`` on every rank when the replicas differ.  ``rendezvous``: first make sure, host side and with a
+        timeout, that every rank is here (``_meet``) -- for call sites user code might reach on one rank only
+        (``save_training_state`` under ``if rank == 0:``); the per-iteration ``tick`` does not pay for it."""
+        from .fingerprint import SALT, fingerprint_table
+        if self.world == 1 and not self.force:
+            return 0
+        if rendezvous and self.world > 1:
+            _meet(self, "replica_check", None,
+                  "replica drift guard: only %d of %d ranks reached %s (call %d) within %.0f s.  With check_every set, "
+                  "save_training_state() compares the replicas before it writes and is a COLLECTIVE call: make it on every "
+                  "rank (pass path=None on the ranks that should not write), not inside `if rank == 0:`")
+        a = self.arena
+        z = getattr(a, "zero1", None)
+        if z is not None:
+            z.wait_pending()  # all-gathers of the bf16 weights still running beside a forward
+        if a.params.is_cuda:
+            for s in self.wait_streams:
+                torch.cuda.current_stream().wait_stream(s)
+        plan = self.plan(level)
+        t = fingerprint_table([(getattr(a, buf), s, e, SALT[buf]) for buf, g, s, e in plan])
+        self.checks += 1
+        mn, mx = self._agree(t)
+        words = sum((e - s) * getattr(a, buf).element_size() // 4 for buf, g, s, e in plan)
+        diff = torch.nonzero(mn != mx).flatten()
+        if diff.numel() == 0:
+            return words
+        buf, g, lo, hi = plan[int(diff[0])]
+        word = t[int(diff[0]):int(diff[0]) + 1]
+        while hi - lo > self.BLOCK:
+            step = self.BLOCK
+            while step * self.FAN < hi - lo:
+                step *= 2
+            blocks = [(s, min(s + step, hi)) for s in range(lo, hi, step)]
+            tb = self._table(buf, blocks)
+            bmn, bmx = self._agree(tb)
+            d = torch.nonzero(bmn != bmx).flatten()
+            if d.numel() == 0:  # (a collision inside every block: astronomically unlikely; report the range as it is)
+                break
+            lo, hi = blocks[int(d[0])]
+            word = tb[int(d[0]):int(d[0]) + 1]
+        names = [n for n, (o, k, *_) in sorted(getattr(a, "info", {}).items(), key=lambda kv: kv[1][0]) if o < hi and o + k > lo]
+        word = word.contiguous() if self.backend == "nccl" else word.cpu()
+        every = [torch.empty_like(word) for _ in range(self.world)]
+        dist.all_gather(every, word, group=self.group)
+        ranks = [r for r in range(self.world) if int(every[r]) != int(every[0])]
+        msg = ("replicas differ%s at iteration %d: buffer %s, group %s, parameter %s, elements [%d, %d): rank(s) %s disagree "
+               "with rank 0" % (" (%s)" % what if what else "", self.iteration, buf, g, ", ".join(names) or "(none)", lo, hi,
+                                ", ".join(str(r) for r in ranks)))
+        raise ReplicaDrift(msg, buf, g, names, (lo, hi), ranks, self.iteration)
+
+    def tick(self):
+        """count one training iteration; every ``every``-th runs ``check``.  ``every`` None: nothing happens."""
+        if self.every is None:
+            return None
+        self.iteration += 1
+        if self.iteration % self.every:
+            return None
+        return self.check()

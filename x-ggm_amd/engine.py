@@ -361,6 +361,13 @@ class CapturedTrainer:
         else:
             b = self.run_pass(branch)
             a = self.run_pass("plain")
+        guard = getattr(self.model, "_replica_guard", None)
+        if guard is not None:
+            # eager work between two replays, never part of a graph (the check is a collective); what the staged
+            # exchange left on the communication stream is waited for first
+            if self._comm is not None and all(self._comm is not s for s in guard.wait_streams):
+                guard.wait_streams.append(self._comm)
+            guard.tick()
         return a, b
 
 

@@ -1199,6 +1199,52 @@ def sqnorm_multi(buf, spans, out, norm=None, overwrite=True, square=True, mul=1.
              ptr(norm) if last else None, ptr(ws), int(overwrite and ci == 0), int(square), float(mul) if last else 1.0, stream())
 
 
+class FpSpan(_ct.Structure):
+    """mirror of ``xggm_fp_span`` (include/xggm.h)"""
+    _fields_ = [("ptr", _ct.c_void_p), ("bytes", _ct.c_int64), ("salt", _ct.c_uint32), ("pad", _ct.c_uint32)]
+
+
+_FP_WS = {}
+FP_MAX_WORKGROUPS = 4096  # largest ``max_workgroups`` fingerprint_spans takes: the cached workspace is sized for it, once
+
+
+def fingerprint_workspace(device, max_workgroups=FP_MAX_WORKGROUPS):
+    """a workspace of one's own for ``fingerprint_spans(ws=...)`` (int64 tensor)"""
+    nb = _lib.lib.xggm_fingerprint_workspace_bytes(1, int(max_workgroups))
+    return torch.empty((nb + 7) // 8, device=device, dtype=torch.int64)
+
+
+def fingerprint_spans(spans, device, out=None, max_workgroups=0, ws=None):
+    """64-bit fingerprints (contract: xggm_fingerprint_spans in xggm.h) of the byte ranges ``spans`` = [(device
+    pointer, bytes, salt)] on ``device`` -> int64 tensor [len(spans)] (the uint64 words' bit patterns), every word
+    written.  One grid for all ranges + one finishing launch.  ``ws`` None: the workspace cached per device -- made ONCE,
+    at the first eager call (inside a stream capture an allocation would belong to that graph's pool), for the largest
+    ``max_workgroups`` there is (FP_MAX_WORKGROUPS), and never replaced, so a captured call keeps a valid pointer.  It
+    serves calls that are ordered against each other (one stream, or a graph and the stream it is replayed on); calls
+    that may run side by side on different streams pass their own ``ws`` (``fingerprint_workspace``)."""
+    device = torch.device(device)
+    n = len(spans)
+    if not 0 <= int(max_workgroups) <= FP_MAX_WORKGROUPS:
+        raise ValueError("fingerprint_spans: max_workgroups must lie in [0, %d]" % FP_MAX_WORKGROUPS)
+    if out is None:
+        out = torch.empty(n, device=device, dtype=torch.int64)
+    assert out.is_cuda and out.dtype == torch.int64 and out.is_contiguous() and out.numel() >= n
+    if n == 0:
+        return out
+    if ws is None:
+        ws = _FP_WS.get(device)
+        if ws is None:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("fingerprint_spans: call it once eagerly on %s before capturing it (workspace)" % device)
+            ws = _FP_WS[device] = fingerprint_workspace(device)
+    assert ws.is_cuda and ws.dtype == torch.int64 and ws.is_contiguous()
+    arr = (FpSpan * n)()
+    for i, (p, b, salt) in enumerate(spans):
+        arr[i].ptr, arr[i].bytes, arr[i].salt = (int(p) or None), int(b), int(salt) & 0xFFFFFFFF
+    call("xggm_fingerprint_spans", _ct.addressof(arr), n, ptr(out), ptr(ws), ws.numel() * 8, int(max_workgroups), stream())
+    return out
+
+
 class _PassTail(_ct.Structure):
     _fields_ = [("steps", _ct.c_void_p), ("lr_scale", _ct.c_void_p), ("index", _ct.c_void_p), ("t_total", _ct.c_void_p),
                 ("warmup", _ct.c_void_p), ("n", _ct.c_int), ("rng", _ct.c_void_p), ("rng_by", _ct.c_uint64)]

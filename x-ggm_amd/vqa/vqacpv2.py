@@ -61,7 +61,8 @@ def remove_diagonal(adj_true):
     return ops.zero_diag(adj_true.float().contiguous())
 
 
-def enable_data_parallel(model, group=None, wire_dtype=None, overlap=None, zero1=False):
+def enable_data_parallel(model, group=None, wire_dtype=None, overlap=None, zero1=False, check_every=None,
+                         check_level="weights"):
     """one process per GPU: average the flat gradient arena over ``group`` between backward and
     the fused clip + BertAdam of every pass (xggm_amd.dist.GradSync); replicas start equal.
     ``overlap`` (default on; XGGM_DP_OVERLAP=0 turns it off): cut the backward between the single-modality
@@ -71,7 +72,11 @@ def enable_data_parallel(model, group=None, wire_dtype=None, overlap=None, zero1
     of the bf16 weights the GEMMs read).
     Every rank draws its OWN dropout masks and denoising noise (the Philox seed is folded with the rank): the
     averaged gradient is then that of one batch of world x B samples with independent noise; only the host-side
-    branch decision is shared (``pick_branch``)."""
+    branch decision is shared (``pick_branch``).
+    ``check_every`` (default None: off, nothing is launched or exchanged): every so many iterations the ranks compare
+    fingerprints of what ``check_level`` names ("weights" or "state", dist.ReplicaGuard) and ALL raise
+    ``dist.ReplicaDrift`` when their replicas have come apart; ``save_training_state`` then checks before it writes and
+    is a collective call under either update mode: make it on EVERY rank (``path=None`` where no file is wanted)."""
     import os
     import torch.distributed as dist
     from ..dist import GradSync, broadcast_params
@@ -105,7 +110,17 @@ def enable_data_parallel(model, group=None, wire_dtype=None, overlap=None, zero1
     if overlap is None:
         overlap = os.environ.get("XGGM_DP_OVERLAP", "1") != "0"
     rt.cut_enabled = bool(overlap)
+    if check_every is not None:
+        from ..dist import ReplicaGuard
+        object.__setattr__(model, "_replica_guard", ReplicaGuard(rt.arena, group, every=check_every, level=check_level))
     return model
+
+
+def _tick_guard(model):
+    """end of a training iteration: the replica drift guard (when ``enable_data_parallel`` made one) counts it"""
+    guard = getattr(model, "_replica_guard", None)
+    if guard is not None:
+        guard.tick()
 
 
 def _sync_grads(model):
@@ -234,6 +249,7 @@ def train_iteration(model, optim, bce_loss, batch, delta=5, sigma=1.0, order="vq
         out["loss_plain"], out["logit"] = plain_pass(model, optim, bce_loss, *args, clip=clip, advance=True)
     out.update(ex)
     out["branch"] = branch
+    _tick_guard(model)
     return out
 
 
@@ -289,6 +305,13 @@ def save_training_state(path, model, optim, **extra):
     # under the sharded update (ZeRO-1) this is a collective: every rank calls it (they all hold the gathered state
     # afterwards; let one of them pass a real ``path`` and the others ``None`` to write a single file)
     rt.arena.gather_sharded_state()
+    guard = getattr(model, "_replica_guard", None)
+    if guard is not None:
+        # everything is comparable now (masters and moments are whole): a drifted run leaves no checkpoint behind.
+        # With a guard this is a COLLECTIVE under the replicated update too: EVERY rank calls save_training_state (path
+        # None where nothing is to be written); a rank that comes alone gets a RuntimeError after
+        # XGGM_COLLECTIVE_TIMEOUT seconds (dist._meet), not a hung group
+        guard.check("checkpoint", level="state", rendezvous=True)
     ck = {"model": model.state_dict(), "optimizer": optim.state_dict(), "rng": rt.rng.cpu(),
           "python_random": random.getstate(), "extra": extra}
     if path is not None:
