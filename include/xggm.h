@@ -724,6 +724,39 @@ size_t xggm_fingerprint_workspace_bytes(int n_spans, int max_workgroups);
 int xggm_fingerprint_spans(const xggm_fp_span* spans, int n_spans, uint64_t* out, void* ws, size_t ws_bytes,
                            int max_workgroups, xggm_stream_t stream);
 
+/* ---- answer log ---------------------------------------------------------------------------
+ * The reference turns logits into answers on the host: `logit.max(1)[1].cpu()` in every training iteration
+ * (src/vqa/vqacpv2.py:180-181, scored per epoch by the evaluator, src/vqa/vqacpv2_data.py:134-142) and per batch of
+ * the validation sweep (src/vqa/vqacpv2.py:333-334; GQA twin src/gqa/gqa_ood.py:379-403).  Here one launch APPENDS the
+ * chosen answers of a batch to buffers that stay on the device, and the host reads the log once per sweep / epoch.
+ *
+ * For row b < n, n = rows ? clamp(*rows, 0, B) : B (`rows`: DEVICE int, the kept rows of a padded short batch; rows
+ * >= n are neither read nor logged), and c = *cursor on entry:
+ *     label        = what torch.max(logits, 1) returns on the CPU: the first maximal index; a row holding NaN gives
+ *                    the index of its FIRST NaN; +-inf are ordinary values; -0 == +0
+ *     labels[c+b]  = label
+ *     scores[c+b]  = target[b * target_stride + label]                       (with a target)
+ *     *score_sum   = (..((*score_sum + scores[c]) + scores[c+1]) + ..)       (with a target and score_sum; fp64, row
+ *                    order, one thread: the same bits eagerly, replayed from a graph or beside other work)
+ *     *cursor      = c + n
+ * If c + n > capacity NOTHING is stored, *cursor stays and *flags = (*flags | 1) + 2: bit 0 says an append did not
+ * fit, the bits above it count the refused appends.  No store leaves [0, capacity) under any input.
+ * logits: fp32 [B, A] with row_stride >= A floats (4-byte aligned rows are enough; 16-byte loads are used where the
+ * row allows them); target: fp32 [B, A] with target_stride >= A, or NULL.  A target needs `scores`.  B <= 262144.
+ * `ws`: XGGM_SUM_WS_FLOATS floats as for the losses (ws[0] == 0 at launch, left 0).  One launch of min(B, 128)
+ * workgroups (more only past 8192 rows), no allocation, no host synchronisation: legal inside a stream capture.
+ * Launches that share a log must be ordered against each other (one stream, or graphs replayed on it). */
+typedef struct xggm_answer_log {
+    int64_t* labels;   /* [capacity] chosen answer indices */
+    float* scores;     /* [capacity] soft score per sample, or NULL */
+    int64_t* cursor;   /* samples logged so far */
+    double* score_sum; /* running sum of the scores, or NULL */
+    int* flags;        /* bit 0: an append did not fit; bits 1..: how many did not */
+    int64_t capacity;  /* size of labels / scores */
+} xggm_answer_log;
+int xggm_answer_pick_f32(const float* logits, int64_t row_stride, const float* target, int64_t target_stride, int B, int A,
+                         const int* rows, xggm_answer_log* log, float* ws, xggm_stream_t stream);
+
 /* ---- utilities ---------------------------------------------------------------------------*/
 int xggm_rng_advance(uint64_t* rng, uint64_t by, xggm_stream_t stream);
 int xggm_cast_f32_to_bf16(const float* x, void* out, int64_t n, xggm_stream_t stream);

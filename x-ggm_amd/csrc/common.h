@@ -102,6 +102,19 @@ __device__ __forceinline__ float wave_max(float v) {
     return fmaxf(fmaxf(row_lane(v, 0), row_lane(v, 16)), fmaxf(row_lane(v, 32), row_lane(v, 48)));
 }
 
+// 64-bit values through the same moves (two 32-bit halves each): the integer reductions of fingerprint.hip and answers.hip
+template <int CTRL>
+__device__ __forceinline__ uint64_t dpp_move64(uint64_t v) {
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_mov_dpp((int)(uint32_t)v, CTRL, 0xF, 0xF, true);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_mov_dpp((int)(uint32_t)(v >> 32), CTRL, 0xF, 0xF, true);
+    return ((uint64_t)hi << 32) | lo;
+}
+__device__ __forceinline__ uint64_t lane64(uint64_t v, int l) {
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, l);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), l);
+    return ((uint64_t)hi << 32) | lo;
+}
+
 // ---------------------------------------------------------------- math
 // erf by Abramowitz & Stegun 7.1.26 (|abs error| <= 1.5e-7), branch-free: one rcp, one exp and a
 // degree-5 Horner chain instead of libm's range-split erff.  Inside GELU the error is 7.5e-8*|x|,

@@ -31,17 +31,6 @@ __device__ __forceinline__ uint64_t fp_word(uint32_t w, uint32_t ks, uint32_t od
     return (uint64_t)x * (uint64_t)odd;
 }
 
-template <int CTRL>
-__device__ __forceinline__ uint64_t dpp_move64(uint64_t v) {
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_mov_dpp((int)(uint32_t)v, CTRL, 0xF, 0xF, true);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_mov_dpp((int)(uint32_t)(v >> 32), CTRL, 0xF, 0xF, true);
-    return ((uint64_t)hi << 32) | lo;
-}
-__device__ __forceinline__ uint64_t lane64(uint64_t v, int l) {
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, l);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), l);
-    return ((uint64_t)hi << 32) | lo;
-}
 // wrapping sum over the wave, every lane active (the pattern of wave_sum in common.h)
 __device__ __forceinline__ uint64_t wave_sum_u64(uint64_t v) {
     v += dpp_move64<0xB1>(v);

@@ -44,15 +44,107 @@ class _quiet_gc:
             gc.enable()
 
 
+class AnswerLog:
+    """Device-resident log of chosen answers (``ops.answer_pick`` / xggm_answer_pick_f32): every call appends the
+    arg-max of its batch -- with a target also the soft scores and their running fp64 sum -- and the host reads the
+    log ONCE per sweep or epoch instead of once per batch (the reference: ``logit.max(1)[1].cpu()``,
+    src/vqa/vqacpv2.py:180-181 and :333-334).
+
+        log = AnswerLog(len(dset), dev, with_scores=False)
+        pred = CapturedPredictor(model, 512, log=log)
+        log.reset()
+        for ques_id, feats, boxes, sent in loader: pred.push(feats, boxes, sent)   # no host synchronisation
+        labels, _, _, n = log.read()                                              # the one read-back
+
+    Everything lives in one int64 device buffer -- [cursor, score sum (fp64), flags, labels, scores] -- so that
+    ``read`` is one transfer into one pinned host buffer.  An append that does not fit stores nothing and raises the
+    overflow flag; ``read`` then raises.  Calls that share a log must be ordered against each other (one stream)."""
+
+    def __init__(self, capacity, device, with_scores=True):
+        capacity = int(capacity)
+        if capacity <= 0:
+            raise ValueError("AnswerLog: capacity must be positive")
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError("xggm_amd: the answer log must live on the GPU (no CPU fallback)")
+        self.capacity, self.with_scores = capacity, bool(with_scores)
+        words = 3 + capacity + ((capacity + 1) // 2 if with_scores else 0)
+        self.buf = torch.zeros(words, dtype=torch.int64, device=device)
+        self.host = torch.zeros(words, dtype=torch.int64).pin_memory()
+        self.cursor = self.buf[0:1]
+        self.score_sum = self.buf[1:2].view(torch.float64) if with_scores else None
+        self.flags = self.buf[2:3].view(torch.int32)[0:1]
+        self.labels = self.buf[3:3 + capacity]
+        self.scores = self.buf[3 + capacity:].view(torch.float32)[:capacity] if with_scores else None
+        # the kept rows of a padded short batch: a device word the captured launch reads, fed from ONE pinned slot
+        self.rows = torch.zeros(1, dtype=torch.int32, device=device)
+        self._rows_host = torch.zeros(1, dtype=torch.int32).pin_memory()
+        self._rows_sent = None   # value the device word holds (after the copies queued so far)
+        self._rows_copied = None  # event behind the last copy out of the pinned slot
+        self.count = 0  # host mirror of the cursor: samples handed to the log since reset()
+
+    def set_rows(self, n):
+        """queue ``rows = n`` in stream order (nothing is queued while the value does not change: full batches).  The
+        pinned slot is rewritten only once the previous copy out of it has run -- it was queued batches ago; should it
+        still be pending, the new value goes through a fresh slot instead of waiting"""
+        n = int(n)
+        if n == self._rows_sent:
+            return
+        if self._rows_copied is not None and not self._rows_copied.query():
+            self._rows_host = torch.zeros(1, dtype=torch.int32).pin_memory()
+        self._rows_host[0] = n
+        self.rows.copy_(self._rows_host, non_blocking=True)
+        self._rows_copied = torch.cuda.Event()
+        self._rows_copied.record()
+        self._rows_sent = n
+
+    def note(self, n):
+        """host bookkeeping of an append of ``n`` samples that has been queued (a graph replay runs no Python): an
+        append past the capacity is refused here already, before anything is queued"""
+        if self.count + n > self.capacity:
+            raise RuntimeError("answer log overflow: capacity %d, %d samples logged, %d more do not fit"
+                               % (self.capacity, self.count, n))
+        self.count += n
+
+    def reset(self):
+        """cursor, score sum and flags back to zero, in stream order (no synchronisation)"""
+        self.buf[:3].zero_()
+        self.count = 0
+
+    def read(self):
+        """-> (labels [n] int64, scores [n] fp32 or None, score_sum float, n) as CPU tensors / numbers: ONE
+        device-to-host transfer and one wait for it.  RuntimeError when an append was refused."""
+        from .answers import decode_packed
+        self.host.copy_(self.buf, non_blocking=True)
+        torch.cuda.current_stream(self.buf.device).synchronize()
+        return decode_packed(self.host, self.capacity, self.with_scores)
+
+    def score(self):
+        """mean soft score of the logged samples (the reference's per-epoch train score, src/vqa/vqacpv2.py:285, as a
+        fraction; the evaluator's sum, src/vqa/vqacpv2_data.py:134-142, over the count)"""
+        if not self.with_scores:
+            raise RuntimeError("AnswerLog.score: the log was built without scores")
+        _, _, total, n = self.read()
+        return total / n if n else 0.0
+
+
 class CapturedTrainer:
     def __init__(self, model, optim, batch, sigma=1.0, order="vqa", clip=5.0, use_graph=True, warmup_iters=2,
-                 packed_spec=None):
+                 packed_spec=None, answer_log=None):
         """``batch``: dict of DEVICE tensors feats, boxes, input_ids, input_mask, segment_ids,
         target, adj_true; they become the static input buffers (``load_batch`` copies into them).
         ``packed_spec`` = ``DataLoaderX.spec`` of a loader with ``handover="inline"``: the static buffers are then
         views of ONE flat device buffer laid out like the loader's pinned slots, and ``load_packed`` hands a batch over
-        with a single host-to-device copy on the compute stream."""
+        with a single host-to-device copy on the compute stream.
+        ``answer_log`` = an ``AnswerLog`` with scores: the PLAIN pass (whose answers the reference logs,
+        src/vqa/vqacpv2.py:180-181) then ends with one ``ops.answer_pick`` on its logits and the static target, inside
+        the captured graph; ``train_score()`` / ``answers()`` read it back.  It observes only: nothing of the step
+        depends on it.  Under data parallelism each rank logs its own samples -- the caller averages the ranks'
+        ``train_score()`` (weighted by their counts); no collective is added.  None (default): no launch is added."""
         self.model, self.optim = model, optim
+        self.answer_log = answer_log
+        if answer_log is not None and not answer_log.with_scores:
+            raise ValueError("CapturedTrainer: answer_log needs scores (AnswerLog(with_scores=True))")
         self.rt = runtime_of(model)
         self.static_flat = None
         if packed_spec is not None:
@@ -84,6 +176,8 @@ class CapturedTrainer:
         model.train()
         if use_graph:
             self._capture(warmup_iters)
+        if answer_log is not None:
+            answer_log.reset()  # what the warm-up passes logged
 
     # ------------------------------------------------------------------ the two halves of a pass
     def _fwd_bwd(self, kind, between=None):
@@ -92,6 +186,10 @@ class CapturedTrainer:
         if kind == "plain":
             loss, logit = forward_backward_plain(self.model, self.bce, s["feats"], s["boxes"], sent, s["target"],
                                                  between=between)
+            if self.answer_log is not None:
+                # reads the logits and the target only: behind the backward it costs one short launch at the tail of the
+                # (last backward) graph and nothing waits for it
+                ops.answer_pick(logit, self.answer_log, target=s["target"])
         else:
             loss, logit, _ = forward_backward_ggm(self.model, self.bce, s["feats"], s["boxes"], sent, s["target"],
                                                   s["adj_true"], kind, self.sigma, self.kl_weight, between=between)
@@ -287,7 +385,24 @@ class CapturedTrainer:
         self.static_flat.copy_(it.flat, non_blocking=True)
         it.mark_copied()
 
+    def train_score(self):
+        """mean soft score of the plain pass's answers since the log's last ``reset()`` (the reference's per-epoch train
+        score, src/vqa/vqacpv2.py:285, as a fraction): one read-back"""
+        return self._log().score()
+
+    def answers(self):
+        """-> (labels [n] int64, scores [n] fp32) of the plain passes since the log's last ``reset()``, CPU tensors"""
+        labels, scores, _, _ = self._log().read()
+        return labels, scores
+
+    def _log(self):
+        if self.answer_log is None:
+            raise RuntimeError("CapturedTrainer was built without answer_log")
+        return self.answer_log
+
     def run_pass(self, kind):
+        if kind == "plain" and self.answer_log is not None:
+            self.answer_log.note(self.static["target"].shape[0])
         if not self.use_graph:
             return self._eager_pass(kind)
         gs = self.graphs[kind]
@@ -376,10 +491,14 @@ class CapturedPredictor:
     src/gqa/gqa_ood.py:379-403): eval mode, no autograd, encoder -> ``logit_fc`` -> arg-max; the generator is
     not on this path.  The forward of one full batch is captured once and replayed; a short last batch is
     padded (its padding rows are computed and dropped: samples are independent, so the kept rows do not change).
-    The logits are fp32 and the arg-max is torch's (first maximal index), as in ``logit.max(1)``."""
+    The logits are fp32 and the arg-max is torch's (first maximal index), as in ``logit.max(1)``.
+    ``log`` = an ``AnswerLog``: the forward then ends in ``ops.answer_pick`` instead (same indices), which appends the
+    kept rows' answers to the log on the device; ``push`` queues a batch without handing anything back, and the sweep
+    reads the log once at its end (``vqa.vqacpv2.predict`` does so when the predictor carries a log)."""
 
-    def __init__(self, model, batch_size, n_objects=36, feat_dim=None, max_seq_length=None, use_graph=True):
+    def __init__(self, model, batch_size, n_objects=36, feat_dim=None, max_seq_length=None, use_graph=True, log=None):
         self.model = model
+        self.log = log
         dev = next(model.parameters()).device
         enc = model.lxrt_encoder
         T = max_seq_length or enc.max_seq_length
@@ -394,6 +513,8 @@ class CapturedPredictor:
         if use_graph:
             was_training = model.training
             model.eval()
+            if log is not None:
+                log.set_rows(batch_size)
             side = torch.cuda.Stream()
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):
@@ -404,18 +525,33 @@ class CapturedPredictor:
             with _quiet_gc(), torch.cuda.graph(self.graph):
                 self.logit, self.label = self._forward()
             model.train(was_training)
+            if log is not None:
+                log.reset()  # what the warm-up forward logged
 
     def _forward(self):
         s = self.static
         with torch.no_grad():
             _, _, x = self.model(s["feats"], s["boxes"], (s["ids"][0], s["ids"][1], s["ids"][2]))
             logit = self.model.logit_fc(x)
+            if self.log is not None:
+                ops.answer_pick(logit, self.log, rows=self.log.rows)
+                return logit, None
             return logit, logit.max(1)[1]
 
     def __call__(self, feats, boxes, sent):
         """-> (labels [b] int64, logits [b, A] fp32) for b <= batch_size samples; ``sent``: list of strings or the
         (input_ids, input_mask, segment_ids) tuple.  The returned tensors are views of static buffers: consume
-        them (``.cpu()``) before the next call."""
+        them (``.cpu()``) before the next call.  With a log the labels are views of the log's newest ``b`` entries."""
+        b = self.push(feats, boxes, sent)
+        if self.log is not None:
+            return self.log.labels[self.log.count - b:self.log.count], self.logit[:b]
+        return self.label[:b], self.logit[:b]
+
+    def push(self, feats, boxes, sent):
+        """queue the forward of one batch (b <= batch_size samples) and return b: what ``__call__`` does, without tensors
+        to consume.  With a log the answers of the b kept rows are appended to it on the device -- the row count of a
+        short batch travels to the device in stream order ahead of the replay, as the ids do, so the padded rows never
+        enter the log -- and the host is not synchronised."""
         b = feats.shape[0]
         if b > self.B:
             raise ValueError("batch of %d exceeds the captured batch size %d" % (b, self.B))
@@ -429,6 +565,9 @@ class CapturedPredictor:
             batcher.record_copy()  # the pinned buffer is not rewritten before this copy has read it
         s["feats"][:b].copy_(feats, non_blocking=True)
         s["boxes"][:b].copy_(boxes, non_blocking=True)
+        if self.log is not None:
+            self.log.note(b)
+            self.log.set_rows(b)
         if self.graph is not None:
             self.graph.replay()
         else:
@@ -436,4 +575,4 @@ class CapturedPredictor:
             self.model.eval()
             self.logit, self.label = self._forward()
             self.model.train(was_training)
-        return self.label[:b], self.logit[:b]
+        return b

@@ -1245,6 +1245,52 @@ def fingerprint_spans(spans, device, out=None, max_workgroups=0, ws=None):
     return out
 
 
+class AnswerLogDesc(_ct.Structure):
+    """mirror of ``xggm_answer_log`` (include/xggm.h)"""
+    _fields_ = [("labels", _ct.c_void_p), ("scores", _ct.c_void_p), ("cursor", _ct.c_void_p), ("score_sum", _ct.c_void_p),
+                ("flags", _ct.c_void_p), ("capacity", _ct.c_int64)]
+
+
+def answer_pick(logits, log, target=None, rows=None):
+    """append the arg-max of every row of ``logits`` (fp32 [B, A], unit inner stride) to ``log`` -- anything with the
+    device tensors ``labels`` int64 [capacity], ``scores`` fp32 [capacity] or None, ``cursor`` int64 [1], ``score_sum``
+    fp64 [1] or None, ``flags`` int32 [1] (``engine.AnswerLog``) -- and, with ``target`` (fp32 [B, A]), the rows' soft
+    scores and their running sum.  ``rows``: int32 [1] DEVICE tensor, the kept rows of a padded batch (None: all).
+    Contract: xggm_answer_pick_f32 in xggm.h.  One launch, nothing returned: the log is read with ``log.read()``."""
+    _chk(logits, F32, "logits")
+    B, A, ld = _rows(logits)
+    if B <= 0 or A <= 0:
+        raise ValueError("answer_pick: empty logits %s" % (tuple(logits.shape),))
+    t_ld = 0
+    if target is not None:
+        _chk(target, F32, "target")
+        if tuple(target.shape) != (B, A) or target.stride(1) != 1:
+            raise ValueError("answer_pick: target %s does not match the logits %s" % (tuple(target.shape), (B, A)))
+        if log.scores is None:
+            raise ValueError("answer_pick: a target needs a log with scores (AnswerLog(with_scores=True))")
+        t_ld = target.stride(0)
+    d = AnswerLogDesc()
+    cap = int(log.capacity)
+    _c(log.labels, torch.int64, "log.labels"), _c(log.cursor, torch.int64, "log.cursor"), _c(log.flags, torch.int32, "log.flags")
+    if log.labels.numel() < cap or log.cursor.numel() < 1 or log.flags.numel() < 1:
+        raise ValueError("answer_pick: log.labels holds %d entries, the capacity is %d" % (log.labels.numel(), cap))
+    if log.scores is not None:
+        _c(log.scores, F32, "log.scores")
+        assert log.scores.numel() >= cap
+    if log.score_sum is not None:
+        _c(log.score_sum, torch.float64, "log.score_sum")
+    if rows is not None:
+        _c(rows, torch.int32, "rows")
+        assert rows.numel() >= 1
+    for t in (target, rows, log.labels, log.scores, log.cursor, log.score_sum, log.flags):
+        if t is not None and t.device != logits.device:
+            raise RuntimeError("answer_pick: the log, the target and the logits must live on one device")
+    d.labels, d.scores, d.cursor = ptr(log.labels), ptr(log.scores), ptr(log.cursor)
+    d.score_sum, d.flags, d.capacity = ptr(log.score_sum), ptr(log.flags), cap
+    call("xggm_answer_pick_f32", ptr(logits), ld, ptr(target), t_ld, B, A, ptr(rows), _ct.addressof(d),
+         ptr(sum_ws(logits.device)), stream())
+
+
 class _PassTail(_ct.Structure):
     _fields_ = [("steps", _ct.c_void_p), ("lr_scale", _ct.c_void_p), ("index", _ct.c_void_p), ("t_total", _ct.c_void_p),
                 ("warmup", _ct.c_void_p), ("n", _ct.c_int), ("rng", _ct.c_void_p), ("rng_by", _ct.c_uint64)]

@@ -267,24 +267,38 @@ def predict(model, eval_tuple, dump=None, predictor=None):
     """``VQA.predict`` (src/vqa/vqacpv2.py:315-339; GQA twin src/gqa/gqa_ood.py:379-403): eval mode, encoder ->
     ``logit_fc`` -> arg-max -> ``{question_id: answer}``.  ``eval_tuple`` = (dset, loader, evaluator) as in the
     reference; only the first four fields of a loader item are looked at (never the ground truth).  ``predictor``:
-    an ``engine.CapturedPredictor`` to replay one captured forward per batch instead of launching eagerly."""
+    an ``engine.CapturedPredictor`` to replay one captured forward per batch instead of launching eagerly.  When the
+    predictor carries an ``engine.AnswerLog`` the answers stay on the device for the whole sweep: every batch is only
+    queued (``push``), the question ids are kept on the host in call order, and the log is read ONCE behind the loop --
+    no host synchronisation between the first and the last batch (the per-batch ``.cpu()`` of :333 is gone)."""
     dset, loader, evaluator = eval_tuple
     dev = next(model.parameters()).device
     was_training = model.training
     model.eval()
     quesid2ans = {}
     try:
-        for datum_tuple in loader:
-            ques_id, feats, boxes, sent = datum_tuple[:4]
-            feats, boxes = feats.to(dev, non_blocking=True), boxes.to(dev, non_blocking=True)
-            if predictor is not None:
-                label, _ = predictor(feats, boxes, sent)
-            else:
-                with torch.no_grad():
-                    _, _, x = model(feats, boxes, sent)
-                    label = model.logit_fc(x).max(1)[1]
-            for qid, l in zip(ques_id, label.cpu().numpy()):
-                quesid2ans[qid.item() if hasattr(qid, "item") else qid] = dset.label2ans[l]
+        if predictor is not None and getattr(predictor, "log", None) is not None:
+            from ..answers import to_quesid2ans
+            log, ques_ids = predictor.log, []
+            log.reset()
+            for datum_tuple in loader:
+                ques_id, feats, boxes, sent = datum_tuple[:4]
+                predictor.push(feats.to(dev, non_blocking=True), boxes.to(dev, non_blocking=True), sent)
+                ques_ids.extend(ques_id.tolist() if torch.is_tensor(ques_id) else ques_id)
+            labels = log.read()[0]
+            quesid2ans = to_quesid2ans(ques_ids, labels, dset.label2ans)
+        else:
+            for datum_tuple in loader:
+                ques_id, feats, boxes, sent = datum_tuple[:4]
+                feats, boxes = feats.to(dev, non_blocking=True), boxes.to(dev, non_blocking=True)
+                if predictor is not None:
+                    label, _ = predictor(feats, boxes, sent)
+                else:
+                    with torch.no_grad():
+                        _, _, x = model(feats, boxes, sent)
+                        label = model.logit_fc(x).max(1)[1]
+                for qid, l in zip(ques_id, label.cpu().numpy()):
+                    quesid2ans[qid.item() if hasattr(qid, "item") else qid] = dset.label2ans[l]
     finally:
         model.train(was_training)
     if dump is not None:
