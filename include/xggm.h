@@ -757,6 +757,47 @@ typedef struct xggm_answer_log {
 int xggm_answer_pick_f32(const float* logits, int64_t row_stride, const float* target, int64_t target_stride, int B, int A,
                          const int* rows, xggm_answer_log* log, float* ws, xggm_stream_t stream);
 
+/* ---- training log -------------------------------------------------------------------------
+ * The reference loop reads its scalars from the GPU in every iteration: the running loss, `total_loss += loss.detach()
+ * / logit.size(0)` (src/vqa/vqacpv2.py:179), and the tensorboard scalars Train/batch_loss, Train/average_loss and lr
+ * (src/vqa/vqacpv2.py:256-270; GQA twin src/gqa/gqa_ood.py:165-292).  Here one short launch at the end of an optimiser
+ * pass APPENDS one record of up to XGGM_TRAINLOG_COLS device scalars to a ring that stays on the device, and the host
+ * reads the ring once per N iterations or per epoch.  Nothing is computed: the values are the ones earlier launches of
+ * the stream left in device memory.
+ *
+ * src: HOST array of n <= COLS DEVICE pointers to single floats (copied into the kernel arguments, like the ranges of
+ * xggm_zero_ranges_f32); a NULL entry = the column is absent.  mul: HOST array of n floats, or NULL = all ones.
+ * step: DEVICE int64 (an optimiser step counter) or NULL.  With r = *cursor on entry and row = r % capacity:
+ *     v_i                   = *src[i] * mul[i]                 (present columns; ONE fp32 multiply)
+ *     values[row*COLS + i]  = v_i; absent columns and columns >= n hold 0.0f and their mask bit is clear
+ *     steps[row]            = *step                            (when both `steps` and `step` are given)
+ *     kinds[row]            = kind | mask << 8                 (bit i of mask: column i is present)
+ *     sums[kind][i]         = sums[kind][i] + (double)v_i      (present columns only; non-finite values included: the
+ *                             sum then turns NaN or inf, as the reference's total_loss would)
+ *     counts[kind]         += 1
+ *     *first_bad            = r   when *first_bad < 0 and some present v_i is inf or NaN
+ *     *cursor               = r + 1
+ * One thread does the stores and the sums, in column order: the same bits eagerly, replayed from a graph or beside other
+ * work on the device.  No store leaves the described buffers under any input.  One launch of one wave, no allocation,
+ * no host synchronisation: legal inside a stream capture.  Launches that share a log must be ordered against each
+ * other (one stream, or graphs replayed on it).  Refused before any launch: n outside (0, COLS], kind outside [0,
+ * KINDS), capacity <= 0, a null values / kinds / cursor / sums / counts / first_bad, 64-bit buffers that are not 8-byte
+ * aligned, values / kinds / columns that are not 4-byte aligned. */
+#define XGGM_TRAINLOG_COLS 8
+#define XGGM_TRAINLOG_KINDS 4
+typedef struct xggm_train_log {
+    float* values;      /* [capacity, COLS]  record r lives in row r % capacity */
+    int64_t* steps;     /* [capacity] optimiser step counter at the append, or NULL */
+    int32_t* kinds;     /* [capacity] kind | (present-column mask << 8) */
+    int64_t* cursor;    /* records appended so far (never wraps) */
+    double* sums;       /* [KINDS, COLS] running sums per kind and column */
+    int64_t* counts;    /* [KINDS] records per kind */
+    int64_t* first_bad; /* -1, or the index of the first record with a non-finite present column */
+    int64_t capacity;
+} xggm_train_log;
+int xggm_train_log_append(const float* const* src, const float* mul, int n, int kind, const int64_t* step,
+                          xggm_train_log* log, xggm_stream_t stream);
+
 /* ---- utilities ---------------------------------------------------------------------------*/
 int xggm_rng_advance(uint64_t* rng, uint64_t by, xggm_stream_t stream);
 int xggm_cast_f32_to_bf16(const float* x, void* out, int64_t n, xggm_stream_t stream);

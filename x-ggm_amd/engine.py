@@ -25,7 +25,7 @@ from . import ops
 
 from .runtime import runtime_of
 from .vqa.vqacpv2 import (forward_backward_plain, forward_backward_ggm, clip_and_step, _sync_grads,
-                          BCEWithLogitsLoss)
+                          BCEWithLogitsLoss, log_pass)
 
 
 class _quiet_gc:
@@ -128,9 +128,82 @@ class AnswerLog:
         return total / n if n else 0.0
 
 
+class TrainLog:
+    """Device-resident log of the scalars of every optimiser pass (``ops.train_log_append`` / xggm_train_log_append):
+    the loss and its terms, the pre-clip gradient norm and the schedule value are appended to a ring of ``capacity``
+    records, with running fp64 sums per pass kind and the index of the first record that holds an inf or a NaN.  The
+    host reads it ONCE per N iterations or per epoch instead of calling ``float()`` on a device scalar in every pass
+    (the reference: ``total_loss += loss.detach() / logit.size(0)``, src/vqa/vqacpv2.py:179, and the tensorboard scalars
+    Train/batch_loss, Train/average_loss and lr, :256-270).
+
+        log = TrainLog(2 * iters_per_epoch, dev)
+        trainer = CapturedTrainer(model, optim, batch, train_log=log)
+        for ...: trainer.iteration(branch)                       # no host synchronisation
+        rec = log.read()                                         # the one read-back
+        rec["values"][rec["kinds"] == TrainLog.PLAIN, TrainLog.LOSS] / batch_size   # Train/batch_loss of every iteration
+        log.average_loss(batch_size, rec)                        # Train/average_loss, from the same read-back
+
+    Everything lives in one int64 device buffer (layout: ``trainlog.words``), so that ``read`` is one transfer into one
+    pinned host buffer.  The ring keeps the last ``capacity`` records; the sums, the counts and ``first_bad`` cover every
+    record since ``reset()``.  Calls that share a log must be ordered against each other (one stream)."""
+
+    LOSS, BCE, KL, DSM, GRAD_NORM, LR_SCALE = range(6)  # columns (trainlog.py); 6 and 7 are spare
+    PLAIN, REL, NODE = 0, 1, 2                          # kinds
+
+    def __init__(self, capacity, device):
+        from . import trainlog
+        capacity = int(capacity)
+        if capacity <= 0:
+            raise ValueError("TrainLog: capacity must be positive")
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError("xggm_amd: the training log must live on the GPU (no CPU fallback)")
+        self.capacity = capacity
+        C, K, H = trainlog.COLS, trainlog.KINDS, trainlog.HEADER
+        n = trainlog.words(capacity)
+        self.buf = torch.zeros(n, dtype=torch.int64, device=device)
+        self.host = torch.zeros(n, dtype=torch.int64).pin_memory()
+        self.cursor = self.buf[0:1]
+        self.first_bad_word = self.buf[1:2]
+        self.counts = self.buf[2:2 + K]
+        self.sums = self.buf[2 + K:H].view(torch.float64).view(K, C)
+        self.steps = self.buf[H:H + capacity]
+        o = H + capacity
+        self.values = self.buf[o:o + capacity * C // 2].view(torch.float32).view(capacity, C)
+        self.kinds = self.buf[o + capacity * C // 2:].view(torch.int32)[:capacity]
+        self.reset()
+
+    def reset(self):
+        """an empty log (ring, sums, counts and cursor zero, ``first_bad`` -1), in stream order: no synchronisation"""
+        self.buf.zero_()
+        self.first_bad_word.fill_(-1)
+
+    def read(self):
+        """-> dict of CPU tensors: values [m, COLS] fp32, steps [m] int64, kinds [m] int64, present [m, COLS] bool,
+        cursor, sums [KINDS, COLS] fp64, counts [KINDS] int64, first_bad -- the records are the last m = min(cursor,
+        capacity), oldest first.  ONE device-to-host transfer and one wait for it."""
+        from .trainlog import decode_packed
+        self.host.copy_(self.buf, non_blocking=True)
+        torch.cuda.current_stream(self.buf.device).synchronize()
+        return decode_packed(self.host, self.capacity)
+
+    def average_loss(self, batch_size, rec=None):
+        """the reference's Train/average_loss (src/vqa/vqacpv2.py:179, :262): the sum of the plain passes' losses since
+        ``reset()``, each divided by the batch size, over their count -- sums[PLAIN][LOSS] / batch_size / counts[PLAIN].
+        ``rec``: what ``read()`` returned (no further transfer); None reads the log"""
+        rec = self.read() if rec is None else rec
+        n = int(rec["counts"][self.PLAIN])
+        return float(rec["sums"][self.PLAIN, self.LOSS]) / batch_size / n if n else 0.0
+
+    def first_bad(self, rec=None):
+        """-1, or the index (counted from ``reset()``) of the first record with an inf or a NaN in a present column;
+        ``rec`` as in ``average_loss``"""
+        return int((self.read() if rec is None else rec)["first_bad"])
+
+
 class CapturedTrainer:
     def __init__(self, model, optim, batch, sigma=1.0, order="vqa", clip=5.0, use_graph=True, warmup_iters=2,
-                 packed_spec=None, answer_log=None):
+                 packed_spec=None, answer_log=None, train_log=None):
         """``batch``: dict of DEVICE tensors feats, boxes, input_ids, input_mask, segment_ids,
         target, adj_true; they become the static input buffers (``load_batch`` copies into them).
         ``packed_spec`` = ``DataLoaderX.spec`` of a loader with ``handover="inline"``: the static buffers are then
@@ -140,9 +213,16 @@ class CapturedTrainer:
         src/vqa/vqacpv2.py:180-181) then ends with one ``ops.answer_pick`` on its logits and the static target, inside
         the captured graph; ``train_score()`` / ``answers()`` read it back.  It observes only: nothing of the step
         depends on it.  Under data parallelism each rank logs its own samples -- the caller averages the ranks'
-        ``train_score()`` (weighted by their counts); no collective is added.  None (default): no launch is added."""
+        ``train_score()`` (weighted by their counts); no collective is added.  None (default): no launch is added.
+        ``train_log`` = a ``TrainLog``: EVERY pass then ends with one ``ops.train_log_append`` (``vqa.vqacpv2.log_pass``)
+        behind its update -- inside the captured graph, under data parallelism inside the update graph's capture -- that
+        records the pass's total loss, its un-weighted terms, the pre-clip norm and the schedule value of the update
+        (which value: ``log_pass``).  It reads device scalars the pass leaves anyway and observes only.  Each rank logs
+        its own values; no collective is added.  None (default): no launch is added."""
         self.model, self.optim = model, optim
         self.answer_log = answer_log
+        self.train_log = train_log
+        self._pass = None  # (kind, loss, terms) of the running pass, for the record its update appends
         if answer_log is not None and not answer_log.with_scores:
             raise ValueError("CapturedTrainer: answer_log needs scores (AnswerLog(with_scores=True))")
         self.rt = runtime_of(model)
@@ -178,6 +258,8 @@ class CapturedTrainer:
             self._capture(warmup_iters)
         if answer_log is not None:
             answer_log.reset()  # what the warm-up passes logged
+        if train_log is not None:
+            train_log.reset()  # the records of the warm-up and capture passes
 
     # ------------------------------------------------------------------ the two halves of a pass
     def _fwd_bwd(self, kind, between=None):
@@ -190,13 +272,25 @@ class CapturedTrainer:
                 # reads the logits and the target only: behind the backward it costs one short launch at the tail of the
                 # (last backward) graph and nothing waits for it
                 ops.answer_pick(logit, self.answer_log, target=s["target"])
+            terms = None
         else:
-            loss, logit, _ = forward_backward_ggm(self.model, self.bce, s["feats"], s["boxes"], sent, s["target"],
-                                                  s["adj_true"], kind, self.sigma, self.kl_weight, between=between)
+            loss, logit, terms = forward_backward_ggm(self.model, self.bce, s["feats"], s["boxes"], sent, s["target"],
+                                                      s["adj_true"], kind, self.sigma, self.kl_weight, between=between)
+        if self.train_log is not None:
+            self._pass = (kind, loss, terms)  # the loss-kernel slots stay alive until the update has appended them
         return loss, logit
 
     def _update(self):
-        return clip_and_step(self.model, self.optim, self.clip, advance=True)
+        total = clip_and_step(self.model, self.optim, self.clip, advance=True)
+        self._log_pass(total)
+        return total
+
+    def _log_pass(self, total):
+        """the training log's record of the running pass, issued (or captured) behind its update"""
+        if self.train_log is not None:
+            kind, loss, terms = self._pass
+            self._pass = None
+            log_pass(self.train_log, self.model, self.optim, kind, loss, total, terms)
 
     # the update as graphs: one, or -- sharded update -- two with the norm's scalar all-reduce between them and the
     # all-gather of the weights behind them (collectives run on the live communicator, never inside a capture)
@@ -216,6 +310,7 @@ class CapturedTrainer:
         with torch.cuda.graph(g2, pool=pool, capture_error_mode=self.capture_mode):
             total = clip_norm_finish(arena, self.clip, tail=(self.optim, None))  # (the schedule step rides on the finish)
             self.optim.step()
+            self._log_pass(total)
         z.gather()
         self.optim.zero_grad()
         # Runtime.advance (new dropout masks for the next pass) is NOT run here: a capture executes nothing, and the

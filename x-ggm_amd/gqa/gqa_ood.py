@@ -4,6 +4,6 @@ from ..vqa.vqacpv2 import (loss_func, compute_kl_loss, BCEWithLogitsLoss, plain_
                            train_iteration as _train_iteration, make_optimizer)  # noqa: F401
 
 
-def train_iteration(model, optim, bce_loss, batch, delta=5, sigma=1.0, branch=None, clip=5.0):
+def train_iteration(model, optim, bce_loss, batch, delta=5, sigma=1.0, branch=None, clip=5.0, train_log=None):
     return _train_iteration(model, optim, bce_loss, batch, delta=delta, sigma=sigma, order="gqa", branch=branch,
-                            clip=clip)
+                            clip=clip, train_log=train_log)

@@ -1291,6 +1291,63 @@ def answer_pick(logits, log, target=None, rows=None):
          ptr(sum_ws(logits.device)), stream())
 
 
+TRAINLOG_COLS = 8   # XGGM_TRAINLOG_COLS (include/xggm.h)
+TRAINLOG_KINDS = 4  # XGGM_TRAINLOG_KINDS
+
+
+class TrainLogDesc(_ct.Structure):
+    """mirror of ``xggm_train_log`` (include/xggm.h)"""
+    _fields_ = [("values", _ct.c_void_p), ("steps", _ct.c_void_p), ("kinds", _ct.c_void_p), ("cursor", _ct.c_void_p),
+                ("sums", _ct.c_void_p), ("counts", _ct.c_void_p), ("first_bad", _ct.c_void_p), ("capacity", _ct.c_int64)]
+
+
+def train_log_append(log, kind, cols, mul=None, step=None):
+    """append ONE record to ``log`` -- anything with the device tensors ``values`` fp32 [capacity, 8], ``steps`` int64
+    [capacity] or None, ``kinds`` int32 [capacity], ``cursor`` int64 [1], ``sums`` fp64 [4, 8], ``counts`` int64 [4],
+    ``first_bad_word`` int64 [1] (``engine.TrainLog``).  ``cols``: up to 8 entries, each a 0-dim or 1-element fp32 DEVICE
+    tensor or None (column absent); ``mul``: one host float per column (None: all ones), the record holds ``col * mul``;
+    ``step``: 1-element int64 device tensor (an optimiser step counter) or None.  Contract: xggm_train_log_append in
+    xggm.h.  One launch, nothing returned and nothing kept alive: the log is read with ``log.read()``."""
+    cols = list(cols)
+    n = len(cols)
+    if not 0 < n <= TRAINLOG_COLS:
+        raise ValueError("train_log_append: %d columns (a record holds 1 .. %d)" % (n, TRAINLOG_COLS))
+    if mul is not None and len(mul) != n:
+        raise ValueError("train_log_append: %d factors for %d columns" % (len(mul), n))
+    for i, t in enumerate(cols):
+        if t is None:
+            continue
+        if t.dtype != F32 or t.numel() != 1:
+            raise ValueError("train_log_append: column %d is %s %s, expected ONE fp32 value (0-dim or 1-element)"
+                             % (i, t.dtype, tuple(t.shape)))
+        _chk(t, F32, "column %d" % i)
+    _c(log.values, F32, "log.values"), _c(log.kinds, torch.int32, "log.kinds"), _c(log.cursor, torch.int64, "log.cursor")
+    _c(log.sums, torch.float64, "log.sums"), _c(log.counts, torch.int64, "log.counts")
+    _c(log.first_bad_word, torch.int64, "log.first_bad_word")
+    cap = int(log.capacity)
+    if log.values.numel() < cap * TRAINLOG_COLS or log.kinds.numel() < cap or log.sums.numel() < TRAINLOG_KINDS * TRAINLOG_COLS \
+            or log.counts.numel() < TRAINLOG_KINDS or log.cursor.numel() < 1 or log.first_bad_word.numel() < 1:
+        raise ValueError("train_log_append: the log's buffers are smaller than its capacity %d says" % cap)
+    if log.steps is not None:
+        _c(log.steps, torch.int64, "log.steps")
+        if log.steps.numel() < cap:
+            raise ValueError("train_log_append: log.steps holds %d entries, the capacity is %d" % (log.steps.numel(), cap))
+    if step is not None:
+        _c(step, torch.int64, "step")
+        if step.numel() != 1:
+            raise ValueError("train_log_append: step must be ONE int64 counter")
+    dev = log.cursor.device
+    for t in cols + [step, log.values, log.steps, log.kinds, log.sums, log.counts, log.first_bad_word]:
+        if t is not None and t.device != dev:
+            raise RuntimeError("train_log_append: the log, the columns and the step must live on one device")
+    d = TrainLogDesc(ptr(log.values), ptr(log.steps), ptr(log.kinds), ptr(log.cursor), ptr(log.sums), ptr(log.counts),
+                     ptr(log.first_bad_word), cap)
+    src = (_ct.c_void_p * n)(*[ptr(t) for t in cols])
+    fac = None if mul is None else (_ct.c_float * n)(*[float(m) for m in mul])
+    call("xggm_train_log_append", _ct.cast(src, _ct.c_void_p), None if fac is None else _ct.cast(fac, _ct.c_void_p), n,
+         int(kind), ptr(step), _ct.addressof(d), stream())
+
+
 class _PassTail(_ct.Structure):
     _fields_ = [("steps", _ct.c_void_p), ("lr_scale", _ct.c_void_p), ("index", _ct.c_void_p), ("t_total", _ct.c_void_p),
                 ("warmup", _ct.c_void_p), ("n", _ct.c_int), ("rng", _ct.c_void_p), ("rng_by", _ct.c_uint64)]

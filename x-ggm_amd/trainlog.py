@@ -1,0 +1,53 @@
+"""Host side of the device-resident training log (``engine.TrainLog``, ``xggm_train_log_append``): pure Python,
+importable without a GPU.  The kernel appends one record per optimiser pass -- the scalars the reference reads from the
+GPU in every iteration (``total_loss += loss.detach() / logit.size(0)``, src/vqa/vqacpv2.py:179; the tensorboard scalars
+of :256-270) -- to a ring on the device; what is here turns ONE read-back of that ring into host tensors."""
+
+COLS = 8   # XGGM_TRAINLOG_COLS
+KINDS = 4  # XGGM_TRAINLOG_KINDS
+LOSS, BCE, KL, DSM, GRAD_NORM, LR_SCALE = range(6)  # columns of a pass record; 6 and 7 are spare
+PLAIN, REL, NODE = 0, 1, 2                          # kinds
+KIND_OF = {"plain": PLAIN, "rel": REL, "node": NODE}
+HEADER = 2 + KINDS + KINDS * COLS  # int64 words in front of the ring: cursor, first_bad, counts, sums (fp64 bits)
+
+
+def words(capacity):
+    """int64 words of the one buffer a log of ``capacity`` records lives in:
+    [cursor, first_bad, counts[KINDS], sums[KINDS * COLS] (fp64), steps[capacity], values[capacity * COLS] (fp32),
+    kinds[capacity] (int32)]"""
+    capacity = int(capacity)
+    return HEADER + capacity + capacity * COLS // 2 + (capacity + 1) // 2
+
+
+def unroll(cursor, capacity):
+    """row order of the retained records, oldest first: record r lives in row r % capacity and the ring keeps the last
+    min(cursor, capacity) records"""
+    cursor, capacity = int(cursor), int(capacity)
+    if capacity <= 0 or cursor < 0:
+        raise ValueError("unroll: cursor %d, capacity %d" % (cursor, capacity))
+    return [r % capacity for r in range(max(cursor - capacity, 0), cursor)]
+
+
+def decode_packed(w, capacity):
+    """what ``TrainLog.read`` does with the int64 words of its ONE transfer (layout: ``words``) -> dict of CPU tensors /
+    numbers: values [m, COLS] fp32, steps [m] int64, kinds [m] int64 (the kind alone), present [m, COLS] bool, cursor,
+    sums [KINDS, COLS] fp64, counts [KINDS] int64, first_bad; the m = min(cursor, capacity) retained records oldest
+    first"""
+    import torch
+    capacity = int(capacity)
+    cursor = int(w[0])
+    if cursor < 0:
+        raise RuntimeError("training log: cursor %d is negative" % cursor)
+    o = HEADER
+    steps = w[o:o + capacity]
+    o += capacity
+    values = w[o:o + capacity * COLS // 2].view(torch.float32).view(capacity, COLS)
+    o += capacity * COLS // 2
+    packed = w[o:].view(torch.int32)[:capacity]
+    order = torch.tensor(unroll(cursor, capacity), dtype=torch.int64)
+    packed = packed[order].to(torch.int64)
+    mask = packed >> 8
+    return dict(values=values[order].clone(), steps=steps[order].clone(), kinds=packed & 0xFF,
+                present=((mask[:, None] >> torch.arange(COLS)) & 1).bool(), cursor=w[0].clone(),
+                sums=w[2 + KINDS:HEADER].view(torch.float64).view(KINDS, COLS).clone(), counts=w[2:2 + KINDS].clone(),
+                first_bad=w[1].clone())

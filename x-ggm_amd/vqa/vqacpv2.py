@@ -180,10 +180,12 @@ def forward_backward_ggm(model, bce_loss, feats, boxes, sent, target, adj_true, 
         raise ValueError(branch)
     x_gen = model.fusion_fc(XF.PoolConcatFn.apply(x_fuse, node_feats))
     logit = model.logit_fc(x_gen)
-    loss = XF.LossSumFn.apply(bce_loss(logit, target, scale=A, slot=rt.scalar_slot()), d_loss, loss_grad)
+    bce = bce_loss(logit, target, scale=A, slot=rt.scalar_slot())
+    loss = XF.LossSumFn.apply(bce, d_loss, loss_grad)
     rt.backward(loss, between)
-    # reported as the reference logs them: d_loss = KL * A, loss_grad = the unweighted DSM term
-    return loss.detach(), logit.detach(), dict(d_loss=_Scaled(d_loss, w_kl / A), loss_grad=_Scaled(loss_grad, w_dsm))
+    # reported as the reference logs them: bce = BCE * A, d_loss = KL * A, loss_grad = the unweighted DSM term
+    return loss.detach(), logit.detach(), dict(d_loss=_Scaled(d_loss, w_kl / A), loss_grad=_Scaled(loss_grad, w_dsm),
+                                               bce=_Scaled(bce, 1.0))
 
 
 def clip_and_step(model, optim, clip=5.0, advance=False):
@@ -202,18 +204,55 @@ def clip_and_step(model, optim, clip=5.0, advance=False):
     return total
 
 
-def plain_pass(model, optim, bce_loss, feats, boxes, sent, target, clip=5.0, advance=False):
+def log_pass(train_log, model, optim, kind, loss, total, terms=None):
+    """one ``ops.train_log_append`` behind the update of a pass (``plain_pass`` / ``ggm_pass`` here,
+    ``engine.CapturedTrainer(train_log=)``): the same call with the same operands wherever the pass runs, hence the same
+    bits.  ``train_log``: an ``engine.TrainLog``; ``loss`` / ``total``: the pass's total loss and pre-clip norm (device
+    scalars); ``terms``: the third value of ``forward_backward_ggm`` (the loss-kernel slots and the weights ``_Scaled``
+    divides by), None for the plain pass, whose loss IS its BCE term.  The recorded terms are the un-weighted ones the
+    reference logs: BCE x answers, KL x answers, the DSM term.
+
+    LR_SCALE and the record's step come from the arena group of the answer head ``model.logit_fc`` -- part of
+    ``optim.param_groups[0]`` under ``make_optimizer``, and the one group of it that EVERY pass updates (a group that only
+    the GGM passes touch would leave stale values in the plain records).  The schedule step of a pass runs BEFORE its update (on the norm's finishing
+    launch, ``clip_grad_norm_``; else at the top of ``BertAdam.step``): it writes lr_scale = warmup_linear(s / t_total,
+    warmup) from the counter s it finds and leaves s + 1.  The append is issued behind the update, so it reads the
+    value THIS pass's update multiplied its lr by, together with the counter the pass left: a record with step k holds
+    warmup_linear((k - 1) / t_total, warmup)."""
+    from .. import ops, trainlog as T
+    arena = runtime_of(model).arena
+    xg = getattr(next(model.logit_fc.parameters()), "_xg", None)
+    gi = arena.group_index[xg[3]] if xg is not None and xg[0] is arena else None
+    cols, mul = [None] * 6, [1.0] * 6
+    cols[T.LOSS] = loss
+    if terms is None:
+        cols[T.BCE] = loss
+    else:
+        for c, key in ((T.BCE, "bce"), (T.KL, "d_loss"), (T.DSM, "loss_grad")):
+            cols[c], mul[c] = terms[key].t, 1.0 / terms[key].c
+    cols[T.GRAD_NORM] = total
+    if gi is not None:
+        cols[T.LR_SCALE] = arena.lr_scale[gi:gi + 1]
+    ops.train_log_append(train_log, T.KIND_OF[kind], cols, mul, step=None if gi is None else arena.steps[gi:gi + 1])
+
+
+def plain_pass(model, optim, bce_loss, feats, boxes, sent, target, clip=5.0, advance=False, train_log=None):
+    """``train_log`` = an ``engine.TrainLog``: the pass ends with one ``log_pass`` behind its update (None: no launch)"""
     out = forward_backward_plain(model, bce_loss, feats, boxes, sent, target)
     _sync_grads(model)
-    clip_and_step(model, optim, clip, advance)
+    total = clip_and_step(model, optim, clip, advance)
+    if train_log is not None:
+        log_pass(train_log, model, optim, "plain", out[0], total)
     return out
 
 
 def ggm_pass(model, optim, bce_loss, feats, boxes, sent, target, adj_true, branch, sigma=1.0, kl_weight=8.0,
-             randn=None, clip=5.0, advance=False):
+             randn=None, clip=5.0, advance=False, train_log=None):
     out = forward_backward_ggm(model, bce_loss, feats, boxes, sent, target, adj_true, branch, sigma, kl_weight, randn)
     _sync_grads(model)
-    clip_and_step(model, optim, clip, advance)
+    total = clip_and_step(model, optim, clip, advance)
+    if train_log is not None:
+        log_pass(train_log, model, optim, branch, out[0], total, out[2])
     return out
 
 
@@ -229,10 +268,12 @@ def pick_branch(delta, rng=random, model=None):
     return "rel" if rel else "node"
 
 
-def train_iteration(model, optim, bce_loss, batch, delta=5, sigma=1.0, order="vqa", branch=None, clip=5.0):
+def train_iteration(model, optim, bce_loss, batch, delta=5, sigma=1.0, order="vqa", branch=None, clip=5.0, train_log=None):
     """one iteration = two fwd+bwd+clip+BertAdam passes.  ``batch``: dict with feats, boxes,
     sent, target, adj_true (device tensors).  order 'vqa': plain then GGM (KL weight 8);
-    'gqa': GGM then plain (KL weight 12, src/gqa/gqa_ood.py:197)."""
+    'gqa': GGM then plain (KL weight 12, src/gqa/gqa_ood.py:197).  ``train_log`` = an ``engine.TrainLog``: every pass
+    appends its record to it on the device (``log_pass``) -- the scalars of src/vqa/vqacpv2.py:179 and :256-270 without a
+    read per iteration."""
     rt = runtime_of(model)
     model.train()
     if branch is None:
@@ -240,14 +281,14 @@ def train_iteration(model, optim, bce_loss, batch, delta=5, sigma=1.0, order="vq
     args = (batch["feats"], batch["boxes"], batch["sent"], batch["target"])
     out = {}
     if order == "vqa":
-        out["loss_plain"], out["logit"] = plain_pass(model, optim, bce_loss, *args, clip=clip, advance=True)
+        out["loss_plain"], out["logit"] = plain_pass(model, optim, bce_loss, *args, clip=clip, advance=True, train_log=train_log)
         out["loss_ggm"], _, ex = ggm_pass(model, optim, bce_loss, *args, batch["adj_true"], branch, sigma, 8.0,
-                                          clip=clip, advance=True)
+                                          clip=clip, advance=True, train_log=train_log)
     else:
         out["loss_ggm"], _, ex = ggm_pass(model, optim, bce_loss, *args, batch["adj_true"], branch, sigma, 12.0,
-                                          clip=clip, advance=True)
-        out["loss_plain"], out["logit"] = plain_pass(model, optim, bce_loss, *args, clip=clip, advance=True)
-    out.update(ex)
+                                          clip=clip, advance=True, train_log=train_log)
+        out["loss_plain"], out["logit"] = plain_pass(model, optim, bce_loss, *args, clip=clip, advance=True, train_log=train_log)
+    out.update((k, v) for k, v in ex.items() if k != "bce")  # the BCE slot is ``log_pass``'s: the keys stay the reference's
     out["branch"] = branch
     _tick_guard(model)
     return out
