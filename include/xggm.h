@@ -620,6 +620,62 @@ int xggm_sched_step(int64_t* step, float* lr_scale, int64_t t_total, float warmu
 int xggm_sched_step_multi(int64_t* steps, float* lr_scale, const int* index, const int64_t* t_total, const float* warmup,
                           int n, xggm_stream_t stream);
 
+/* The reference's other optimisers (src/param.py:9-31 binds --optim rms|adam|adamw|adamax|sgd to torch.optim classes,
+ * src/vqa/vqacpv2.py:141 builds args.optimizer(self.model.parameters(), args.lr)) on the same fused pass as BertAdam:
+ * clip scale, update, bf16 shadow, n & 3 tail, spans through a prefix table.  torch's single-tensor semantics with
+ * g' = g * coef + weight_decay * p (coef: clip scale times g_scale):
+ *   ADAM     m += (g' - m)(1 - b1); v = b2 v + (1 - b2) g'^2; p -= lr / bc1 * m / (sqrt(v) / sqrt(bc2) + eps)
+ *   ADAMW    p *= 1 - lr * weight_decay first, then ADAM with g' = g * coef
+ *   ADAMAX   m as ADAM; v = max(b2 v, |g'| + eps); p -= lr / bc1 * m / v
+ *   SGD      momentum == 0: p -= lr g' (m, v neither read nor written); else m = g' at the group's first step,
+ *            momentum * m + (1 - dampening) g' after it; p -= lr * (nesterov ? g' + momentum * m : m)
+ *   RMSPROP  v = alpha v + (1 - alpha) g'^2; d = g' / (sqrt(v) + eps); momentum == 0: p -= lr d (m untouched), else
+ *            m = momentum * m + d; p -= lr m
+ * `a` holds the span as for xggm_bertadam_multi (a.b1 / a.b2 are ignored for these rules, a.shadow8 must be NULL; a.eps
+ * and a.weight_decay are used).  The complements 1 - b1, 1 - b2, 1 - dampening, 1 - alpha are taken in DOUBLE on the host
+ * (fp32 1 - 0.999f is off by 1.3e-5 relative).  bc = 1 - b^t comes from `step_scalars`: three device floats {1 / bc1,
+ * 1 / sqrt(bc2), first-step flag} that xggm_sched_step_ex computed in double from the device-resident step counter
+ * (required for ADAM / ADAMW / ADAMAX and for SGD with momentum; NULL elsewhere).
+ * XGGM_RULE_BERTADAM runs xggm_bertadam_multi's kernel on `a` alone. */
+#define XGGM_RULE_BERTADAM 0
+#define XGGM_RULE_ADAM 1
+#define XGGM_RULE_ADAMW 2
+#define XGGM_RULE_ADAMAX 3
+#define XGGM_RULE_SGD 4
+#define XGGM_RULE_RMSPROP 5
+typedef struct xggm_optim_args {
+    xggm_adam_args a;
+    int rule;                  /* XGGM_RULE_*: the same for every span of a call */
+    const float* step_scalars; /* device: {1 / bc1, 1 / sqrt(bc2), first step ? 1 : 0} of this span's group */
+    double b1, b2;             /* ADAM / ADAMW / ADAMAX */
+    double momentum;           /* SGD, RMSPROP (zero or not: the same for every span of a call) */
+    double dampening;          /* SGD */
+    double alpha;              /* RMSPROP */
+    int nesterov;              /* SGD */
+} xggm_optim_args;
+/* n spans (HOST array) in one launch per 8 spans; all spans share rule, gradient type and whether momentum is zero
+ * (src/param.py:9-31, src/vqa/vqacpv2.py:141) */
+int xggm_optim_multi(const xggm_optim_args* args, int n, xggm_stream_t stream);
+
+/* xggm_sched_step_multi with a schedule kind per entry (src/lxrt/optimization.py:27-48: warmup_cosine, warmup_constant,
+ * warmup_linear; the xggm_sched_step* calls keep meaning warmup_linear) and the per-step scalars of xggm_optim_multi:
+ * for entry i with k = index, s = steps[k]: lr_scale[k] = kind(s / t_total, warmup) in double (1 when t_total <= 0),
+ * steps[k] = t = s + 1 and, with step_scalars (or NULL), step_scalars[4 k ..] = {1 / (1 - b1^t), 1 / sqrt(1 - b2^t),
+ * s == 0 ? 1 : 0, 0} -- computed ONCE per step in double from the device counter (graphs replay it), as torch computes
+ * them from Python floats (src/param.py:9-31, src/vqa/vqacpv2.py:141).  entries: HOST array, n <= 16 distinct counters. */
+#define XGGM_SCHED_LINEAR 0
+#define XGGM_SCHED_COSINE 1
+#define XGGM_SCHED_CONSTANT 2
+typedef struct xggm_sched_entry {
+    int index;
+    int kind; /* XGGM_SCHED_* */
+    int64_t t_total;
+    double warmup;
+    double b1, b2;
+} xggm_sched_entry;
+int xggm_sched_step_ex(int64_t* steps, float* lr_scale, float* step_scalars, const xggm_sched_entry* entries, int n,
+                       xggm_stream_t stream);
+
 /* The tail of a pass in two launches instead of seven: nn.utils.clip_grad_norm_'s norm (src/vqa/vqacpv2.py:175) over up
  * to 24 ranges in all -- `n` ranges of the gradient buffer `g` (squared) and `n_slots` ranges of the slot table the
  * weight-gradient products filled (xggm_gemm_problem.sqsum: summed as they are) -- with partials added in (range, slice)

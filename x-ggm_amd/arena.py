@@ -140,6 +140,9 @@ class ParamArena:
         self.steps = torch.zeros(len(order), device=dev, dtype=torch.int64)
         self.lr_scale = torch.ones(len(order), device=dev, dtype=torch.float32)
         self.sqnorm = torch.zeros(1, device=dev, dtype=torch.float32)
+        # per group {1 / bc1, 1 / sqrt(bc2), first step, -}: the bias corrections of the torch.optim rules (xggm_amd.optim),
+        # written in double by the launch that advances ``steps`` (ops.sched_step_ex), read by the update kernel
+        self.step_scalars = torch.zeros(4 * len(order), device=dev, dtype=torch.float32)
         # learning rate of each group as the update kernels read it (BertAdam.sync_hyper keeps it equal to
         # param_groups[i]['lr']: an edit between replays of a captured pass takes effect)
         self.lr_table = torch.zeros(len(order), device=dev, dtype=torch.float32)

@@ -7,6 +7,8 @@
 //                           p/g/m/v (src/lxrt/optimization.py:159-193): 16 B read + 12(+2) B
 //                           written per parameter, the HBM floor of the update.
 //   xggm_sched_step         warmup_linear(step/t_total) on the device-resident step counter
+//   xggm_optim_multi        the same pass for torch.optim's Adam / AdamW / Adamax / SGD / RMSprop rules (src/param.py:9-31)
+//   xggm_sched_step_ex      schedule kinds per entry + bias corrections in double from the device counter
 //                           (optimization.py:42-48,177-181) so a captured graph replays correctly
 // Scalars (losses, norms, schedule values, upstream gradients) live in device memory: nothing
 // here synchronises with the host.
@@ -384,11 +386,90 @@ __device__ __forceinline__ void adam_update(float& p, float& m, float& v, float 
     p = __fmaf_rn(-lr, upd, p);
 }
 
+// The reference's other optimisers (src/param.py:9-31, src/vqa/vqacpv2.py:141: torch.optim classes) on the same pass.
+// A rule is a compile-time instantiation of the body; SGD and RMSprop come with and without a momentum buffer so that a
+// buffer the rule does not have is neither read nor written.
+enum { R_BERT = 0, R_ADAM, R_ADAMAX, R_SGD0, R_SGDM, R_RMS0, R_RMSM };
+template <int RULE> struct RuleTraits {
+    static constexpr bool use_m = RULE == R_BERT || RULE == R_ADAM || RULE == R_ADAMAX || RULE == R_SGDM || RULE == R_RMSM;
+    static constexpr bool use_v = RULE == R_BERT || RULE == R_ADAM || RULE == R_ADAMAX || RULE == R_RMS0 || RULE == R_RMSM;
+};
+struct RuleArgs {
+    const float* hs = nullptr;  // device: {1 / bc1, 1 / sqrt(bc2), first step} (xggm_sched_step_ex)
+    float omb1 = 0.f, omb2 = 0.f;  // 1 - b1, 1 - b2 (RMSprop: 1 - alpha), rounded from DOUBLE differences
+    float mom = 0.f, omd = 0.f;    // momentum, 1 - dampening
+    int nesterov = 0;
+    int decoupled = 0;             // AdamW: p *= 1 - lr * wd first, no wd in g'
+};
+// what a rule needs once per launch and span (uniform over the grid)
+struct RuleStep {
+    float lr;         // scheduled lr; Adam / Adamax: lr / bc1
+    float isb2 = 1.f;  // 1 / sqrt(bc2)
+    float dec = 1.f;   // AdamW: 1 - lr * wd
+    float wd = 0.f;    // coupled weight decay of g'
+    bool first = false;
+};
+template <int RULE>
+__device__ __forceinline__ RuleStep rule_step(const AdamArgs& a, const RuleArgs& r, float lr) {
+    RuleStep s;
+    s.lr = lr;
+    s.wd = a.wd;
+    if (RULE == R_BERT) return s;
+    if (r.decoupled) {
+        s.dec = __fmaf_rn(-lr, a.wd, 1.f);
+        s.wd = 0.f;
+    }
+    if (RULE == R_ADAM || RULE == R_ADAMAX) {
+        s.lr = __fmul_rn(lr, r.hs[0]);
+        s.isb2 = r.hs[1];
+    }
+    if (RULE == R_SGDM) s.first = r.hs[2] != 0.f;
+    return s;
+}
+// One element; the multiply-adds are pinned as in adam_update, so the fp32- and the bf16-gradient instantiation of a
+// rule give the same bits on the same values.  Operation order after torch/optim/{adam,adamax,sgd,rmsprop}.py
+// (_single_tensor_*); with a zero gradient and zero state a zero p stays exactly zero under every rule, and so do its
+// shadow and m; v does too except under Adamax, whose exp_inf = max(b2 u, |g| + eps) becomes eps by torch's definition.
+template <int RULE>
+__device__ __forceinline__ void rule_update(float& p, float& m, float& v, float gk, const AdamArgs& a, const RuleArgs& r,
+                                            const RuleStep& s) {
+    if (RULE == R_BERT) {
+        adam_update(p, m, v, gk, a.b1, a.b2, a.eps, a.wd, s.lr);
+        return;
+    }
+    if (r.decoupled) p = __fmul_rn(p, s.dec);
+    const float g = __fmaf_rn(s.wd, p, gk);
+    if (RULE == R_ADAM) {
+        m = __fmaf_rn(__fadd_rn(g, -m), r.omb1, m);
+        v = __fmaf_rn(v, a.b2, __fmul_rn(__fmul_rn(r.omb2, g), g));
+        p = __fmaf_rn(-s.lr, m / __fmaf_rn(sqrtf(v), s.isb2, a.eps), p);
+    } else if (RULE == R_ADAMAX) {
+        m = __fmaf_rn(__fadd_rn(g, -m), r.omb1, m);
+        v = fmaxf(__fmul_rn(a.b2, v), __fadd_rn(fabsf(g), a.eps));
+        p = __fmaf_rn(-s.lr, m / v, p);
+    } else if (RULE == R_SGD0) {
+        p = __fmaf_rn(-s.lr, g, p);
+    } else if (RULE == R_SGDM) {
+        m = s.first ? g : __fmaf_rn(r.mom, m, __fmul_rn(r.omd, g));
+        p = __fmaf_rn(-s.lr, r.nesterov ? __fmaf_rn(r.mom, m, g) : m, p);
+    } else {  // R_RMS0, R_RMSM
+        v = __fmaf_rn(v, a.b2, __fmul_rn(__fmul_rn(r.omb2, g), g));
+        const float d = g / __fadd_rn(sqrtf(v), a.eps);
+        if (RULE == R_RMSM) {
+            m = __fmaf_rn(r.mom, m, d);
+            p = __fmaf_rn(-s.lr, m, p);
+        } else {
+            p = __fmaf_rn(-s.lr, d, p);
+        }
+    }
+}
+
 // One float4 of each of p, g, m, v per step; UNR independent float4 quadruples per thread and
 // iteration (loads issued before any use).  g is read once and m, v, shadow are not re-read before the
 // next step: non-temporal accesses keep them from displacing the weights' bf16 shadow in L2/MALL.
-template <int UNR, bool NTMP, bool GB16>
-__device__ __forceinline__ void bertadam_body(const AdamArgs& a, const int blk, const int nblk) {
+template <int UNR, bool NTMP, bool GB16, int RULE = R_BERT>
+__device__ __forceinline__ void bertadam_body(const AdamArgs& a, const int blk, const int nblk, const RuleArgs& ra = RuleArgs()) {
+    constexpr bool USE_M = RuleTraits<RULE>::use_m, USE_V = RuleTraits<RULE>::use_v;
     float coef = 1.f;
     if (a.sqnorm) {
         const float total = sqrtf(*a.sqnorm);
@@ -396,6 +477,7 @@ __device__ __forceinline__ void bertadam_body(const AdamArgs& a, const int blk, 
     }
     coef *= a.g_scale;
     const float lr = (a.lr_dev ? *a.lr_dev : a.lr) * (a.lr_scale ? *a.lr_scale : 1.f);
+    const RuleStep rs = rule_step<RULE>(a, ra, lr);
     const int64_t n4 = a.n >> 2;
     typedef float __attribute__((ext_vector_type(4))) f4;
     typedef short __attribute__((ext_vector_type(4))) s4;
@@ -434,12 +516,14 @@ __device__ __forceinline__ void bertadam_body(const AdamArgs& a, const int blk, 
                     g[u] = reinterpret_cast<const f4*>(a.g)[i];
                 }
                 if (NTMP) {
-                    m[u] = __builtin_nontemporal_load(reinterpret_cast<const f4*>(a.m) + i);
-                    v[u] = __builtin_nontemporal_load(reinterpret_cast<const f4*>(a.v) + i);
+                    if (USE_M) m[u] = __builtin_nontemporal_load(reinterpret_cast<const f4*>(a.m) + i);
+                    if (USE_V) v[u] = __builtin_nontemporal_load(reinterpret_cast<const f4*>(a.v) + i);
                 } else {
-                    m[u] = reinterpret_cast<const f4*>(a.m)[i];
-                    v[u] = reinterpret_cast<const f4*>(a.v)[i];
+                    if (USE_M) m[u] = reinterpret_cast<const f4*>(a.m)[i];
+                    if (USE_V) v[u] = reinterpret_cast<const f4*>(a.v)[i];
                 }
+                if (!USE_M) m[u] = f4{0.f, 0.f, 0.f, 0.f};
+                if (!USE_V) v[u] = f4{0.f, 0.f, 0.f, 0.f};
             }
         }
         float w8q[UNR];
@@ -455,7 +539,7 @@ __device__ __forceinline__ void bertadam_body(const AdamArgs& a, const int blk, 
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
                     float pk = p[u][k], mk = m[u][k], vk = v[u][k];
-                    adam_update(pk, mk, vk, __fmul_rn(g[u][k], coef), a.b1, a.b2, a.eps, a.wd, lr);
+                    rule_update<RULE>(pk, mk, vk, __fmul_rn(g[u][k], coef), a, ra, rs);
                     p[u][k] = pk;
                     m[u][k] = mk;
                     v[u][k] = vk;
@@ -463,11 +547,11 @@ __device__ __forceinline__ void bertadam_body(const AdamArgs& a, const int blk, 
                 if (NTMP) __builtin_nontemporal_store(p[u], reinterpret_cast<f4*>(a.p) + i);
                 else reinterpret_cast<f4*>(a.p)[i] = p[u];
                 if (NTMP) {
-                    __builtin_nontemporal_store(m[u], reinterpret_cast<f4*>(a.m) + i);
-                    __builtin_nontemporal_store(v[u], reinterpret_cast<f4*>(a.v) + i);
+                    if (USE_M) __builtin_nontemporal_store(m[u], reinterpret_cast<f4*>(a.m) + i);
+                    if (USE_V) __builtin_nontemporal_store(v[u], reinterpret_cast<f4*>(a.v) + i);
                 } else {
-                    reinterpret_cast<f4*>(a.m)[i] = m[u];
-                    reinterpret_cast<f4*>(a.v)[i] = v[u];
+                    if (USE_M) reinterpret_cast<f4*>(a.m)[i] = m[u];
+                    if (USE_V) reinterpret_cast<f4*>(a.v)[i] = v[u];
                 }
                 if (a.shadow) {
                     s4 sh;
@@ -498,10 +582,10 @@ __device__ __forceinline__ void bertadam_body(const AdamArgs& a, const int blk, 
     if (blk == 0 && threadIdx.x < (a.n & 3)) {  // (ranges with an e4m3 copy are multiples of 256: no tail there)
         const int64_t i = (n4 << 2) + threadIdx.x;
         const float gi = GB16 ? __bfloat162float(reinterpret_cast<const bf16*>(a.g)[i]) : reinterpret_cast<const float*>(a.g)[i];
-        float p = a.p[i], m = a.m[i], v = a.v[i];
-        adam_update(p, m, v, __fmul_rn(gi, coef), a.b1, a.b2, a.eps, a.wd, lr);
-        a.m[i] = m;
-        a.v[i] = v;
+        float p = a.p[i], m = USE_M ? a.m[i] : 0.f, v = USE_V ? a.v[i] : 0.f;
+        rule_update<RULE>(p, m, v, __fmul_rn(gi, coef), a, ra, rs);
+        if (USE_M) a.m[i] = m;
+        if (USE_V) a.v[i] = v;
         a.p[i] = p;
         if (a.shadow) a.shadow[i] = __float2bfloat16(p);
     }
@@ -528,6 +612,22 @@ __global__ __launch_bounds__(NT) void bertadam_multi_kernel(AdamMulti am) {
     for (int k = 1; k < ADAM_MULTI; ++k)
         if (k < am.n && (int)blockIdx.x >= am.blk0[k]) j = k;
     bertadam_body<UNR, NTMP, GB16>(am.a[j], (int)blockIdx.x - am.blk0[j], am.blk0[j + 1] - am.blk0[j]);
+}
+
+// the same launch for a rule of xggm_optim_multi: every span carries its rule arguments beside the update's
+struct OptimMulti {
+    AdamArgs a[ADAM_MULTI];
+    RuleArgs r[ADAM_MULTI];
+    int blk0[ADAM_MULTI + 1];
+    int n;
+};
+template <int UNR, bool NTMP, bool GB16, int RULE>
+__global__ __launch_bounds__(NT) void optim_multi_kernel(OptimMulti om) {
+    int j = 0;
+#pragma unroll
+    for (int k = 1; k < ADAM_MULTI; ++k)
+        if (k < om.n && (int)blockIdx.x >= om.blk0[k]) j = k;
+    bertadam_body<UNR, NTMP, GB16, RULE>(om.a[j], (int)blockIdx.x - om.blk0[j], om.blk0[j + 1] - om.blk0[j], om.r[j]);
 }
 
 // Delayed scaling of the e4m3 operands (weights and activation sites share one table).  Producers record the
@@ -608,6 +708,41 @@ __global__ void sched_multi_kernel(int64_t* steps, float* lr_scale, SchedArgs a)
     }
     lr_scale[k] = sc;
     steps[k] = s + 1;
+}
+
+// sched_multi_kernel with a schedule kind per entry (src/lxrt/optimization.py:27-48), evaluated in double, and the
+// per-step scalars of the torch.optim rules: bias corrections 1 - b^t from the DEVICE counter, in double, once per step
+// (fp32 1 - b2^t at t = 1, b2 = 0.999 is wrong by 1.3e-5 relative; torch takes them from Python floats)
+struct SchedExArgs {
+    int index[MAX_SCHED];
+    int kind[MAX_SCHED];
+    int64_t t_total[MAX_SCHED];
+    double warmup[MAX_SCHED];
+    double b1[MAX_SCHED], b2[MAX_SCHED];
+    int n;
+};
+__global__ void sched_ex_kernel(int64_t* steps, float* lr_scale, float* hs, SchedExArgs a) {
+    const int i = threadIdx.x;
+    if (blockIdx.x != 0 || i >= a.n) return;
+    const int k = a.index[i];
+    const int64_t s = steps[k];
+    double sc = 1.0;
+    if (a.t_total[i] > 0) {
+        const double x = (double)s / (double)a.t_total[i], w = a.warmup[i];
+        if (x < w) sc = x / w;
+        else if (a.kind[i] == XGGM_SCHED_COSINE) sc = 0.5 * (1.0 + cos(3.141592653589793 * x));
+        else if (a.kind[i] == XGGM_SCHED_CONSTANT) sc = 1.0;
+        else sc = fmax((x - 1.0) / (w - 1.0), 0.0);
+    }
+    lr_scale[k] = (float)sc;
+    steps[k] = s + 1;
+    if (hs) {
+        const double t = (double)(s + 1);
+        hs[4 * k + 0] = (float)(1.0 / (1.0 - pow(a.b1[i], t)));
+        hs[4 * k + 1] = (float)(1.0 / sqrt(1.0 - pow(a.b2[i], t)));
+        hs[4 * k + 2] = s == 0 ? 1.f : 0.f;
+        hs[4 * k + 3] = 0.f;
+    }
 }
 
 __global__ void rng_advance_kernel(uint64_t* rng, uint64_t by) {
@@ -808,6 +943,79 @@ extern "C" int xggm_bertadam_multi(const xggm_adam_args* args, int n, hipStream_
     return XGGM_OK;
 }
 
+extern "C" int xggm_optim_multi(const xggm_optim_args* args, int n, hipStream_t st) {
+    XGGM_REQUIRE(args && n > 0, "xggm_optim_multi: no spans");
+    const int rule = args[0].rule;
+    XGGM_REQUIRE(rule >= XGGM_RULE_BERTADAM && rule <= XGGM_RULE_RMSPROP, "xggm_optim_multi: unknown rule %d", rule);
+    const bool mom0 = args[0].momentum == 0.0;
+    int inst = R_BERT;
+    if (rule == XGGM_RULE_ADAM || rule == XGGM_RULE_ADAMW) inst = R_ADAM;
+    else if (rule == XGGM_RULE_ADAMAX) inst = R_ADAMAX;
+    else if (rule == XGGM_RULE_SGD) inst = mom0 ? R_SGD0 : R_SGDM;
+    else if (rule == XGGM_RULE_RMSPROP) inst = mom0 ? R_RMS0 : R_RMSM;
+    for (int i0 = 0; i0 < n; i0 += ADAM_MULTI) {
+        OptimMulti om;
+        om.n = std::min(ADAM_MULTI, n - i0);
+        int nblk = 0;
+        for (int i = 0; i < om.n; ++i) {
+            const xggm_optim_args& x = args[i0 + i];
+            if (int e = adam_args_of(&x.a, om.a[i])) return e;
+            XGGM_REQUIRE(x.rule == rule && (x.momentum == 0.0) == mom0 && x.a.g_bf16 == args[0].a.g_bf16,
+                         "xggm_optim_multi: the spans of one call share the rule, the gradient type and whether momentum is zero");
+            RuleArgs& r = om.r[i];
+            r = RuleArgs();
+            if (inst != R_BERT) {
+                XGGM_REQUIRE(!x.a.shadow8, "xggm_optim_multi: the e4m3 weight copy is written by the BertAdam rule only");
+                XGGM_REQUIRE(x.step_scalars || !(inst == R_ADAM || inst == R_ADAMAX || inst == R_SGDM),
+                             "xggm_optim_multi: rule %d needs step_scalars (xggm_sched_step_ex)", rule);
+                r.hs = x.step_scalars;
+                r.decoupled = rule == XGGM_RULE_ADAMW;
+                r.mom = (float)x.momentum;
+                r.nesterov = x.nesterov != 0;
+                r.omd = (float)(1.0 - x.dampening);
+                if (inst == R_ADAM || inst == R_ADAMAX) {
+                    XGGM_REQUIRE(x.b1 >= 0.0 && x.b1 < 1.0 && x.b2 >= 0.0 && x.b2 < 1.0, "xggm_optim_multi: betas outside [0, 1)");
+                    om.a[i].b1 = (float)x.b1;
+                    om.a[i].b2 = (float)x.b2;
+                    r.omb1 = (float)(1.0 - x.b1);
+                    r.omb2 = (float)(1.0 - x.b2);
+                } else if (inst == R_RMS0 || inst == R_RMSM) {
+                    om.a[i].b2 = (float)x.alpha;
+                    r.omb2 = (float)(1.0 - x.alpha);
+                }
+            }
+            om.blk0[i] = nblk;
+            nblk += grid1d(om.a[i].n / 8 + 1, 65536);
+        }
+        om.blk0[om.n] = nblk;
+        const bool gb = args[0].a.g_bf16 != 0;
+#define OPTIM_LAUNCH(R)                                                                                              \
+    case R:                                                                                                          \
+        if (gb) hipLaunchKernelGGL((optim_multi_kernel<2, true, true, R>), dim3(nblk), dim3(NT), 0, st, om);        \
+        else hipLaunchKernelGGL((optim_multi_kernel<2, true, false, R>), dim3(nblk), dim3(NT), 0, st, om);          \
+        break;
+        switch (inst) {
+            OPTIM_LAUNCH(R_ADAM)
+            OPTIM_LAUNCH(R_ADAMAX)
+            OPTIM_LAUNCH(R_SGD0)
+            OPTIM_LAUNCH(R_SGDM)
+            OPTIM_LAUNCH(R_RMS0)
+            OPTIM_LAUNCH(R_RMSM)
+            default: {  // XGGM_RULE_BERTADAM: xggm_bertadam_multi's kernel
+                AdamMulti am;
+                am.n = om.n;
+                for (int i = 0; i < om.n; ++i) am.a[i] = om.a[i];
+                for (int i = 0; i <= om.n; ++i) am.blk0[i] = om.blk0[i];
+                if (gb) hipLaunchKernelGGL((bertadam_multi_kernel<2, true, true>), dim3(nblk), dim3(NT), 0, st, am);
+                else hipLaunchKernelGGL((bertadam_multi_kernel<2, true, false>), dim3(nblk), dim3(NT), 0, st, am);
+            }
+        }
+#undef OPTIM_LAUNCH
+        if (int e = xggm_check_launch("xggm_optim_multi")) return e;
+    }
+    return XGGM_OK;
+}
+
 extern "C" int xggm_sqnorm_bf16(const void* g, int64_t n, float* out, float* ws, hipStream_t st) {
     XGGM_REQUIRE(g && out && ws && n > 0, "xggm_sqnorm_bf16: bad arguments");
     XGGM_REQUIRE(reinterpret_cast<uintptr_t>(g) % 16 == 0, "xggm_sqnorm_bf16: pointer must be 16-byte aligned");
@@ -850,6 +1058,29 @@ extern "C" int xggm_sched_step_multi(int64_t* steps, float* lr_scale, const int*
     }
     hipLaunchKernelGGL(sched_multi_kernel, dim3(1), dim3(64), 0, st, steps, lr_scale, a);
     return xggm_check_launch("xggm_sched_step_multi");
+}
+
+extern "C" int xggm_sched_step_ex(int64_t* steps, float* lr_scale, float* step_scalars, const xggm_sched_entry* entries, int n,
+                                  hipStream_t st) {
+    XGGM_REQUIRE(steps && lr_scale && entries && n > 0 && n <= MAX_SCHED,
+                 "xggm_sched_step_ex: bad arguments (n = %d, at most %d counters per call)", n, MAX_SCHED);
+    SchedExArgs a;
+    a.n = n;
+    for (int i = 0; i < n; ++i) {
+        const xggm_sched_entry& e = entries[i];
+        XGGM_REQUIRE(e.index >= 0, "xggm_sched_step_ex: negative index");
+        XGGM_REQUIRE(e.kind >= XGGM_SCHED_LINEAR && e.kind <= XGGM_SCHED_CONSTANT, "xggm_sched_step_ex: unknown schedule kind %d", e.kind);
+        XGGM_REQUIRE(e.b1 >= 0.0 && e.b1 < 1.0 && e.b2 >= 0.0 && e.b2 < 1.0, "xggm_sched_step_ex: betas outside [0, 1)");
+        for (int j = 0; j < i; ++j) XGGM_REQUIRE(entries[j].index != e.index, "xggm_sched_step_ex: counter %d listed twice", e.index);
+        a.index[i] = e.index;
+        a.kind[i] = e.kind;
+        a.t_total[i] = e.t_total;
+        a.warmup[i] = e.warmup;
+        a.b1[i] = e.b1;
+        a.b2[i] = e.b2;
+    }
+    hipLaunchKernelGGL(sched_ex_kernel, dim3(1), dim3(64), 0, st, steps, lr_scale, step_scalars, a);
+    return xggm_check_launch("xggm_sched_step_ex");
 }
 
 namespace {

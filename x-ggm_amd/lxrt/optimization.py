@@ -126,7 +126,10 @@ def _tail_of(arena, tail):
     sched = rng = None
     if tail is not None:
         optim, rt = tail
-        entries = [(gi, pg['t_total'], pg['warmup']) for _, pg, gi in optim._todo(arena)]
+        require_arena_aware(optim)
+        # the optimiser says what its schedule step is; None: the norm's finishing launch cannot carry it (a non-linear
+        # schedule kind, or a rule with bias corrections) -- ``sched_done`` stays False and ``step()`` makes its own launch
+        entries = optim._tail_entries(arena)
         if entries and len(entries) <= ops.CLIP_NORM_MAX_SCHED:
             sched = (arena.steps, arena.lr_scale, entries)
             arena.sched_done = True
@@ -172,7 +175,176 @@ def clip_norm_finish(arena, max_norm, tail=None):
     return total.view(())
 
 
-class BertAdam(Optimizer):
+def require_arena_aware(optim):
+    """A ``torch.optim`` class over arena-managed parameters looks healthy and trains nothing: it updates the fp32
+    masters while every product reads the bf16 shadow only the fused update writes, and it never sees the clip scale
+    (``clip_grad_norm_`` applies it inside the fused update)."""
+    if not isinstance(optim, ArenaOptimizer):
+        raise TypeError("%s is not arena-aware: over this package's models it would update the fp32 masters only (stale "
+                        "bf16 weights, unclipped gradients).  Use the class of the same name from xggm_amd.optim (Adam, "
+                        "AdamW, Adamax, SGD, RMSprop) or xggm_amd.lxrt.optimization.BertAdam"
+                        % (type(optim).__module__ + "." + type(optim).__name__))
+
+
+class ArenaOptimizer(Optimizer):
+    """What every optimiser of this package shares: state in the model's flat arena, one device-resident step counter
+    per arena group, learning rates in a device table, ONE fused launch for all spans of a pass.  A subclass gives the
+    rule: its kernel hyper-parameters, its schedule step and its state layout."""
+
+    @property
+    def _name(self):
+        return type(self).__name__
+
+    # ---- hooks
+    def _state_into_arena(self, arena, state):
+        raise NotImplementedError
+
+    def _check_arena(self, arena):
+        """refuse arena modes the rule does not support"""
+
+    def _kernel_hyper(self, pg):
+        """(b1, b2, eps, weight_decay) of ``xggm_adam_args`` for this param_group"""
+        raise NotImplementedError
+
+    def _tail_entries(self, arena):
+        """[(counter, t_total, warmup)] when the schedule step of the coming ``step()`` can ride on the norm's finishing
+        launch (warmup_linear semantics of ``xggm_pass_tail``), else None"""
+        return None
+
+    def _sched_launch(self, arena, todo):
+        """the stand-alone schedule step: counters, ``lr_scale`` and whatever the rule needs per step"""
+        raise NotImplementedError
+
+    def _launch(self, arena, jobs):
+        """``jobs``: [(positional arguments of ops.bertadam_ex, its keyword arguments, param_group)]"""
+        raise NotImplementedError
+
+    # ---- shared plumbing
+    def _arena(self):
+        arena = _arena_of_params(p for pg in self.param_groups for p in pg['params'])
+        pending = getattr(self, "_pending_state", None)
+        if arena is not None and pending is not None:
+            self._pending_state = None
+            self._state_into_arena(arena, pending)
+        return arena
+
+    def _hyper_of_group(self, arena, gname):
+        """the optimiser param_group that holds ALL parameters of arena group ``gname`` (one contiguous range, one
+        launch, one set of hyper-parameters).  A param_groups split that cuts through an arena group -- the usual
+        BERT "no decay for bias / LayerNorm" grouping would -- cannot be honoured by a flat update and is refused
+        instead of silently applying the first parameter's settings to the whole range."""
+        cache = getattr(self, "_group_pg", None)
+        if cache is None:
+            cache = self._group_pg = {}
+        if gname not in cache:
+            owner = {}
+            for i, pg in enumerate(self.param_groups):
+                for p in pg['params']:
+                    owner[id(p)] = i
+            idx = {owner.get(id(p)) for p in arena.groups[gname].params}
+            if len(idx) > 1:
+                raise ValueError("%s: the parameters of arena group '%s' are spread over optimiser param_groups %s; "
+                                 "a group is updated as one range with one lr / weight_decay / schedule -- keep its "
+                                 "parameters in one param_group (vqa.vqacpv2.make_optimizer does)"
+                                 % (self._name, gname, sorted(idx, key=str)))
+            cache[gname] = idx.pop()
+        i = cache[gname]
+        return None if i is None else self.param_groups[i]
+
+    def sync_hyper(self):
+        """push ``param_groups[i]['lr']`` to the device table the update kernels read: call after editing a learning
+        rate between replays of a captured pass (an eager ``step()`` does it by itself)"""
+        arena = self._arena()
+        if arena is None:
+            return
+        for g in arena.groups:
+            pg = self._hyper_of_group(arena, g)
+            gi = arena.group_index[g]
+            if pg is not None and arena.lr_host[gi] != float(pg['lr']):
+                if torch.cuda.is_current_stream_capturing():
+                    raise RuntimeError("%s: a learning rate changed during graph capture; call sync_hyper() before" % self._name)
+                arena.lr_table[gi] = float(pg['lr'])
+                arena.lr_host[gi] = float(pg['lr'])
+
+    def zero_grad(self, set_to_none=True):
+        super().zero_grad(set_to_none=True)
+        arena = self._arena()
+        if arena is not None:
+            arena.begin_pass()
+
+    def _todo(self, arena):
+        """(group, its param_group, its index) for every arena group that received gradients in this pass"""
+        self._check_arena(arena)
+        todo = []
+        for g in arena.active_groups():
+            G = arena.groups[g]
+            pg = self._hyper_of_group(arena, g)
+            if pg is None:
+                continue  # parameters not handed to this optimiser
+            if any(p.grad is None for p in G.params):
+                raise RuntimeError("arena group '%s' received gradients for only part of its parameters" % g)
+            todo.append((G, pg, arena.group_index[g]))
+        return todo
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = closure() if closure is not None else None
+        arena = self._arena()
+        if arena is None:
+            raise RuntimeError("%s.step: parameters are not arena-managed; run a forward/backward first" % self._name)
+        sq = arena.sqnorm if arena.pending_clip is not None else None
+        max_norm = arena.pending_clip if arena.pending_clip is not None else 0.0
+        todo = self._todo(arena)
+        if todo and not getattr(arena, "sched_done", False):  # schedule values and step counters of all groups: one launch
+            self._sched_launch(arena, todo)
+        arena.sched_done = False  # (True: clip_grad_norm_'s finishing launch has taken the step along)
+        if not torch.cuda.is_current_stream_capturing():
+            self.sync_hyper()  # the kernels read lr from a device table: edits of param_groups survive graph replay
+        elif any(arena.lr_host[gi] is None for _, _, gi in todo):
+            raise RuntimeError("%s.step is being captured before any eager step: run one pass eagerly first "
+                               "(the learning rates are uploaded to the device outside of captures)" % self._name)
+        f8 = arena.fp8
+        gbuf = arena.wire if arena.wire is not None else arena.grads  # bf16 wire arena: the update reads it directly
+        gscale = arena.grad_scale if arena.wire is not None else 1.0     # ... and holds sums over the ranks
+        z = arena.zero1
+        jobs = []  # every span of this step: ONE launch (xggm_bertadam_multi / xggm_optim_multi)
+        if f8 is not None:
+            # new scales of the weight operands of every group, before the update rewrites their e4m3 copies
+            f8.update_weight_scales_of([G.name for G, _, _ in todo])
+        for G, pg, gi in todo:
+            scale_t = arena.lr_scale[gi:gi + 1]
+            hyper = tuple(self._kernel_hyper(pg))
+            if z is not None:
+                # sharded update: this rank's slice of every matrix run of the group + the whole vector region.  With the
+                # fp8 forward a slice also writes ITS part of the e4m3 weight copies (slices are whole 256-element chunks
+                # of the scale-id table) under scales derived from maxima that ShardedUpdate.exchange_norm has just
+                # MAX-reduced over the ranks -- identical tables on every rank; gather() brings the other slices over
+                w8g = f8.adam_w8(G.name) if f8 is not None else None
+                pieces = [z.own(r) + (True,) for r in z.runs if r[0] >= G.start and r[1] <= G.vec_start]
+                pieces.append((G.vec_start, G.end, False))
+                for a, b, is_mat in pieces:
+                    if b > a:
+                        sl = slice(a, b)
+                        w8 = ((f8.shadow8[sl],) + w8g) if (w8g is not None and is_mat) else None
+                        jobs.append(((arena.params[sl], gbuf[sl], arena.m[sl], arena.v[sl], arena.shadow[sl], sq, max_norm,
+                                      pg['lr'], scale_t) + hyper,
+                                     dict(lr_dev=arena.lr_table[gi:gi + 1], w8=w8, elem0=a, g_scale=gscale), pg, gi))
+                continue
+            sl = slice(G.start, G.end)
+            w8 = f8.adam_w8(G.name) if f8 is not None else None
+            if w8 is not None:
+                # fp8 forward: this group's weight operands get their e4m3 copies from the same pass over p, with
+                # the scales the delayed update derives from the maxima earlier steps recorded
+                w8 = (f8.shadow8[sl],) + w8
+            jobs.append(((arena.params[sl], gbuf[sl], arena.m[sl], arena.v[sl],
+                          None if arena.shadow is None else arena.shadow[sl], sq, max_norm, pg['lr'], scale_t) + hyper,
+                         dict(lr_dev=arena.lr_table[gi:gi + 1], w8=w8, elem0=G.start, g_scale=gscale), pg, gi))
+        self._launch(arena, jobs)
+        arena.pending_clip = None
+        return loss
+
+
+class BertAdam(ArenaOptimizer):
     """ref: src/lxrt/optimization.py:58-203 (no bias correction; decoupled weight decay on
     every parameter; gradient clipping is done outside, as LXMERT does)."""
 
@@ -182,8 +354,6 @@ class BertAdam(Optimizer):
             raise ValueError("Invalid learning rate: {} - should be >= 0.0".format(lr))
         if schedule not in SCHEDULES:
             raise ValueError("Invalid schedule parameter: {}".format(schedule))
-        if schedule != 'warmup_linear' and t_total != -1:
-            raise NotImplementedError("only warmup_linear (the reference trainers' schedule) runs on the device")
         if not 0.0 <= warmup < 1.0 and not warmup == -1:
             raise ValueError("Invalid warmup: {} - should be in [0.0, 1.0[ or -1".format(warmup))
         if not 0.0 <= b1 < 1.0:
@@ -198,14 +368,6 @@ class BertAdam(Optimizer):
 
     # ---- checkpointing: the reference layout (src/lxrt/optimization.py:147-155 keeps per-parameter
     # state['step'], state['next_m'], state['next_v']), read from / written into the flat arena
-    def _arena(self):
-        arena = _arena_of_params(p for pg in self.param_groups for p in pg['params'])
-        pending = getattr(self, "_pending_state", None)
-        if arena is not None and pending is not None:
-            self._pending_state = None
-            self._state_into_arena(arena, pending)
-        return arena
-
     def state_dict(self):
         sd = super().state_dict()
         arena = self._arena()
@@ -256,43 +418,6 @@ class BertAdam(Optimizer):
         for gname, s in step_of.items():
             arena.steps[arena.group_index[gname]] = s
 
-    def _hyper_of_group(self, arena, gname):
-        """the optimiser param_group that holds ALL parameters of arena group ``gname`` (one contiguous range, one
-        launch, one set of hyper-parameters).  A param_groups split that cuts through an arena group -- the usual
-        BERT "no decay for bias / LayerNorm" grouping would -- cannot be honoured by a flat update and is refused
-        instead of silently applying the first parameter's settings to the whole range."""
-        cache = getattr(self, "_group_pg", None)
-        if cache is None:
-            cache = self._group_pg = {}
-        if gname not in cache:
-            owner = {}
-            for i, pg in enumerate(self.param_groups):
-                for p in pg['params']:
-                    owner[id(p)] = i
-            idx = {owner.get(id(p)) for p in arena.groups[gname].params}
-            if len(idx) > 1:
-                raise ValueError("BertAdam: the parameters of arena group '%s' are spread over optimiser param_groups %s; "
-                                 "a group is updated as one range with one lr / weight_decay / schedule -- keep its "
-                                 "parameters in one param_group (vqa.vqacpv2.make_optimizer does)" % (gname, sorted(idx, key=str)))
-            cache[gname] = idx.pop()
-        i = cache[gname]
-        return None if i is None else self.param_groups[i]
-
-    def sync_hyper(self):
-        """push ``param_groups[i]['lr']`` to the device table the update kernels read: call after editing a learning
-        rate between replays of a captured pass (an eager ``step()`` does it by itself)"""
-        arena = self._arena()
-        if arena is None:
-            return
-        for g in arena.groups:
-            pg = self._hyper_of_group(arena, g)
-            gi = arena.group_index[g]
-            if pg is not None and arena.lr_host[gi] != float(pg['lr']):
-                if torch.cuda.is_current_stream_capturing():
-                    raise RuntimeError("BertAdam: a learning rate changed during graph capture; call sync_hyper() before")
-                arena.lr_table[gi] = float(pg['lr'])
-                arena.lr_host[gi] = float(pg['lr'])
-
     def get_lr(self):
         """ref :100-114: the scheduled learning rate of every parameter, in param_groups order; ``[0]`` while some
         parameter has never been stepped (the reference's empty ``state[p]``)."""
@@ -315,78 +440,26 @@ class BertAdam(Optimizer):
                     lr.append(pg['lr'])
         return lr
 
-    def zero_grad(self, set_to_none=True):
-        super().zero_grad(set_to_none=True)
-        arena = self._arena()
-        if arena is not None:
-            arena.begin_pass()
+    # ---- the rule
+    def _kernel_hyper(self, pg):
+        return pg['b1'], pg['b2'], pg['e'], pg['weight_decay']
 
-    def _todo(self, arena):
-        """(group, its param_group, its index) for every arena group that received gradients in this pass"""
-        todo = []
-        for g in arena.active_groups():
-            G = arena.groups[g]
-            pg = self._hyper_of_group(arena, g)
-            if pg is None:
-                continue  # parameters not handed to this optimiser
-            if any(p.grad is None for p in G.params):
-                raise RuntimeError("arena group '%s' received gradients for only part of its parameters" % g)
-            todo.append((G, pg, arena.group_index[g]))
-        return todo
+    @staticmethod
+    def _linear(pg):
+        return pg['schedule'] == 'warmup_linear' or pg['t_total'] <= 0  # (no t_total: every kind is the constant 1)
 
-    @torch.no_grad()
-    def step(self, closure=None):
-        loss = closure() if closure is not None else None
-        arena = self._arena()
-        if arena is None:
-            raise RuntimeError("BertAdam.step: parameters are not arena-managed; run a forward/backward first")
-        sq = arena.sqnorm if arena.pending_clip is not None else None
-        max_norm = arena.pending_clip if arena.pending_clip is not None else 0.0
+    def _tail_entries(self, arena):
         todo = self._todo(arena)
-        if todo and not getattr(arena, "sched_done", False):  # schedule values and step counters of all groups: one launch
+        if not all(self._linear(pg) for _, pg, _ in todo):
+            return None
+        return [(gi, pg['t_total'], pg['warmup']) for _, pg, gi in todo]
+
+    def _sched_launch(self, arena, todo):
+        if all(self._linear(pg) for _, pg, _ in todo):
             ops.sched_step_multi(arena.steps, arena.lr_scale, [(gi, pg['t_total'], pg['warmup']) for _, pg, gi in todo])
-        arena.sched_done = False  # (True: clip_grad_norm_'s finishing launch has taken the step along)
-        if not torch.cuda.is_current_stream_capturing():
-            self.sync_hyper()  # the kernels read lr from a device table: edits of param_groups survive graph replay
-        elif any(arena.lr_host[gi] is None for _, _, gi in todo):
-            raise RuntimeError("BertAdam.step is being captured before any eager step: run one pass eagerly first "
-                               "(the learning rates are uploaded to the device outside of captures)")
-        f8 = arena.fp8
-        gbuf = arena.wire if arena.wire is not None else arena.grads  # bf16 wire arena: the update reads it directly
-        gscale = arena.grad_scale if arena.wire is not None else 1.0     # ... and holds sums over the ranks
-        z = arena.zero1
-        jobs = []  # every span of this step: ONE launch (xggm_bertadam_multi)
-        if f8 is not None:
-            # new scales of the weight operands of every group, before the update rewrites their e4m3 copies
-            f8.update_weight_scales_of([G.name for G, _, _ in todo])
-        for G, pg, gi in todo:
-            scale_t = arena.lr_scale[gi:gi + 1]
-            if z is not None:
-                # sharded update: this rank's slice of every matrix run of the group + the whole vector region.  With the
-                # fp8 forward a slice also writes ITS part of the e4m3 weight copies (slices are whole 256-element chunks
-                # of the scale-id table) under scales derived from maxima that ShardedUpdate.exchange_norm has just
-                # MAX-reduced over the ranks -- identical tables on every rank; gather() brings the other slices over
-                w8g = f8.adam_w8(G.name) if f8 is not None else None
-                pieces = [z.own(r) + (True,) for r in z.runs if r[0] >= G.start and r[1] <= G.vec_start]
-                pieces.append((G.vec_start, G.end, False))
-                for a, b, is_mat in pieces:
-                    if b > a:
-                        sl = slice(a, b)
-                        w8 = ((f8.shadow8[sl],) + w8g) if (w8g is not None and is_mat) else None
-                        jobs.append(((arena.params[sl], gbuf[sl], arena.m[sl], arena.v[sl], arena.shadow[sl], sq, max_norm,
-                                      pg['lr'], scale_t, pg['b1'], pg['b2'], pg['e'], pg['weight_decay']),
-                                     dict(lr_dev=arena.lr_table[gi:gi + 1], w8=w8, elem0=a, g_scale=gscale)))
-                continue
-            sl = slice(G.start, G.end)
-            w8 = f8.adam_w8(G.name) if f8 is not None else None
-            if w8 is not None:
-                # fp8 forward: this group's weight operands get their e4m3 copies from the same pass over p, with
-                # the scales the delayed update derives from the maxima earlier steps recorded
-                w8 = (f8.shadow8[sl],) + w8
-            jobs.append(((arena.params[sl], gbuf[sl], arena.m[sl], arena.v[sl],
-                          None if arena.shadow is None else arena.shadow[sl], sq, max_norm, pg['lr'], scale_t,
-                          pg['b1'], pg['b2'], pg['e'], pg['weight_decay']),
-                         dict(lr_dev=arena.lr_table[gi:gi + 1], w8=w8, elem0=G.start, g_scale=gscale)))
-        ops.bertadam_multi(jobs)
-        arena.pending_clip = None
-        return loss
+        else:  # warmup_cosine / warmup_constant (ref :27-39): a schedule kind per entry
+            ops.sched_step_ex(arena.steps, arena.lr_scale, None,
+                              [(gi, pg['t_total'], pg['warmup'], pg['schedule'], 0.0, 0.0) for _, pg, gi in todo])
+
+    def _launch(self, arena, jobs):
+        ops.bertadam_multi([(a, kw) for a, kw, _, _ in jobs])

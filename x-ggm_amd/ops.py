@@ -1524,6 +1524,61 @@ def bertadam_multi(jobs):
             call("xggm_bertadam_multi", _ct.cast(arr, _ct.c_void_p), len(chunk), stream())
 
 
+RULES = {"bertadam": 0, "adam": 1, "adamw": 2, "adamax": 3, "sgd": 4, "rmsprop": 5}  # XGGM_RULE_* (include/xggm.h)
+SCHED_KINDS = {"warmup_linear": 0, "warmup_cosine": 1, "warmup_constant": 2}            # XGGM_SCHED_*
+
+
+class OptimArgs(_ct.Structure):
+    """mirror of ``xggm_optim_args`` (include/xggm.h)"""
+    _fields_ = [("a", AdamArgs), ("rule", _ct.c_int), ("step_scalars", _ct.c_void_p), ("b1", _ct.c_double),
+                ("b2", _ct.c_double), ("momentum", _ct.c_double), ("dampening", _ct.c_double), ("alpha", _ct.c_double),
+                ("nesterov", _ct.c_int)]
+
+
+class SchedEntry(_ct.Structure):
+    """mirror of ``xggm_sched_entry`` (include/xggm.h)"""
+    _fields_ = [("index", _ct.c_int), ("kind", _ct.c_int), ("t_total", _ct.c_int64), ("warmup", _ct.c_double),
+                ("b1", _ct.c_double), ("b2", _ct.c_double)]
+
+
+def optim_multi(rule, jobs):
+    """the fused update under a torch.optim rule (src/param.py:9-31): ``rule`` a key of ``RULES``; ``jobs``: (argument
+    tuple of ``bertadam_ex``, dict of its keyword arguments, dict of the rule's: step_scalars (3 device floats of the span's
+    group, ``sched_step_ex``), b1, b2, momentum, dampening, alpha, nesterov) per span.  ONE launch per 8 spans
+    (xggm_optim_multi), in chunks by gradient type."""
+    if not jobs:
+        return
+    structs = []
+    for a, kw, r in jobs:
+        hs = r.get("step_scalars")
+        if hs is not None:
+            _c(hs, F32)
+            assert hs.numel() >= 3
+        structs.append(OptimArgs(_adam_args(*a, **kw), RULES[rule], ptr(hs), float(r.get("b1", 0.0)), float(r.get("b2", 0.0)),
+                                 float(r.get("momentum", 0.0)), float(r.get("dampening", 0.0)), float(r.get("alpha", 0.0)),
+                                 int(bool(r.get("nesterov", False)))))
+    for bf in (0, 1):
+        chunk = [x for x in structs if x.a.g_bf16 == bf]
+        if chunk:
+            arr = (OptimArgs * len(chunk))(*chunk)
+            call("xggm_optim_multi", _ct.cast(arr, _ct.c_void_p), len(chunk), stream())
+
+
+def sched_step_ex(steps, lr_scale, step_scalars, entries):
+    """``entries``: [(index, t_total, warmup, kind, b1, b2)] with ``kind`` a key of ``SCHED_KINDS``: schedule value and
+    counter as ``sched_step_multi``, evaluated in double, plus -- with ``step_scalars`` (fp32 [groups * 4]) -- the bias
+    corrections {1 / (1 - b1^t), 1 / sqrt(1 - b2^t), first step} of the step, in double on the device"""
+    _c(steps, torch.int64), _c(lr_scale, F32)
+    if step_scalars is not None:
+        _c(step_scalars, F32)
+        assert step_scalars.numel() >= 4 * steps.numel()
+    for i in range(0, len(entries), 16):
+        ch = entries[i:i + 16]
+        arr = (SchedEntry * len(ch))(*[SchedEntry(int(e[0]), SCHED_KINDS[e[3]], int(e[1]), float(e[2]), float(e[4]), float(e[5]))
+                                       for e in ch])
+        call("xggm_sched_step_ex", ptr(steps), ptr(lr_scale), ptr(step_scalars), _ct.cast(arr, _ct.c_void_p), len(ch), stream())
+
+
 def bertadam_ex(p, g, m, v, shadow, sqn, max_norm, lr, lr_scale, b1, b2, eps, wd, lr_dev=None, w8=None, elem0=0, g_scale=1.0):
     """the update with device-resident lr (``lr_dev``), bf16 gradients (``g.dtype``) and/or the e4m3 weight copy
     ``w8`` = (shadow8 slice, id table, qscale table, amax table); ``elem0``: arena offset of p[0]."""

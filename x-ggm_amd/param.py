@@ -4,9 +4,23 @@ reference parses ``sys.argv`` at import time; here ``args`` is a plain namespace
 import argparse
 
 
+def get_optimizer(optim):
+    """the reference's ``--optim`` names (src/param.py:9-31) bound to this package's arena-aware classes of the same
+    names (``xggm_amd.optim``: the ``torch.optim`` rules on the fused device update); ``'bert'`` stays the string the
+    trainers turn into ``BertAdam`` (src/vqa/vqacpv2.py:113-128)."""
+    names = {'rms': 'RMSprop', 'adam': 'Adam', 'adamw': 'AdamW', 'adamax': 'Adamax', 'sgd': 'SGD'}
+    if optim in names:
+        from . import optim as xo  # (imports the compiled library: only when an optimiser is asked for)
+        return getattr(xo, names[optim])
+    if 'bert' in optim:
+        return 'bert'  # bound later, as in the reference
+    assert False, "Please add your optimizer %s in the list." % optim
+
+
 def build_parser():
     p = argparse.ArgumentParser()
     p.add_argument("--bs", dest="batch_size", type=int, default=8)
+    p.add_argument("--optim", default="bert")
     p.add_argument("--lr", type=float, default=1e-5)
     p.add_argument("--epochs", type=int, default=4)
     p.add_argument("--seed", type=int, default=9595)
@@ -27,7 +41,8 @@ def build_parser():
 def parse_args(argv=None):
     global args
     args = build_parser().parse_args(argv or [])
+    args.optimizer = get_optimizer(args.optim)  # src/param.py:121
     return args
 
 
-args = build_parser().parse_args([])
+args = parse_args([])

@@ -12,7 +12,7 @@ import torch
 import torch.nn as nn
 
 from .. import functional as XF
-from ..lxrt.optimization import clip_grad_norm_
+from ..lxrt.optimization import clip_grad_norm_, require_arena_aware
 from ..runtime import runtime_of
 
 
@@ -192,6 +192,7 @@ def clip_and_step(model, optim, clip=5.0, advance=False):
     """nn.utils.clip_grad_norm_(params, 5.) + optim.step() + optim.zero_grad()
     (src/vqa/vqacpv2.py:175-177), fused: one norm reduction, one update pass.  ``advance``: also end the pass
     (Runtime.advance: new dropout masks / noise for the next one) -- the RNG step then rides on the norm's last launch."""
+    require_arena_aware(optim)  # a torch.optim class here would train nothing, silently (TypeError)
     rt = runtime_of(model)
     total = clip_grad_norm_(model.parameters(), clip, tail=(optim, rt if advance else None))
     optim.step()
@@ -294,9 +295,16 @@ def train_iteration(model, optim, bce_loss, batch, delta=5, sigma=1.0, order="vq
     return out
 
 
-def make_optimizer(model, lr, t_total, warmup=0.1):
+def make_optimizer(model, lr, t_total, warmup=0.1, optim='bert'):
     """the two parameter groups of src/vqa/vqacpv2.py:113-128: heads/generator at 4*lr,
-    encoder at lr; BertAdam(warmup=0.1, t_total=2*iters)."""
+    encoder at lr; BertAdam(warmup=0.1, t_total=2*iters).  ``optim``: another ``--optim`` name of the reference
+    (rms, adam, adamw, adamax, sgd) or what ``param.get_optimizer`` returned for it builds the else-branch
+    (src/vqa/vqacpv2.py:141): one group, all parameters, ``lr`` -- the arena-aware class of ``xggm_amd.optim``."""
+    if isinstance(optim, str):
+        from ..param import get_optimizer
+        optim = get_optimizer(optim)
+    if optim != 'bert':
+        return optim(model.parameters(), lr)
     from ..lxrt.optimization import BertAdam
     lxrt_ids = set(map(id, model.lxrt_encoder.parameters()))
     base_params = [p for p in model.parameters() if id(p) not in lxrt_ids]
