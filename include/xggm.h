@@ -657,6 +657,27 @@ typedef struct xggm_optim_args {
  * (src/param.py:9-31, src/vqa/vqacpv2.py:141) */
 int xggm_optim_multi(const xggm_optim_args* args, int n, xggm_stream_t stream);
 
+/* Split param_groups: the two multi-span updates with lr and weight decay PER TENSOR, for an optimiser whose param_groups cut
+ * through a contiguous range (the BERT "no decay for bias / LayerNorm" grouping, layer-wise lr decay, parameters left out).
+ *   ids    DEVICE, one uint8 per 8 elements of the arena: element i of a span reads ids[(elem0 + i) >> 3].  Tensors start on
+ *          multiples of 8 elements, so 8 elements never mix two tensors: 1/8 byte of map per parameter.
+ *   table  DEVICE, n_table pairs {lr, weight_decay}, 8-byte aligned; entry 0 is not read.
+ * Per element: lr = table[id].lr * *lr_scale and weight_decay = table[id].weight_decay take the place of the span's lr /
+ * lr_dev / weight_decay (which are not read); the schedule value, the clip scale, g_scale, the rule's arguments, the bf16
+ * shadow and the e4m3 copy are the span's, and the arithmetic is xggm_bertadam_multi's / xggm_optim_multi's bit for bit.
+ * Id 0 (and any id >= n_table) means "not in this optimiser": p, m, v, the shadow and the e4m3 copy of such an element are
+ * not written.  Alignment gaps hold zeros and may carry any id.  Checked before any launch: map, ids and table non-NULL,
+ * 1 <= n_table <= 256, every span's elem0 a multiple of 8 and [elem0, elem0 + n) inside the n_ids * 8 elements the map covers.
+ * One launch per 8 spans, no atomics beyond the e4m3 maxima, no allocation, no synchronisation. */
+typedef struct xggm_hyper_map {
+    const uint8_t* ids;
+    int64_t n_ids;
+    const float* table;
+    int n_table;
+} xggm_hyper_map;
+int xggm_bertadam_multi_mapped(const xggm_adam_args* args, int n, const xggm_hyper_map* map, xggm_stream_t stream);
+int xggm_optim_multi_mapped(const xggm_optim_args* args, int n, const xggm_hyper_map* map, xggm_stream_t stream);
+
 /* xggm_sched_step_multi with a schedule kind per entry (src/lxrt/optimization.py:27-48: warmup_cosine, warmup_constant,
  * warmup_linear; the xggm_sched_step* calls keep meaning warmup_linear) and the per-step scalars of xggm_optim_multi:
  * for entry i with k = index, s = steps[k]: lr_scale[k] = kind(s / t_total, warmup) in double (1 when t_total <= 0),

@@ -92,6 +92,33 @@ def layout(named, group_of, model=None):
     return order, groups, info, _align(off, ALIGN_MAT)
 
 
+HYPER_MAX_ID = 255  # ids of the hyper map are uint8; 0 = not in the optimiser
+
+
+def hyper_id_map(info, owner, total):
+    """The id map of an optimiser with split param_groups (``split_groups=True``): one uint8 per ``ALIGN`` = 8 elements of
+    the arena -- ceil(total / 8) bytes, 1/8 byte per parameter -- that the mapped update indexes by arena offset.
+    ``info``: {name: (offset, numel, ...)} as ``layout`` returns it; ``owner``: {name: id} with id = 1 + index of the
+    optimiser param_group that holds the parameter, 0 or absent for a parameter the optimiser was not given; ``total``:
+    elements of the arena.  Tensors start on multiples of 8, so an id never stands for two tensors.  The gap behind a
+    tensor (up to the next tensor's start) carries that tensor's id: gaps hold zeros, which stay zeros under every rule, and
+    with its neighbour's id a gap behaves exactly as under the unmapped update.  Plain Python / numpy: no device needed."""
+    import numpy as np
+    n_ids = (int(total) + ALIGN - 1) // ALIGN
+    ids = np.zeros(n_ids, dtype=np.uint8)
+    spans = sorted((int(v[0]), int(v[1]), n) for n, v in info.items())
+    for j, (o, k, n) in enumerate(spans):
+        i = int(owner.get(n, 0) or 0)
+        if not 0 <= i <= HYPER_MAX_ID:
+            raise ValueError("split_groups: %d optimiser param_groups, the id map holds at most %d" % (i, HYPER_MAX_ID))
+        if o % ALIGN or o + k > total or (j and o < spans[j - 1][0] + spans[j - 1][1]):
+            raise ValueError("hyper_id_map: '%s' (offset %d, %d elements) is misaligned, overlaps its neighbour or lies "
+                             "outside the %d elements of the arena" % (n, o, k, total))
+        end = spans[j + 1][0] if j + 1 < len(spans) else int(total)
+        ids[o // ALIGN:(end + ALIGN - 1) // ALIGN] = i
+    return ids
+
+
 def default_group_of(name, model=None):
     if name.startswith("lxrt_encoder."):
         tail = getattr(model, "_enc_tail_prefixes", ())

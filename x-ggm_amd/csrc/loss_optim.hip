@@ -426,15 +426,35 @@ __device__ __forceinline__ RuleStep rule_step(const AdamArgs& a, const RuleArgs&
     if (RULE == R_SGDM) s.first = r.hs[2] != 0.f;
     return s;
 }
+// the same under a hyper map (bertadam_body, MAP): lr and wd are the element's param_group's, per lane; `u` is
+// rule_step's result for the span, whose device scalars (isb2, first and -- kept in u.lr by the caller, who passes lr 1 --
+// 1 / bc1) are taken over, so they are read once per thread.  The derived values have rule_step's pinned shapes.
+template <int RULE>
+__device__ __forceinline__ RuleStep rule_step_lane(const RuleArgs& r, const RuleStep& u, float lr, float wd) {
+    RuleStep s;
+    s.lr = lr;
+    s.wd = wd;
+    if (RULE == R_BERT) return s;
+    if (r.decoupled) {
+        s.dec = __fmaf_rn(-lr, wd, 1.f);
+        s.wd = 0.f;
+    }
+    if (RULE == R_ADAM || RULE == R_ADAMAX) {
+        s.lr = __fmul_rn(lr, u.lr);
+        s.isb2 = u.isb2;
+    }
+    s.first = u.first;
+    return s;
+}
 // One element; the multiply-adds are pinned as in adam_update, so the fp32- and the bf16-gradient instantiation of a
 // rule give the same bits on the same values.  Operation order after torch/optim/{adam,adamax,sgd,rmsprop}.py
 // (_single_tensor_*); with a zero gradient and zero state a zero p stays exactly zero under every rule, and so do its
 // shadow and m; v does too except under Adamax, whose exp_inf = max(b2 u, |g| + eps) becomes eps by torch's definition.
-template <int RULE>
+template <int RULE, bool MAP = false>
 __device__ __forceinline__ void rule_update(float& p, float& m, float& v, float gk, const AdamArgs& a, const RuleArgs& r,
                                             const RuleStep& s) {
     if (RULE == R_BERT) {
-        adam_update(p, m, v, gk, a.b1, a.b2, a.eps, a.wd, s.lr);
+        adam_update(p, m, v, gk, a.b1, a.b2, a.eps, MAP ? s.wd : a.wd, s.lr);
         return;
     }
     if (r.decoupled) p = __fmul_rn(p, s.dec);
@@ -467,8 +487,20 @@ __device__ __forceinline__ void rule_update(float& p, float& m, float& v, float 
 // One float4 of each of p, g, m, v per step; UNR independent float4 quadruples per thread and
 // iteration (loads issued before any use).  g is read once and m, v, shadow are not re-read before the
 // next step: non-temporal accesses keep them from displacing the weights' bf16 shadow in L2/MALL.
-template <int UNR, bool NTMP, bool GB16, int RULE = R_BERT>
-__device__ __forceinline__ void bertadam_body(const AdamArgs& a, const int blk, const int nblk, const RuleArgs& ra = RuleArgs()) {
+//
+// MAP (split param_groups): lr and weight decay are the element's own -- hm.ids holds one id per 8 elements of the arena
+// (tensors start on multiples of 8, so a float4 never mixes two tensors; a wave does, in the vector region: the values are
+// per lane), hm.table {lr, weight_decay} per id.  Id 0 = not in this optimiser: nothing of the element is written (p, m,
+// v, shadow, e4m3 copy).  The span's a.lr / a.lr_dev / a.wd are not read; lr_scale, the clip scale and everything else
+// are the span's.  The map is a compile-time switch: without it the body is the code it was.
+struct HyperMap {
+    const unsigned char* ids = nullptr;
+    const float2* table = nullptr;
+    unsigned n_table = 0;
+};
+template <int UNR, bool NTMP, bool GB16, int RULE = R_BERT, bool MAP = false>
+__device__ __forceinline__ void bertadam_body(const AdamArgs& a, const int blk, const int nblk, const RuleArgs& ra = RuleArgs(),
+                                              const HyperMap& hm = HyperMap()) {
     constexpr bool USE_M = RuleTraits<RULE>::use_m, USE_V = RuleTraits<RULE>::use_v;
     float coef = 1.f;
     if (a.sqnorm) {
@@ -476,8 +508,10 @@ __device__ __forceinline__ void bertadam_body(const AdamArgs& a, const int blk, 
         coef = fminf(a.max_norm / (total + 1e-6f), 1.f);  // torch.nn.utils.clip_grad_norm_
     }
     coef *= a.g_scale;
-    const float lr = (a.lr_dev ? *a.lr_dev : a.lr) * (a.lr_scale ? *a.lr_scale : 1.f);
-    const RuleStep rs = rule_step<RULE>(a, ra, lr);
+    // MAP: the span's schedule value alone; rule_step with lr 1 then leaves 1 / bc1 in rs.lr (1 * x is x)
+    const float lr = (MAP ? 1.f : (a.lr_dev ? *a.lr_dev : a.lr)) * (a.lr_scale ? *a.lr_scale : 1.f);
+    const float lr_scale = lr;
+    const RuleStep rs = rule_step<RULE>(a, ra, MAP ? 1.f : lr);
     const int64_t n4 = a.n >> 2;
     typedef float __attribute__((ext_vector_type(4))) f4;
     typedef short __attribute__((ext_vector_type(4))) s4;
@@ -494,6 +528,15 @@ __device__ __forceinline__ void bertadam_body(const AdamArgs& a, const int blk, 
         // back when the packed bytes are stored (they sat behind the update's arithmetic before: a dependent L2 round
         // trip or two at the end of every step)
         unsigned w8id[UNR];
+        unsigned hid[UNR];  // MAP: the float4's param_group, 0 (also past the end, and for an id the table does not hold) = skip
+        if (MAP) {
+#pragma unroll
+            for (int u = 0; u < UNR; ++u) {
+                const int64_t i = i0 + u * stride;
+                const unsigned id = i < n4 ? hm.ids[(a.elem0 + 4 * i) >> 3] : 0u;
+                hid[u] = id < hm.n_table ? id : 0u;
+            }
+        }
         if (a.shadow8) {
 #pragma unroll
             for (int u = 0; u < UNR; ++u) {
@@ -504,7 +547,7 @@ __device__ __forceinline__ void bertadam_body(const AdamArgs& a, const int blk, 
 #pragma unroll
         for (int u = 0; u < UNR; ++u) {
             const int64_t i = i0 + u * stride;
-            if (i < n4) {
+            if (i < n4 && (!MAP || hid[u])) {
                 p[u] = NTMP ? __builtin_nontemporal_load(reinterpret_cast<const f4*>(a.p) + i) : reinterpret_cast<const f4*>(a.p)[i];
                 if (GB16) {
                     const s4 gb = __builtin_nontemporal_load(reinterpret_cast<const s4*>(a.g) + i);
@@ -531,15 +574,21 @@ __device__ __forceinline__ void bertadam_body(const AdamArgs& a, const int blk, 
 #pragma unroll
             for (int u = 0; u < UNR; ++u) w8q[u] = w8id[u] ? a.w8_qscale[w8id[u]] : 0.f;
         }
+        float2 hyp[UNR];
+        if (MAP) {
+#pragma unroll
+            for (int u = 0; u < UNR; ++u) hyp[u] = hid[u] ? hm.table[hid[u]] : float2{0.f, 0.f};
+        }
 #pragma unroll
         for (int u = 0; u < UNR; ++u) {
             const int64_t i = i0 + u * stride;
-            const bool on = i < n4;
+            const bool on = i < n4 && (!MAP || hid[u]);
             if (on) {
+                const RuleStep rl = MAP ? rule_step_lane<RULE>(ra, rs, __fmul_rn(hyp[u].x, lr_scale), hyp[u].y) : rs;
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
                     float pk = p[u][k], mk = m[u][k], vk = v[u][k];
-                    rule_update<RULE>(pk, mk, vk, __fmul_rn(g[u][k], coef), a, ra, rs);
+                    rule_update<RULE, MAP>(pk, mk, vk, __fmul_rn(g[u][k], coef), a, ra, rl);
                     p[u][k] = pk;
                     m[u][k] = mk;
                     v[u][k] = vk;
@@ -581,9 +630,17 @@ __device__ __forceinline__ void bertadam_body(const AdamArgs& a, const int blk, 
     }
     if (blk == 0 && threadIdx.x < (a.n & 3)) {  // (ranges with an e4m3 copy are multiples of 256: no tail there)
         const int64_t i = (n4 << 2) + threadIdx.x;
+        RuleStep rl = rs;
+        if (MAP) {
+            unsigned id = hm.ids[(a.elem0 + i) >> 3];
+            if (id >= hm.n_table) id = 0u;
+            if (!id) return;
+            const float2 h = hm.table[id];
+            rl = rule_step_lane<RULE>(ra, rs, __fmul_rn(h.x, lr_scale), h.y);
+        }
         const float gi = GB16 ? __bfloat162float(reinterpret_cast<const bf16*>(a.g)[i]) : reinterpret_cast<const float*>(a.g)[i];
         float p = a.p[i], m = USE_M ? a.m[i] : 0.f, v = USE_V ? a.v[i] : 0.f;
-        rule_update<RULE>(p, m, v, __fmul_rn(gi, coef), a, ra, rs);
+        rule_update<RULE, MAP>(p, m, v, __fmul_rn(gi, coef), a, ra, rl);
         if (USE_M) a.m[i] = m;
         if (USE_V) a.v[i] = v;
         a.p[i] = p;
@@ -628,6 +685,24 @@ __global__ __launch_bounds__(NT) void optim_multi_kernel(OptimMulti om) {
     for (int k = 1; k < ADAM_MULTI; ++k)
         if (k < om.n && (int)blockIdx.x >= om.blk0[k]) j = k;
     bertadam_body<UNR, NTMP, GB16, RULE>(om.a[j], (int)blockIdx.x - om.blk0[j], om.blk0[j + 1] - om.blk0[j], om.r[j]);
+}
+
+// the two launches above under a hyper map; the map is an argument of these kernels only
+template <int UNR, bool NTMP, bool GB16>
+__global__ __launch_bounds__(NT) void bertadam_multi_mapped_kernel(AdamMulti am, HyperMap hm) {
+    int j = 0;
+#pragma unroll
+    for (int k = 1; k < ADAM_MULTI; ++k)
+        if (k < am.n && (int)blockIdx.x >= am.blk0[k]) j = k;
+    bertadam_body<UNR, NTMP, GB16, R_BERT, true>(am.a[j], (int)blockIdx.x - am.blk0[j], am.blk0[j + 1] - am.blk0[j], RuleArgs(), hm);
+}
+template <int UNR, bool NTMP, bool GB16, int RULE>
+__global__ __launch_bounds__(NT) void optim_multi_mapped_kernel(OptimMulti om, HyperMap hm) {
+    int j = 0;
+#pragma unroll
+    for (int k = 1; k < ADAM_MULTI; ++k)
+        if (k < om.n && (int)blockIdx.x >= om.blk0[k]) j = k;
+    bertadam_body<UNR, NTMP, GB16, RULE, true>(om.a[j], (int)blockIdx.x - om.blk0[j], om.blk0[j + 1] - om.blk0[j], om.r[j], hm);
 }
 
 // Delayed scaling of the e4m3 operands (weights and activation sites share one table).  Producers record the
@@ -921,10 +996,35 @@ int adam_args_of(const xggm_adam_args* x, AdamArgs& a) {
                  x->g_scale > 0.f ? x->g_scale : 1.f, x->w8_amax_slots > 1 ? x->w8_amax_slots : 1};
     return XGGM_OK;
 }
-}  // namespace
 
-extern "C" int xggm_bertadam_multi(const xggm_adam_args* args, int n, hipStream_t st) {
-    XGGM_REQUIRE(args && n > 0, "xggm_bertadam_multi: no spans");
+// the checks of the mapped entry points, all before any launch: the map covers every span, and a span starts on a whole
+// id (then no float4 of it straddles two)
+int hyper_map_of(const xggm_hyper_map* map, const char* who, HyperMap& hm) {
+    XGGM_REQUIRE(map && map->ids && map->table, "%s: the hyper map needs its id map and its {lr, weight_decay} table", who);
+    XGGM_REQUIRE(map->n_table >= 1 && map->n_table <= 256, "%s: hyper table of %d entries (1 .. 256: entry 0 + one per param_group)",
+                 who, map->n_table);
+    XGGM_REQUIRE(map->n_ids > 0 && reinterpret_cast<uintptr_t>(map->table) % 8 == 0, "%s: empty id map or misaligned hyper table", who);
+    hm.ids = map->ids;
+    hm.table = reinterpret_cast<const float2*>(map->table);
+    hm.n_table = (unsigned)map->n_table;
+    return XGGM_OK;
+}
+int span_in_map(const xggm_adam_args& x, const xggm_hyper_map* map, const char* who, int i) {
+    XGGM_REQUIRE(x.elem0 >= 0 && x.elem0 % 8 == 0, "%s: span %d: elem0 %lld must be a multiple of 8 (one id per 8 elements)", who, i,
+                 (long long)x.elem0);
+    XGGM_REQUIRE(x.n > 0 && (x.elem0 + x.n + 7) / 8 <= map->n_ids, "%s: span %d [%lld, %lld) lies outside the id map (%lld ids)", who, i,
+                 (long long)x.elem0, (long long)(x.elem0 + x.n), (long long)map->n_ids);
+    return XGGM_OK;
+}
+
+int bertadam_multi(const xggm_adam_args* args, int n, const xggm_hyper_map* map, hipStream_t st, const char* who) {
+    XGGM_REQUIRE(args && n > 0, "%s: no spans", who);
+    HyperMap hm;
+    if (map) {
+        if (int e = hyper_map_of(map, who, hm)) return e;
+        for (int i = 0; i < n; ++i)
+            if (int e = span_in_map(args[i], map, who, i)) return e;
+    }
     for (int i0 = 0; i0 < n; i0 += ADAM_MULTI) {
         AdamMulti am;
         am.n = std::min(ADAM_MULTI, n - i0);
@@ -936,17 +1036,48 @@ extern "C" int xggm_bertadam_multi(const xggm_adam_args* args, int n, hipStream_
             nblk += grid1d(am.a[i].n / 8 + 1, 65536);
         }
         am.blk0[am.n] = nblk;
-        if (args[i0].g_bf16) hipLaunchKernelGGL((bertadam_multi_kernel<2, true, true>), dim3(nblk), dim3(NT), 0, st, am);
-        else hipLaunchKernelGGL((bertadam_multi_kernel<2, true, false>), dim3(nblk), dim3(NT), 0, st, am);
-        if (int e = xggm_check_launch("xggm_bertadam_multi")) return e;
+        if (map) {
+            if (args[i0].g_bf16) hipLaunchKernelGGL((bertadam_multi_mapped_kernel<2, true, true>), dim3(nblk), dim3(NT), 0, st, am, hm);
+            else hipLaunchKernelGGL((bertadam_multi_mapped_kernel<2, true, false>), dim3(nblk), dim3(NT), 0, st, am, hm);
+        } else if (args[i0].g_bf16) {
+            hipLaunchKernelGGL((bertadam_multi_kernel<2, true, true>), dim3(nblk), dim3(NT), 0, st, am);
+        } else {
+            hipLaunchKernelGGL((bertadam_multi_kernel<2, true, false>), dim3(nblk), dim3(NT), 0, st, am);
+        }
+        if (int e = xggm_check_launch(who)) return e;
     }
     return XGGM_OK;
 }
 
+int optim_multi(const xggm_optim_args* args, int n, const xggm_hyper_map* map, hipStream_t st, const char* who);
+}  // namespace
+
+extern "C" int xggm_bertadam_multi(const xggm_adam_args* args, int n, hipStream_t st) {
+    return bertadam_multi(args, n, nullptr, st, "xggm_bertadam_multi");
+}
+extern "C" int xggm_bertadam_multi_mapped(const xggm_adam_args* args, int n, const xggm_hyper_map* map, hipStream_t st) {
+    XGGM_REQUIRE(map, "xggm_bertadam_multi_mapped: no hyper map");
+    return bertadam_multi(args, n, map, st, "xggm_bertadam_multi_mapped");
+}
 extern "C" int xggm_optim_multi(const xggm_optim_args* args, int n, hipStream_t st) {
-    XGGM_REQUIRE(args && n > 0, "xggm_optim_multi: no spans");
+    return optim_multi(args, n, nullptr, st, "xggm_optim_multi");
+}
+extern "C" int xggm_optim_multi_mapped(const xggm_optim_args* args, int n, const xggm_hyper_map* map, hipStream_t st) {
+    XGGM_REQUIRE(map, "xggm_optim_multi_mapped: no hyper map");
+    return optim_multi(args, n, map, st, "xggm_optim_multi_mapped");
+}
+
+namespace {
+int optim_multi(const xggm_optim_args* args, int n, const xggm_hyper_map* map, hipStream_t st, const char* who) {
+    XGGM_REQUIRE(args && n > 0, "%s: no spans", who);
+    HyperMap hm;
+    if (map) {
+        if (int e = hyper_map_of(map, who, hm)) return e;
+        for (int i = 0; i < n; ++i)
+            if (int e = span_in_map(args[i].a, map, who, i)) return e;
+    }
     const int rule = args[0].rule;
-    XGGM_REQUIRE(rule >= XGGM_RULE_BERTADAM && rule <= XGGM_RULE_RMSPROP, "xggm_optim_multi: unknown rule %d", rule);
+    XGGM_REQUIRE(rule >= XGGM_RULE_BERTADAM && rule <= XGGM_RULE_RMSPROP, "%s: unknown rule %d", who, rule);
     const bool mom0 = args[0].momentum == 0.0;
     int inst = R_BERT;
     if (rule == XGGM_RULE_ADAM || rule == XGGM_RULE_ADAMW) inst = R_ADAM;
@@ -961,20 +1092,20 @@ extern "C" int xggm_optim_multi(const xggm_optim_args* args, int n, hipStream_t 
             const xggm_optim_args& x = args[i0 + i];
             if (int e = adam_args_of(&x.a, om.a[i])) return e;
             XGGM_REQUIRE(x.rule == rule && (x.momentum == 0.0) == mom0 && x.a.g_bf16 == args[0].a.g_bf16,
-                         "xggm_optim_multi: the spans of one call share the rule, the gradient type and whether momentum is zero");
+                         "%s: the spans of one call share the rule, the gradient type and whether momentum is zero", who);
             RuleArgs& r = om.r[i];
             r = RuleArgs();
             if (inst != R_BERT) {
-                XGGM_REQUIRE(!x.a.shadow8, "xggm_optim_multi: the e4m3 weight copy is written by the BertAdam rule only");
+                XGGM_REQUIRE(!x.a.shadow8, "%s: the e4m3 weight copy is written by the BertAdam rule only", who);
                 XGGM_REQUIRE(x.step_scalars || !(inst == R_ADAM || inst == R_ADAMAX || inst == R_SGDM),
-                             "xggm_optim_multi: rule %d needs step_scalars (xggm_sched_step_ex)", rule);
+                             "%s: rule %d needs step_scalars (xggm_sched_step_ex)", who, rule);
                 r.hs = x.step_scalars;
                 r.decoupled = rule == XGGM_RULE_ADAMW;
                 r.mom = (float)x.momentum;
                 r.nesterov = x.nesterov != 0;
                 r.omd = (float)(1.0 - x.dampening);
                 if (inst == R_ADAM || inst == R_ADAMAX) {
-                    XGGM_REQUIRE(x.b1 >= 0.0 && x.b1 < 1.0 && x.b2 >= 0.0 && x.b2 < 1.0, "xggm_optim_multi: betas outside [0, 1)");
+                    XGGM_REQUIRE(x.b1 >= 0.0 && x.b1 < 1.0 && x.b2 >= 0.0 && x.b2 < 1.0, "%s: betas outside [0, 1)", who);
                     om.a[i].b1 = (float)x.b1;
                     om.a[i].b2 = (float)x.b2;
                     r.omb1 = (float)(1.0 - x.b1);
@@ -989,10 +1120,16 @@ extern "C" int xggm_optim_multi(const xggm_optim_args* args, int n, hipStream_t 
         }
         om.blk0[om.n] = nblk;
         const bool gb = args[0].a.g_bf16 != 0;
-#define OPTIM_LAUNCH(R)                                                                                              \
-    case R:                                                                                                          \
-        if (gb) hipLaunchKernelGGL((optim_multi_kernel<2, true, true, R>), dim3(nblk), dim3(NT), 0, st, om);        \
-        else hipLaunchKernelGGL((optim_multi_kernel<2, true, false, R>), dim3(nblk), dim3(NT), 0, st, om);          \
+#define OPTIM_LAUNCH(R)                                                                                                    \
+    case R:                                                                                                                \
+        if (map) {                                                                                                         \
+            if (gb) hipLaunchKernelGGL((optim_multi_mapped_kernel<2, true, true, R>), dim3(nblk), dim3(NT), 0, st, om, hm);  \
+            else hipLaunchKernelGGL((optim_multi_mapped_kernel<2, true, false, R>), dim3(nblk), dim3(NT), 0, st, om, hm);    \
+        } else if (gb) {                                                                                                   \
+            hipLaunchKernelGGL((optim_multi_kernel<2, true, true, R>), dim3(nblk), dim3(NT), 0, st, om);                  \
+        } else {                                                                                                           \
+            hipLaunchKernelGGL((optim_multi_kernel<2, true, false, R>), dim3(nblk), dim3(NT), 0, st, om);                 \
+        }                                                                                                                  \
         break;
         switch (inst) {
             OPTIM_LAUNCH(R_ADAM)
@@ -1006,15 +1143,22 @@ extern "C" int xggm_optim_multi(const xggm_optim_args* args, int n, hipStream_t 
                 am.n = om.n;
                 for (int i = 0; i < om.n; ++i) am.a[i] = om.a[i];
                 for (int i = 0; i <= om.n; ++i) am.blk0[i] = om.blk0[i];
-                if (gb) hipLaunchKernelGGL((bertadam_multi_kernel<2, true, true>), dim3(nblk), dim3(NT), 0, st, am);
-                else hipLaunchKernelGGL((bertadam_multi_kernel<2, true, false>), dim3(nblk), dim3(NT), 0, st, am);
+                if (map) {
+                    if (gb) hipLaunchKernelGGL((bertadam_multi_mapped_kernel<2, true, true>), dim3(nblk), dim3(NT), 0, st, am, hm);
+                    else hipLaunchKernelGGL((bertadam_multi_mapped_kernel<2, true, false>), dim3(nblk), dim3(NT), 0, st, am, hm);
+                } else if (gb) {
+                    hipLaunchKernelGGL((bertadam_multi_kernel<2, true, true>), dim3(nblk), dim3(NT), 0, st, am);
+                } else {
+                    hipLaunchKernelGGL((bertadam_multi_kernel<2, true, false>), dim3(nblk), dim3(NT), 0, st, am);
+                }
             }
         }
 #undef OPTIM_LAUNCH
-        if (int e = xggm_check_launch("xggm_optim_multi")) return e;
+        if (int e = xggm_check_launch(who)) return e;
     }
     return XGGM_OK;
 }
+}  // namespace
 
 extern "C" int xggm_sqnorm_bf16(const void* g, int64_t n, float* out, float* ws, hipStream_t st) {
     XGGM_REQUIRE(g && out && ws && n > 0, "xggm_sqnorm_bf16: bad arguments");

@@ -191,6 +191,12 @@ class ArenaOptimizer(Optimizer):
     per arena group, learning rates in a device table, ONE fused launch for all spans of a pass.  A subclass gives the
     rule: its kernel hyper-parameters, its schedule step and its state layout."""
 
+    # ``split_groups=True`` (constructor keyword of every class): param_groups may cut through an arena group and differ
+    # there in lr and weight_decay; the update then reads both per tensor from a device map (ops.bertadam_multi /
+    # ops.optim_multi with ``hyper_map``).  Off: one lr / weight_decay per arena group, a split is refused.
+    split_groups = False
+    SPLIT_KEYS = ('lr', 'weight_decay')  # what param_groups inside one arena group may differ in
+
     @property
     def _name(self):
         return type(self).__name__
@@ -215,8 +221,9 @@ class ArenaOptimizer(Optimizer):
         """the stand-alone schedule step: counters, ``lr_scale`` and whatever the rule needs per step"""
         raise NotImplementedError
 
-    def _launch(self, arena, jobs):
-        """``jobs``: [(positional arguments of ops.bertadam_ex, its keyword arguments, param_group)]"""
+    def _launch(self, arena, jobs, hyper_map=None):
+        """``jobs``: [(positional arguments of ops.bertadam_ex, its keyword arguments, param_group)]; ``hyper_map``:
+        (ids, table) under split_groups, to be handed to the ops call"""
         raise NotImplementedError
 
     # ---- shared plumbing
@@ -229,10 +236,17 @@ class ArenaOptimizer(Optimizer):
         return arena
 
     def _hyper_of_group(self, arena, gname):
-        """the optimiser param_group that holds ALL parameters of arena group ``gname`` (one contiguous range, one
-        launch, one set of hyper-parameters).  A param_groups split that cuts through an arena group -- the usual
-        BERT "no decay for bias / LayerNorm" grouping would -- cannot be honoured by a flat update and is refused
-        instead of silently applying the first parameter's settings to the whole range."""
+        """the optimiser param_group that speaks for arena group ``gname`` (one contiguous range, one launch), or None
+        when the optimiser holds none of its parameters.
+        Default: the param_group that holds ALL parameters of the arena group.  A param_groups split that cuts through
+        an arena group -- the usual BERT "no decay for bias / LayerNorm" grouping would -- cannot be honoured by a flat
+        update with one lr / weight_decay and is refused instead of silently applying the first parameter's settings
+        to the whole range.
+        With ``split_groups=True`` the split is honoured: the param_groups that share an arena group may differ in
+        ``lr`` and ``weight_decay`` (read per tensor from the hyper map, ``_hyper_map``), parameters in no param_group
+        are left untouched, and the first param_group found stands for every other key -- schedule, betas, eps,
+        momentum ... -- which must agree inside the arena group (step counter and schedule value stay one per arena
+        group): a difference raises a ValueError that names the key."""
         cache = getattr(self, "_group_pg", None)
         if cache is None:
             cache = self._group_pg = {}
@@ -242,6 +256,18 @@ class ArenaOptimizer(Optimizer):
                 for p in pg['params']:
                     owner[id(p)] = i
             idx = {owner.get(id(p)) for p in arena.groups[gname].params}
+            if self.split_groups:
+                idx = sorted(i for i in idx if i is not None)
+                first = self.param_groups[idx[0]] if idx else None
+                for i in idx[1:]:
+                    pg = self.param_groups[i]
+                    for k in sorted(set(first) | set(pg)):
+                        if k != 'params' and k not in self.SPLIT_KEYS and first.get(k) != pg.get(k):
+                            raise ValueError("%s(split_groups=True): param_groups %d and %d share arena group '%s' and differ "
+                                             "in '%s' (%r, %r); inside an arena group only %s may differ"
+                                             % (self._name, idx[0], i, gname, k, first.get(k), pg.get(k),
+                                                " and ".join(self.SPLIT_KEYS)))
+                idx = {idx[0] if idx else None}
             if len(idx) > 1:
                 raise ValueError("%s: the parameters of arena group '%s' are spread over optimiser param_groups %s; "
                                  "a group is updated as one range with one lr / weight_decay / schedule -- keep its "
@@ -251,11 +277,46 @@ class ArenaOptimizer(Optimizer):
         i = cache[gname]
         return None if i is None else self.param_groups[i]
 
+    def _hyper_map(self, arena, upload=True):
+        """split_groups: (ids, table) of ops.bertadam_multi / ops.optim_multi -- the id map of this optimiser over
+        ``arena`` (arena.hyper_id_map: one uint8 per 8 elements, 1 + index of the owning param_group, 0 = not ours),
+        built and uploaded once, and the {lr, weight_decay} table with one row per param_group behind row 0, rewritten
+        when a value changed.  Both outside of captures only."""
+        st = getattr(self, "_split_state", None)
+        if st is None or st['arena'] is not arena or st['n'] != len(self.param_groups):
+            if not upload or torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("%s.step is being captured before any eager step: run one pass eagerly first "
+                                   "(the hyper map is uploaded to the device outside of captures)" % self._name)
+            from ..arena import hyper_id_map
+            owner = {}
+            for i, pg in enumerate(self.param_groups):
+                for p in pg['params']:
+                    xg = getattr(p, "_xg", None)
+                    if xg is not None and xg[0] is arena:
+                        owner[xg[5]] = i + 1
+            ids = hyper_id_map(arena.info, owner, arena.total)  # (ValueError: more param_groups than the ids hold)
+            st = self._split_state = dict(arena=arena, n=len(self.param_groups), host=None,
+                                          ids=torch.from_numpy(ids).to(arena.device),
+                                          table=torch.zeros(len(self.param_groups) + 1, 2, device=arena.device))
+        if upload:
+            host = [(0.0, 0.0)] + [(float(pg['lr']), float(pg['weight_decay'])) for pg in self.param_groups]
+            if host != st['host']:
+                if torch.cuda.is_current_stream_capturing():
+                    raise RuntimeError("%s: a learning rate or weight decay changed during graph capture; call sync_hyper() "
+                                       "before" % self._name)
+                st['table'].copy_(torch.tensor(host, dtype=torch.float32))
+                st['host'] = host
+        return st['ids'], st['table']
+
     def sync_hyper(self):
-        """push ``param_groups[i]['lr']`` to the device table the update kernels read: call after editing a learning
-        rate between replays of a captured pass (an eager ``step()`` does it by itself)"""
+        """push ``param_groups[i]['lr']`` -- with ``split_groups=True`` also ``['weight_decay']`` -- to the device table the
+        update kernels read: call after editing one between replays of a captured pass (an eager ``step()`` does it by
+        itself)"""
         arena = self._arena()
         if arena is None:
+            return
+        if self.split_groups:
+            self._hyper_map(arena)
             return
         for g in arena.groups:
             pg = self._hyper_of_group(arena, g)
@@ -275,6 +336,10 @@ class ArenaOptimizer(Optimizer):
     def _todo(self, arena):
         """(group, its param_group, its index) for every arena group that received gradients in this pass"""
         self._check_arena(arena)
+        if self.split_groups and arena.zero1 is not None:
+            raise RuntimeError("%s(split_groups=True) does not run under the sharded update (zero1): a rank's slices are "
+                               "updated with one lr / weight_decay per arena group; build the optimiser without "
+                               "split_groups, or the data parallelism without zero1" % self._name)
         todo = []
         for g in arena.active_groups():
             G = arena.groups[g]
@@ -298,9 +363,10 @@ class ArenaOptimizer(Optimizer):
         if todo and not getattr(arena, "sched_done", False):  # schedule values and step counters of all groups: one launch
             self._sched_launch(arena, todo)
         arena.sched_done = False  # (True: clip_grad_norm_'s finishing launch has taken the step along)
+        hyper_map = None
         if not torch.cuda.is_current_stream_capturing():
             self.sync_hyper()  # the kernels read lr from a device table: edits of param_groups survive graph replay
-        elif any(arena.lr_host[gi] is None for _, _, gi in todo):
+        elif not self.split_groups and any(arena.lr_host[gi] is None for _, _, gi in todo):  # (split: _hyper_map below)
             raise RuntimeError("%s.step is being captured before any eager step: run one pass eagerly first "
                                "(the learning rates are uploaded to the device outside of captures)" % self._name)
         f8 = arena.fp8
@@ -339,7 +405,9 @@ class ArenaOptimizer(Optimizer):
             jobs.append(((arena.params[sl], gbuf[sl], arena.m[sl], arena.v[sl],
                           None if arena.shadow is None else arena.shadow[sl], sq, max_norm, pg['lr'], scale_t) + hyper,
                          dict(lr_dev=arena.lr_table[gi:gi + 1], w8=w8, elem0=G.start, g_scale=gscale), pg, gi))
-        self._launch(arena, jobs)
+        if self.split_groups and jobs:
+            hyper_map = self._hyper_map(arena, upload=False)
+        self._launch(arena, jobs, hyper_map)
         arena.pending_clip = None
         return loss
 
@@ -349,7 +417,7 @@ class BertAdam(ArenaOptimizer):
     every parameter; gradient clipping is done outside, as LXMERT does)."""
 
     def __init__(self, params, lr, warmup=-1, t_total=-1, schedule='warmup_linear', b1=0.9, b2=0.999, e=1e-6,
-                 weight_decay=0.01, max_grad_norm=1.0):
+                 weight_decay=0.01, max_grad_norm=1.0, split_groups=False):
         if lr < 0.0:
             raise ValueError("Invalid learning rate: {} - should be >= 0.0".format(lr))
         if schedule not in SCHEDULES:
@@ -364,6 +432,7 @@ class BertAdam(ArenaOptimizer):
             raise ValueError("Invalid epsilon value: {} - should be >= 0.0".format(e))
         defaults = dict(lr=lr, schedule=schedule, warmup=warmup, t_total=t_total, b1=b1, b2=b2, e=e,
                         weight_decay=weight_decay, max_grad_norm=max_grad_norm)
+        self.split_groups = bool(split_groups)
         super().__init__(params, defaults)
 
     # ---- checkpointing: the reference layout (src/lxrt/optimization.py:147-155 keeps per-parameter
@@ -461,5 +530,5 @@ class BertAdam(ArenaOptimizer):
             ops.sched_step_ex(arena.steps, arena.lr_scale, None,
                               [(gi, pg['t_total'], pg['warmup'], pg['schedule'], 0.0, 0.0) for _, pg, gi in todo])
 
-    def _launch(self, arena, jobs):
-        ops.bertadam_multi([(a, kw) for a, kw, _, _ in jobs])
+    def _launch(self, arena, jobs, hyper_map=None):
+        ops.bertadam_multi([(a, kw) for a, kw, _, _ in jobs], hyper_map=hyper_map)

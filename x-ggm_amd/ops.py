@@ -1511,17 +1511,40 @@ class AdamArgs(_ct.Structure):
                 ("w8_amax", _ct.c_void_p), ("elem0", _ct.c_int64), ("g_scale", _ct.c_float), ("w8_amax_slots", _ct.c_int)]
 
 
-def bertadam_multi(jobs):
+class HyperMap(_ct.Structure):
+    """mirror of ``xggm_hyper_map`` (include/xggm.h)"""
+    _fields_ = [("ids", _ct.c_void_p), ("n_ids", _ct.c_int64), ("table", _ct.c_void_p), ("n_table", _ct.c_int)]
+
+
+HYPER_MAP_ELEMS = 8     # elements of the arena one id of the map stands for (arena.ALIGN)
+HYPER_MAP_MAX_ID = 255  # the ids are uint8; 0 = not in the optimiser
+
+
+def _hyper_map(hyper_map):
+    """``hyper_map`` = (ids: uint8 [ceil(arena / 8)], table: fp32 [1 + param_groups, 2] of {lr, weight_decay}), both on the device"""
+    ids, table = hyper_map
+    _c(ids, torch.uint8), _c(table, F32)
+    if table.dim() != 2 or table.shape[1] != 2 or not 1 <= table.shape[0] <= HYPER_MAP_MAX_ID + 1:
+        raise ValueError("xggm_amd: the hyper table is [1 + param_groups <= %d, 2], got %s" % (HYPER_MAP_MAX_ID + 1, tuple(table.shape)))
+    return HyperMap(ptr(ids), ids.numel(), ptr(table), table.shape[0])
+
+
+def bertadam_multi(jobs, hyper_map=None):
     """``jobs``: argument tuples of ``bertadam_ex`` (positional, then a dict of its keyword arguments): ONE launch for all
-    of them (xggm_bertadam_multi), in chunks by gradient type"""
+    of them (xggm_bertadam_multi), in chunks by gradient type.  With ``hyper_map`` (see ``_hyper_map``) lr and weight decay
+    are read per tensor from the map (xggm_bertadam_multi_mapped); the jobs' own are then not used."""
     if not jobs:
         return
     structs = [_adam_args(*a, **kw) for a, kw in jobs]
+    hm = None if hyper_map is None else _hyper_map(hyper_map)
     for bf in (0, 1):
         chunk = [a for a in structs if a.g_bf16 == bf]
         if chunk:
             arr = (AdamArgs * len(chunk))(*chunk)
-            call("xggm_bertadam_multi", _ct.cast(arr, _ct.c_void_p), len(chunk), stream())
+            if hm is None:
+                call("xggm_bertadam_multi", _ct.cast(arr, _ct.c_void_p), len(chunk), stream())
+            else:
+                call("xggm_bertadam_multi_mapped", _ct.cast(arr, _ct.c_void_p), len(chunk), _ct.byref(hm), stream())
 
 
 RULES = {"bertadam": 0, "adam": 1, "adamw": 2, "adamax": 3, "sgd": 4, "rmsprop": 5}  # XGGM_RULE_* (include/xggm.h)
@@ -1541,13 +1564,14 @@ class SchedEntry(_ct.Structure):
                 ("b1", _ct.c_double), ("b2", _ct.c_double)]
 
 
-def optim_multi(rule, jobs):
+def optim_multi(rule, jobs, hyper_map=None):
     """the fused update under a torch.optim rule (src/param.py:9-31): ``rule`` a key of ``RULES``; ``jobs``: (argument
     tuple of ``bertadam_ex``, dict of its keyword arguments, dict of the rule's: step_scalars (3 device floats of the span's
     group, ``sched_step_ex``), b1, b2, momentum, dampening, alpha, nesterov) per span.  ONE launch per 8 spans
-    (xggm_optim_multi), in chunks by gradient type."""
+    (xggm_optim_multi), in chunks by gradient type.  ``hyper_map``: as for ``bertadam_multi`` (xggm_optim_multi_mapped)."""
     if not jobs:
         return
+    hm = None if hyper_map is None else _hyper_map(hyper_map)
     structs = []
     for a, kw, r in jobs:
         hs = r.get("step_scalars")
@@ -1561,7 +1585,10 @@ def optim_multi(rule, jobs):
         chunk = [x for x in structs if x.a.g_bf16 == bf]
         if chunk:
             arr = (OptimArgs * len(chunk))(*chunk)
-            call("xggm_optim_multi", _ct.cast(arr, _ct.c_void_p), len(chunk), stream())
+            if hm is None:
+                call("xggm_optim_multi", _ct.cast(arr, _ct.c_void_p), len(chunk), stream())
+            else:
+                call("xggm_optim_multi_mapped", _ct.cast(arr, _ct.c_void_p), len(chunk), _ct.byref(hm), stream())
 
 
 def sched_step_ex(steps, lr_scale, step_scalars, entries):

@@ -11,7 +11,9 @@ it once per step in double by the launch that advances it (``ops.sched_step_ex``
 torch's Python floats.
 
 Groups that received no gradient in a pass are not touched (no decay, no momentum, no step count): torch's
-``grad is None`` skip.  The sharded update (ZeRO-1) and the fp8 forward are BertAdam's."""
+``grad is None`` skip.  ``split_groups=True`` (every constructor) honours param_groups that cut through an arena group --
+a no-decay group for biases and LayerNorm, layer-wise learning rates, parameters left out: lr and weight_decay are then
+read per tensor from a device map by the same single launch (``ArenaOptimizer._hyper_of_group``).  The sharded update (ZeRO-1) and the fp8 forward are BertAdam's."""
 import torch
 
 from . import ops
@@ -60,13 +62,13 @@ class _TorchRule(ArenaOptimizer):
         """(rule name of ops.RULES, anything else that selects another kernel instantiation): spans of one launch share it"""
         return (self.rule,)
 
-    def _launch(self, arena, jobs):
+    def _launch(self, arena, jobs, hyper_map=None):
         by = {}
         for a, kw, pg, gi in jobs:
             by.setdefault(self._variant(pg), []).append(
                 (a, kw, dict(self._rule_args(pg), step_scalars=arena.step_scalars[4 * gi:4 * gi + 4])))
         for key in sorted(by):
-            ops.optim_multi(key[0], by[key])
+            ops.optim_multi(key[0], by[key], hyper_map=hyper_map)
 
     # ---- checkpointing: torch's per-parameter layout, read from / written into the flat arena
     def state_dict(self):
@@ -152,7 +154,8 @@ class Adam(_TorchRule):
     rule, _m_name, _v_name = "adam", "exp_avg", "exp_avg_sq"
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, *, foreach=None,
-                 maximize=False, capturable=False, differentiable=False, fused=None, decoupled_weight_decay=False):
+                 maximize=False, capturable=False, differentiable=False, fused=None, decoupled_weight_decay=False,
+                 split_groups=False):
         _check_common(lr, eps, weight_decay)
         _check_betas(betas)
         _refuse(self._name, amsgrad=(amsgrad, (False,)), foreach=(foreach, (None,)), maximize=(maximize, (False,)),
@@ -160,6 +163,7 @@ class Adam(_TorchRule):
         defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad, maximize=maximize,
                         foreach=foreach, capturable=capturable, differentiable=differentiable, fused=fused,
                         decoupled_weight_decay=decoupled_weight_decay)
+        self.split_groups = bool(split_groups)
         super().__init__(params, defaults)
 
     def _betas(self, pg):
@@ -177,9 +181,10 @@ class AdamW(Adam):
     """torch.optim.AdamW (src/param.py:20-22): Adam with decoupled weight decay, default 0.01"""
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False, *, maximize=False,
-                 foreach=None, capturable=False, differentiable=False, fused=None):
+                 foreach=None, capturable=False, differentiable=False, fused=None, split_groups=False):
         super().__init__(params, lr, betas, eps, weight_decay, amsgrad, foreach=foreach, maximize=maximize,
-                         capturable=capturable, differentiable=differentiable, fused=fused, decoupled_weight_decay=True)
+                         capturable=capturable, differentiable=differentiable, fused=fused, decoupled_weight_decay=True,
+                         split_groups=split_groups)
 
 
 class Adamax(_TorchRule):
@@ -187,13 +192,14 @@ class Adamax(_TorchRule):
     rule, _m_name, _v_name = "adamax", "exp_avg", "exp_inf"
 
     def __init__(self, params, lr=2e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, foreach=None, *, maximize=False,
-                 differentiable=False, capturable=False):
+                 differentiable=False, capturable=False, split_groups=False):
         _check_common(lr, eps, weight_decay)
         _check_betas(betas)
         _refuse(self._name, foreach=(foreach, (None,)), maximize=(maximize, (False,)), capturable=(capturable, (False,)),
                 differentiable=(differentiable, (False,)))
         defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, foreach=foreach, maximize=maximize,
                         differentiable=differentiable, capturable=capturable)
+        self.split_groups = bool(split_groups)
         super().__init__(params, defaults)
 
     def _betas(self, pg):
@@ -208,7 +214,7 @@ class SGD(_TorchRule):
     rule, _m_name, _v_name, _has_step = "sgd", "momentum_buffer", None, False
 
     def __init__(self, params, lr=1e-3, momentum=0, dampening=0, weight_decay=0, nesterov=False, *, maximize=False,
-                 foreach=None, differentiable=False, fused=None):
+                 foreach=None, differentiable=False, fused=None, split_groups=False):
         _check_common(lr, 0.0, weight_decay)
         if momentum < 0.0:
             raise ValueError("Invalid momentum value: {}".format(momentum))
@@ -218,6 +224,7 @@ class SGD(_TorchRule):
                 fused=(fused, (None,)))
         defaults = dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=nesterov,
                         maximize=maximize, foreach=foreach, differentiable=differentiable, fused=fused)
+        self.split_groups = bool(split_groups)
         super().__init__(params, defaults)
 
     def _names(self, pg):
@@ -235,7 +242,7 @@ class RMSprop(_TorchRule):
     rule, _m_name, _v_name = "rmsprop", "momentum_buffer", "square_avg"
 
     def __init__(self, params, lr=1e-2, alpha=0.99, eps=1e-8, weight_decay=0, momentum=0, centered=False, capturable=False,
-                 foreach=None, maximize=False, differentiable=False):
+                 foreach=None, maximize=False, differentiable=False, split_groups=False):
         _check_common(lr, eps, weight_decay)
         if momentum < 0.0:
             raise ValueError("Invalid momentum value: {}".format(momentum))
@@ -245,6 +252,7 @@ class RMSprop(_TorchRule):
                 maximize=(maximize, (False,)), differentiable=(differentiable, (False,)))
         defaults = dict(lr=lr, momentum=momentum, alpha=alpha, eps=eps, centered=centered, weight_decay=weight_decay,
                         capturable=capturable, foreach=foreach, maximize=maximize, differentiable=differentiable)
+        self.split_groups = bool(split_groups)
         super().__init__(params, defaults)
 
     def _names(self, pg):

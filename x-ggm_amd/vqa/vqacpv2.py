@@ -295,17 +295,81 @@ def train_iteration(model, optim, bce_loss, batch, delta=5, sigma=1.0, order="vq
     return out
 
 
-def make_optimizer(model, lr, t_total, warmup=0.1, optim='bert'):
+ENCODER_PREFIX = "lxrt_encoder."
+# name substrings of the parameters that usually go without weight decay: biases and LayerNorm weights.  The encoder's
+# LayerNorms are attributes called LayerNorm / *_layer_norm; the heads (logit_fc, node_fc, fusion_fc) and the generators'
+# MLPs are Sequential(Linear, GeLU, LayerNorm), whose LayerNorm weight is item "2.weight".
+NO_DECAY = ("bias", "LayerNorm.weight", "layer_norm.weight", ".2.weight")
+
+
+def param_depth(name, llayers, xlayers, rlayers):
+    """depth of a parameter for layer-wise learning-rate decay: 0 for the embeddings and visn_fc, the two towers END level
+    (with L = max(llayers, rlayers): ``encoder.layer.i`` -> i + 1 + (L - llayers), ``encoder.r_layers.i`` -> i + 1 +
+    (L - rlayers)), ``encoder.x_layers.j`` -> L + 1 + j, and D = L + xlayers + 1 for the pooler and everything outside
+    the encoder."""
+    import re
+    L = max(llayers, rlayers)
+    D = L + xlayers + 1
+    if not name.startswith(ENCODER_PREFIX):
+        return D
+    m = re.search(r"\.encoder\.(layer|r_layers|x_layers)\.(\d+)\.", name)
+    if m:
+        i = int(m.group(2))
+        return {"layer": i + 1 + (L - llayers), "r_layers": i + 1 + (L - rlayers), "x_layers": L + 1 + i}[m.group(1)]
+    if ".embeddings." in name or ".encoder.visn_fc." in name:
+        return 0
+    return D  # the pooler
+
+
+def split_param_names(names, lr, no_decay=None, layer_decay=None, llayers=9, xlayers=5, rlayers=5, head_lr_mult=4.0):
+    """The param_groups of ``make_optimizer(..., no_decay, layer_decay)`` over parameter NAMES (``named_parameters()``
+    order is kept inside a group): [{"names": [...], "lr": ..., ("weight_decay": 0.0)}].
+    Base lr: ``lr`` for the encoder, ``head_lr_mult * lr`` for the rest (the reference's two groups,
+    src/vqa/vqacpv2.py:113-128).  ``layer_decay`` = d: a parameter's lr is its base lr times d ** (D - depth)
+    (``param_depth``).  ``no_decay``: name substrings (``NO_DECAY``); a matching parameter goes to a twin group with
+    ``weight_decay`` 0.0, the others keep the optimiser's default.  Every name lands in exactly one group; groups come
+    in the order head, then encoder by falling depth, decay before no-decay.  With both None: the reference's two."""
+    D = max(llayers, rlayers) + xlayers + 1
+    groups = {}
+    for n in names:
+        enc = n.startswith(ENCODER_PREFIX)
+        depth = param_depth(n, llayers, xlayers, rlayers) if layer_decay is not None else D
+        nd = no_decay is not None and any(s in n for s in no_decay)
+        groups.setdefault((enc, -depth, nd), []).append(n)
+    out = []
+    for (enc, mdepth, nd) in sorted(groups):
+        g = {"names": groups[(enc, mdepth, nd)], "lr": (lr if enc else lr * head_lr_mult)}
+        if layer_decay is not None:
+            g["lr"] = g["lr"] * float(layer_decay) ** (D + mdepth)
+        if nd:
+            g["weight_decay"] = 0.0
+        out.append(g)
+    return out
+
+
+def make_optimizer(model, lr, t_total, warmup=0.1, optim='bert', no_decay=None, layer_decay=None):
     """the two parameter groups of src/vqa/vqacpv2.py:113-128: heads/generator at 4*lr,
     encoder at lr; BertAdam(warmup=0.1, t_total=2*iters).  ``optim``: another ``--optim`` name of the reference
     (rms, adam, adamw, adamax, sgd) or what ``param.get_optimizer`` returned for it builds the else-branch
-    (src/vqa/vqacpv2.py:141): one group, all parameters, ``lr`` -- the arena-aware class of ``xggm_amd.optim``."""
+    (src/vqa/vqacpv2.py:141): one group, all parameters, ``lr`` -- the arena-aware class of ``xggm_amd.optim``.
+    ``no_decay`` (name substrings, e.g. ``NO_DECAY``) and / or ``layer_decay`` (a factor d per layer of depth, see
+    ``split_param_names``) build finer param_groups and turn ``split_groups`` on, so that groups which cut through the
+    arena's ranges are honoured; the else-branch's base lr is ``lr`` for every parameter, as without them."""
     if isinstance(optim, str):
         from ..param import get_optimizer
         optim = get_optimizer(optim)
+    split = no_decay is not None or layer_decay is not None
+    if split:
+        enc = model.lxrt_encoder.model.bert.encoder
+        named = dict(model.named_parameters())
+        specs = split_param_names(list(named), lr, no_decay, layer_decay, len(enc.layer), len(enc.x_layers), len(enc.r_layers),
+                                  head_lr_mult=4.0 if optim == 'bert' else 1.0)
+        groups = [dict({k: v for k, v in g.items() if k != "names"}, params=[named[n] for n in g["names"]]) for g in specs]
     if optim != 'bert':
-        return optim(model.parameters(), lr)
+        return optim(groups, lr, split_groups=True) if split else optim(model.parameters(), lr)
     from ..lxrt.optimization import BertAdam
+    if split:
+        return BertAdam(groups, lr=lr, warmup=warmup, t_total=t_total, split_groups=True)
     lxrt_ids = set(map(id, model.lxrt_encoder.parameters()))
     base_params = [p for p in model.parameters() if id(p) not in lxrt_ids]
     groups = [{"params": base_params, "lr": lr * 4}, {"params": list(model.lxrt_encoder.parameters())}]
