@@ -543,6 +543,65 @@ int xggm_bce_bwd_f32(const float* logit, const float* target, const float* gout,
                      xggm_stream_t stream);
 int xggm_bce_bwd_bf16(const float* logit, const float* target, const float* gout, void* dlogit, int64_t n, float coef,
                       xggm_stream_t stream);
+/* Debias answer losses of the language-prior benchmarks (VQA-CP v2, GQA-OOD): ReweightByInvBias, BiasProduct and
+ * LearnedMixin of src/module/vqa_debias_loss_functions.py:84-207 (Plain, :67-71, is xggm_bce_* with coef = 1 / B).
+ * z = logits, y = labels, b = bias in [0, 1] (all fp32 [B, A], rows 4-byte aligned are enough), s = constant_smooth
+ * (+ sigmoid(*smooth_param) when given), p = log(b + s), q = log(1 - b + s):
+ *   LEARNED_MIXIN   g_r = softplus(hidden[r] . lin_w + *lin_b);  d = z + g_r (p - q)
+ *                   *loss += mean_r sum_a [softplus(-d) y + softplus(d) (1 - y)] + w * mean_{r,a} H(g_r (p - q)),
+ *                   H(e) the entropy of (sigmoid(e), sigmoid(-e)): the penalty of :201-207
+ *   BIAS_PRODUCT    the same with g = 1 and no penalty (:113-138)
+ *   REWEIGHT        *loss += sum (1 - b) bce_elem(z, y) / sum (1 - b)          (:85-93)
+ * (all at the scale of BCEWithLogits(mean) * A).  The results are finite wherever the reference's are: s > 0, or no
+ * bias entry at exactly 0 or 1.
+ * Row r reads bias + i * bias_row_stride with i = bias_index ? bias_index[r] : r, clamped into [0, bias_rows): with an
+ * index the bias is a small [groups, A] prior table and never exists as [B, A].
+ * The _f32 / _bf16 suffix names the type of hidden, d_hidden and d_logit (dlogit_f32 != 0: d_logit is fp32 under either
+ * suffix -- the answer head keeps fp32 logits); logits, labels, bias and the three parameters (fp32 masters) are fp32.
+ * forward: ONE launch; needs loss, ws (XGGM_SUM_WS_FLOATS floats, ws[0] == 0 at launch, left 0) and `save`.
+ * backward: reads what the forward left in `save`; d_logit = *gout (NULL: 1) * d loss / d z always; LEARNED_MIXIN also
+ * d_hidden[r] = dpre_r * lin_w (NULL: not wanted).  Parameter gradients (all NULL: not wanted; d_lin_w and d_lin_b come
+ * together) cost a second launch that adds the per-row terms the first left in `part` in row order; accumulate != 0
+ * adds them to d_lin_w [Hd], d_lin_b [1], d_smooth [1] instead of overwriting.
+ * No floating-point atomics, every sum in a fixed order; no allocation, no host synchronisation: legal inside a stream
+ * capture.  Refused before any launch: unknown kind, B or A <= 0, a null logits / labels / bias, LEARNED_MIXIN without
+ * hidden / lin_w / lin_b / Hd / save, REWEIGHT without save or with a smooth_param, a bias of fewer than B rows without
+ * an index, parameter gradients without `part`. */
+#define XGGM_DEBIAS_REWEIGHT 1
+#define XGGM_DEBIAS_BIAS_PRODUCT 2
+#define XGGM_DEBIAS_LEARNED_MIXIN 3
+typedef struct xggm_debias_args {
+    const float* logits;       /* [B, A] */
+    const float* labels;       /* [B, A] soft scores */
+    const float* bias;         /* [bias_rows, >= A] */
+    int64_t bias_row_stride;   /* floats between two rows of bias, >= A */
+    int64_t bias_rows;         /* rows of bias: B, or the groups of a prior table */
+    const int64_t* bias_index; /* [B] row of bias per sample, or NULL */
+    const void* hidden;        /* [B, Hd], LEARNED_MIXIN only */
+    int Hd;
+    const float* lin_w;        /* bias_lin.weight [Hd] */
+    const float* lin_b;        /* bias_lin.bias [1] */
+    const float* smooth_param; /* [1] or NULL */
+    float constant_smooth;
+    float w;                   /* weight of the entropy penalty */
+    int kind, B, A;
+    float* loss;               /* forward: the slot the loss is added to */
+    float* save;               /* LEARNED_MIXIN: 2 B floats (pre-activation, g per row); REWEIGHT: 1 float (sum of weights) */
+    float* ws;                 /* forward: XGGM_SUM_WS_FLOATS floats */
+    const float* gout;         /* backward: upstream gradient, DEVICE scalar, or NULL */
+    void* d_logit;             /* backward: [B, A] */
+    int dlogit_f32;
+    void* d_hidden;            /* backward: [B, Hd] or NULL */
+    float* d_lin_w;            /* backward: [Hd] or NULL */
+    float* d_lin_b;            /* backward: [1] or NULL */
+    float* d_smooth;           /* backward: [1] or NULL */
+    float* part;               /* backward: scratch of 2 B floats, needed for parameter gradients */
+    int accumulate;
+} xggm_debias_args;
+int xggm_debias_fwd_f32(const xggm_debias_args* args, xggm_stream_t stream);
+int xggm_debias_fwd_bf16(const xggm_debias_args* args, xggm_stream_t stream);
+int xggm_debias_bwd_f32(const xggm_debias_args* args, xggm_stream_t stream);
+int xggm_debias_bwd_bf16(const xggm_debias_args* args, xggm_stream_t stream);
 
 /* ---- preprocessing that feeds the path ----------------------------------------------------
  * adj_true of every sample: data/preprocess/vqa/compute_adjacency.py:38-45 (compute_cosin_sim_v2) + :90.

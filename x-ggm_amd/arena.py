@@ -127,7 +127,10 @@ def default_group_of(name, model=None):
 
 
 def is_atomic(name, p):
-    return p.dim() < 2 or "embeddings." in name or name.endswith("box_fc.weight") or p.numel() < 64
+    # (the parameters of an attached debias loss -- bias_lin.weight [1, Hd] among them -- are read as fp32 masters by the
+    # loss kernel and get their gradient added in fp32: vector class, no bf16 shadow read, no weight-gradient GEMM)
+    return (p.dim() < 2 or "embeddings." in name or name.endswith("box_fc.weight") or p.numel() < 64
+            or name.startswith("debias_loss."))
 
 
 class Group:

@@ -227,6 +227,9 @@ class CapturedTrainer:
             raise ValueError("CapturedTrainer: answer_log needs scores (AnswerLog(with_scores=True))")
         self.rt = runtime_of(model)
         self.static_flat = None
+        if packed_spec is not None and getattr(model, "debias_loss", None) is not None:
+            raise ValueError("CapturedTrainer: packed_spec carries no bias for the attached debias loss; hand batches over "
+                             "with load_batch")
         if packed_spec is not None:
             from .tools.data_loader import packed_like
             dev = next(model.parameters()).device
@@ -265,9 +268,11 @@ class CapturedTrainer:
     def _fwd_bwd(self, kind, between=None):
         s = self.static
         sent = (s["input_ids"], s["input_mask"], s["segment_ids"])
+        # an attached debias loss (vqa.vqacpv2.attach_debias_loss) reads its bias from the static batch like everything else
+        kw = dict(bias=s.get("bias"), bias_index=s.get("bias_index")) if getattr(self.model, "debias_loss", None) is not None else {}
         if kind == "plain":
             loss, logit = forward_backward_plain(self.model, self.bce, s["feats"], s["boxes"], sent, s["target"],
-                                                 between=between)
+                                                 between=between, **kw)
             if self.answer_log is not None:
                 # reads the logits and the target only: behind the backward it costs one short launch at the tail of the
                 # (last backward) graph and nothing waits for it
@@ -275,7 +280,7 @@ class CapturedTrainer:
             terms = None
         else:
             loss, logit, terms = forward_backward_ggm(self.model, self.bce, s["feats"], s["boxes"], sent, s["target"],
-                                                      s["adj_true"], kind, self.sigma, self.kl_weight, between=between)
+                                                      s["adj_true"], kind, self.sigma, self.kl_weight, between=between, **kw)
         if self.train_log is not None:
             self._pass = (kind, loss, terms)  # the loss-kernel slots stay alive until the update has appended them
         return loss, logit

@@ -1009,6 +1009,49 @@ class BCEFn(Function):
         return ops.bce_bwd(logit, target, gout.contiguous(), coef, F32), None, None, None
 
 
+class DebiasFn(Function):
+    """ReweightByInvBias / BiasProduct / LearnedMixin (src/module/vqa_debias_loss_functions.py:84-207) on fp32 logits:
+    one launch forward, one backward plus one for the parameter gradients.  Gradients go to the logits, to ``hidden`` and
+    to bias_lin.weight / bias_lin.bias / smooth_param; bias and labels get none.  Parameters that live in a model's arena
+    (``attach_debias_loss``) get theirs written into its fp32 gradient buffer like every other vector-class parameter;
+    parameters of a stand-alone loss module get them through autograd."""
+
+    @staticmethod
+    def forward(ctx, kind, logits, labels, bias, bias_index, hidden, lin_w, lin_b, smooth_param, constant_smooth, w, slot):
+        logits, labels = logits.contiguous(), labels.contiguous()
+        if hidden is not None:
+            hidden = hidden.contiguous()
+        loss, ctx.pr = ops.debias_fwd(kind, logits, labels, bias, bias_index, hidden,
+                                      None if lin_w is None else lin_w.data, None if lin_b is None else lin_b.data,
+                                      None if smooth_param is None else smooth_param.data, constant_smooth, w,
+                                      out=slot.t if slot is not None else None)
+        ctx.params = (lin_w, lin_b, smooth_param)
+        return loss
+
+    @staticmethod
+    def backward(ctx, gout):
+        pr, params = ctx.pr, ctx.params
+        live = [p for p in params if p is not None and p.requires_grad]
+        arenas = {getattr(p, "_xg", (None,))[0] for p in live}
+        targets = None
+        if live and arenas != {None}:
+            if len(arenas) != 1 or len(live) != sum(p is not None for p in params):
+                raise RuntimeError("DebiasFn: the loss's parameters must all live in one arena and all be trained")
+            arena = arenas.pop()
+            targets = tuple(None if p is None else arena.atomic_target(p).view(-1) for p in params)
+        need = ctx.needs_input_grad
+        d_logit, d_hidden, d_w, d_b, d_s = ops.debias_bwd(pr, gout.contiguous(), need_hidden=need[5], need_params=bool(live),
+                                                          dlogit_dtype=F32, targets=targets)
+        if targets is not None or not live:
+            d_w = d_b = d_s = None
+        else:
+            lin_w, lin_b, sp = params
+            d_w = d_w.view(lin_w.shape) if lin_w is not None and need[6] else None
+            d_b = d_b.view(lin_b.shape) if lin_b is not None and need[7] else None
+            d_s = d_s.view(sp.shape) if sp is not None and need[8] else None
+        return (None, d_logit if need[1] else None, None, None, None, d_hidden, d_w, d_b, d_s, None, None, None)
+
+
 class LossSumFn(Function):
     """loss = sum of the (already weighted) loss terms of a pass (src/vqa/vqacpv2.py:220-221, 249-250): one kernel
     instead of a framework add per ``+``; the backward hands the upstream gradient to every term unchanged."""

@@ -1146,6 +1146,130 @@ def bce_bwd(logit, target, gout, coef, dt):
     return dl
 
 
+DEBIAS_REWEIGHT, DEBIAS_BIAS_PRODUCT, DEBIAS_LEARNED_MIXIN = 1, 2, 3  # XGGM_DEBIAS_* (include/xggm.h)
+
+
+class DebiasArgs(_ct.Structure):
+    """mirror of ``xggm_debias_args`` (include/xggm.h)"""
+    _fields_ = [("logits", _ct.c_void_p), ("labels", _ct.c_void_p), ("bias", _ct.c_void_p), ("bias_row_stride", _ct.c_int64),
+                ("bias_rows", _ct.c_int64), ("bias_index", _ct.c_void_p), ("hidden", _ct.c_void_p), ("Hd", _ct.c_int),
+                ("lin_w", _ct.c_void_p), ("lin_b", _ct.c_void_p), ("smooth_param", _ct.c_void_p),
+                ("constant_smooth", _ct.c_float), ("w", _ct.c_float), ("kind", _ct.c_int), ("B", _ct.c_int), ("A", _ct.c_int),
+                ("loss", _ct.c_void_p), ("save", _ct.c_void_p), ("ws", _ct.c_void_p), ("gout", _ct.c_void_p),
+                ("d_logit", _ct.c_void_p), ("dlogit_f32", _ct.c_int), ("d_hidden", _ct.c_void_p), ("d_lin_w", _ct.c_void_p),
+                ("d_lin_b", _ct.c_void_p), ("d_smooth", _ct.c_void_p), ("part", _ct.c_void_p), ("accumulate", _ct.c_int)]
+
+
+class DebiasProblem:
+    """the operands of one debias loss (``debias_fwd`` makes it, ``debias_bwd`` reads it): checked on the host once"""
+
+    def __init__(self, kind, logits, labels, bias, bias_index, hidden, lin_w, lin_b, smooth_param, constant_smooth, w):
+        _c(logits, F32, "logits"), _c(labels, F32, "labels"), _chk(bias, F32, "bias")
+        if logits.dim() != 2 or labels.shape != logits.shape:
+            raise ValueError("debias: logits %s and labels %s must be one [B, A]" % (tuple(logits.shape), tuple(labels.shape)))
+        B, A = logits.shape
+        rows, ba, ld = _rows(bias)
+        if ba != A or (rows > 1 and ld < A):
+            raise ValueError("debias: bias %s does not have the %d answers of the logits" % (tuple(bias.shape), A))
+        if bias_index is not None:
+            _c(bias_index, torch.int64, "bias_index")
+            if bias_index.numel() != B:
+                raise ValueError("debias: bias_index holds %d entries for %d samples" % (bias_index.numel(), B))
+        elif rows != B:
+            raise ValueError("debias: bias has %d rows for %d samples (a prior table needs bias_index)" % (rows, B))
+        self.kind, self.B, self.A, self.Hd = int(kind), B, A, 0
+        self.dt = F32
+        if kind == DEBIAS_LEARNED_MIXIN:
+            if hidden is None or lin_w is None or lin_b is None:
+                raise ValueError("debias: LearnedMixin needs hidden, bias_lin.weight and bias_lin.bias")
+            _c(hidden), _c(lin_w, F32, "bias_lin.weight"), _c(lin_b, F32, "bias_lin.bias")
+            self.dt, self.Hd = hidden.dtype, hidden.shape[-1]
+            sfx(self.dt)
+            if hidden.dim() != 2 or hidden.shape[0] != B or lin_w.numel() != self.Hd or lin_b.numel() != 1:
+                raise ValueError("debias: hidden %s, bias_lin.weight %s, bias_lin.bias %s do not fit %d samples"
+                                 % (tuple(hidden.shape), tuple(lin_w.shape), tuple(lin_b.shape), B))
+        else:
+            hidden = lin_w = lin_b = None
+        if smooth_param is not None:
+            _c(smooth_param, F32, "smooth_param")
+            assert smooth_param.numel() == 1
+        for t in (labels, bias, bias_index, hidden, lin_w, lin_b, smooth_param):
+            if t is not None and t.device != logits.device:
+                raise RuntimeError("debias: all operands must live on one device")
+        self.t = dict(logits=logits, labels=labels, bias=bias, bias_index=bias_index, hidden=hidden, lin_w=lin_w, lin_b=lin_b,
+                      smooth_param=smooth_param)
+        self.bias_ld, self.bias_rows = max(ld, A), rows
+        self.constant_smooth, self.w = float(constant_smooth), float(w)
+        self.save = None
+
+    def args(self):
+        a, t = DebiasArgs(), self.t
+        for k, v in t.items():
+            setattr(a, k, ptr(v))
+        a.bias_row_stride, a.bias_rows, a.Hd = self.bias_ld, self.bias_rows, self.Hd
+        a.constant_smooth, a.w, a.kind, a.B, a.A = self.constant_smooth, self.w, self.kind, self.B, self.A
+        a.save = ptr(self.save)
+        return a
+
+
+def debias_fwd(kind, logits, labels, bias, bias_index=None, hidden=None, lin_w=None, lin_b=None, smooth_param=None,
+               constant_smooth=0.0, w=0.0, out=None, save=None):
+    """ReweightByInvBias / BiasProduct / LearnedMixin (``DEBIAS_*``) on fp32 logits, labels and bias; contract:
+    xggm_debias_fwd_* in xggm.h.  One launch.  -> (0-dim loss, DebiasProblem for ``debias_bwd``).  ``out``: a zeroed
+    1-element slot to accumulate into; ``save``: the per-row buffer (2 B floats) when the caller owns it."""
+    pr = DebiasProblem(kind, logits, labels, bias, bias_index, hidden, lin_w, lin_b, smooth_param, constant_smooth, w)
+    if save is None:
+        save = torch.empty(2 * pr.B, device=logits.device, dtype=F32)
+    _c(save, F32, "save")
+    assert save.numel() >= 2 * pr.B
+    pr.save = save
+    loss = _scalar(out, logits.device)
+    a = pr.args()
+    a.loss, a.ws = ptr(loss), ptr(sum_ws(logits.device))
+    call("xggm_debias_fwd_" + sfx(pr.dt), _ct.addressof(a), stream())
+    return loss, pr
+
+
+def debias_bwd(pr, gout=None, need_hidden=True, need_params=True, dlogit_dtype=None, targets=None):
+    """backward of ``debias_fwd``: -> (d_logit, d_hidden | None, d_lin_w | None, d_lin_b | None, d_smooth | None).
+    ``dlogit_dtype``: F32, or None = the dtype of hidden (the kernel's suffix).  ``targets`` = (d_lin_w, d_lin_b,
+    d_smooth) fp32 tensors (None entries where the loss has no such parameter) the parameter gradients are ADDED to --
+    the arena's cleared vector gradients; None: fresh tensors, overwritten.  One launch, two with parameter gradients."""
+    t, dev = pr.t, pr.t["logits"].device
+    mixin = pr.kind == DEBIAS_LEARNED_MIXIN
+    dl_dt = pr.dt if dlogit_dtype is None else dlogit_dtype
+    if dl_dt not in (pr.dt, F32):
+        raise TypeError("debias_bwd: d_logit is %s or float32" % pr.dt)
+    a = pr.args()
+    d_logit = torch.empty((pr.B, pr.A), device=dev, dtype=dl_dt)
+    a.d_logit, a.dlogit_f32 = ptr(d_logit), int(dl_dt == F32)
+    if gout is not None:
+        a.gout = ptr(_c(gout, F32, "gout"))
+    d_hidden = torch.empty_like(t["hidden"]) if (mixin and need_hidden) else None
+    a.d_hidden = ptr(d_hidden)
+    d_w = d_b = d_s = part = None
+    if need_params and (mixin or t["smooth_param"] is not None):
+        if targets is not None:
+            d_w, d_b, d_s = targets
+            a.accumulate = 1
+        else:
+            d_w = torch.empty(pr.Hd, device=dev, dtype=F32) if mixin else None
+            d_b = torch.empty(1, device=dev, dtype=F32) if mixin else None
+            d_s = torch.empty(1, device=dev, dtype=F32) if t["smooth_param"] is not None else None
+        if not mixin:
+            d_w = d_b = None
+        if t["smooth_param"] is None:
+            d_s = None
+        for x, n, name in ((d_w, pr.Hd, "d bias_lin.weight"), (d_b, 1, "d bias_lin.bias"), (d_s, 1, "d smooth_param")):
+            if x is not None:
+                _c(x, F32, name)
+                assert x.numel() == n and x.device == dev
+        part = torch.empty(2 * pr.B, device=dev, dtype=F32)
+        a.d_lin_w, a.d_lin_b, a.d_smooth, a.part = ptr(d_w), ptr(d_b), ptr(d_s), ptr(part)
+    call("xggm_debias_bwd_" + sfx(pr.dt), _ct.addressof(a), stream())
+    return d_logit, d_hidden, d_w, d_b, d_s
+
+
 # ----------------------------------------------------------------------------- optimiser / utils
 def zero_ranges(buf, ranges, rows=None):
     """zero buf[s:e] for up to 16 (s, e) element ranges per launch (all float4-aligned).  ``rows`` = (table [R, H] fp32,

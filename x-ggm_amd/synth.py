@@ -86,3 +86,34 @@ def generator_inputs(tag, kind, B, N, H, seed):
     if kind == "GAT":
         a = a * (r.random((B, N, N)) > 0.3)
     return x, np.ascontiguousarray(a.astype(np.float32))
+
+
+def debias_case(B, A, Hd=0, seed=0, bias_max=None):
+    """Inputs of one debias-loss parity case (tests/golden/make_debias_golden.py, tests/test_debias_gpu.py):
+    logits ~ 6 N(0,1) with a few entries at +-30; labels: sparse soft scores (about 1 % non-zero, values in (0, 1]);
+    bias ~ U[0,1) with entries that are exactly 0 and exactly 1 (``bias_max``: clipped to it, for the reweighting loss
+    whose weights 1 - bias must not all vanish); with ``Hd``: hidden ~ N(0,1) [B, Hd], bias_lin.weight ~ 0.05 N(0,1)
+    [1, Hd], bias_lin.bias ~ 0.3 N(0,1) [1].  All float32."""
+    r = _rng(seed, "debias_case:%d:%d:%d" % (B, A, Hd))
+    n = B * A
+    logits = (6.0 * r.standard_normal((B, A), dtype=np.float32)).astype(np.float32)
+    flat = logits.reshape(-1)
+    hot = r.choice(n, size=min(6, n), replace=False)
+    flat[hot] = np.where(np.arange(hot.size) % 2 == 0, 30.0, -30.0).astype(np.float32)
+    labels = np.zeros((B, A), dtype=np.float32)
+    k = max(1, n // 100)
+    pos = r.choice(n, size=k, replace=False)
+    labels.reshape(-1)[pos] = (1.0 - r.random(k, dtype=np.float32)).astype(np.float32)  # (0, 1]
+    bias = r.random((B, A), dtype=np.float32)
+    e = max(1, n // 50) if n >= 2 else 0
+    ends = r.choice(n, size=2 * e, replace=False) if e else np.zeros(0, dtype=np.int64)
+    bias.reshape(-1)[ends[:e]] = 0.0
+    bias.reshape(-1)[ends[e:]] = 1.0
+    if bias_max is not None:
+        bias = np.minimum(bias, np.float32(bias_max))
+    out = dict(logits=logits, labels=labels, bias=np.ascontiguousarray(bias, dtype=np.float32))
+    if Hd:
+        out["hidden"] = r.standard_normal((B, Hd), dtype=np.float32)
+        out["lin_w"] = (0.05 * r.standard_normal((1, Hd), dtype=np.float32)).astype(np.float32)
+        out["lin_b"] = (0.3 * r.standard_normal((1,), dtype=np.float32)).astype(np.float32)
+    return out

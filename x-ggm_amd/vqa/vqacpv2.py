@@ -80,6 +80,9 @@ def enable_data_parallel(model, group=None, wire_dtype=None, overlap=None, zero1
     import os
     import torch.distributed as dist
     from ..dist import GradSync, broadcast_params
+    if zero1 and getattr(model, "debias_loss", None) is not None:
+        raise RuntimeError("the sharded update (zero1=True) does not support an attached debias loss; use the replicated "
+                           "update")
     rt = runtime_of(model)
     broadcast_params(rt.arena, group)
     rank = dist.get_rank(group) if dist.is_initialized() else 0
@@ -130,20 +133,70 @@ def _sync_grads(model):
         gs.sync(active_ranges(runtime_of(model).arena))
 
 
-def forward_backward_plain(model, bce_loss, feats, boxes, sent, target, between=None):
+def attach_debias_loss(model, loss):
+    """train ``model`` (a VQAModel / GQAModel) with a debias answer loss -- a ``module.vqa_debias_loss_functions``
+    instance (Plain, ReweightByInvBias, BiasProduct, LearnedMixin) -- in place of BCEWithLogits x answers: sets
+    ``model.debias_loss = loss``.  Every pass (``forward_backward_plain`` / ``_ggm``, ``plain_pass``, ``ggm_pass``,
+    ``train_iteration``, ``engine.CapturedTrainer``) then hands the loss the tensor that enters ``logit_fc`` as ``hidden``,
+    the logits, the target and the batch's ``"bias"`` ([B, A] fp32) or ``"bias_index"`` ([B] int64 rows of
+    ``loss.bias_table``, see ``answer_prior_table`` / ``set_bias_table``).
+    Call it BEFORE the first forward (and before the optimiser is made): the loss's parameters (bias_lin.weight,
+    bias_lin.bias, smooth_param) then join the parameter arena as the group ``debias_loss`` -- vector-class members: fp32
+    gradient, no bf16 shadow read -- and the fused update trains them.  Afterwards the arena's layout is fixed:
+    RuntimeError.  Under ``make_optimizer(..., no_decay=NO_DECAY)`` all three names contain "bias" (de-bias-loss) and land
+    in the undecayed group: intended, they are a bias, a gate and a scalar.
+    Not supported together with the sharded update (``enable_data_parallel(zero1=True)``) or
+    ``CapturedTrainer(packed_spec=)``; replicated data parallelism works."""
+    from ..module.vqa_debias_loss_functions import DebiasLossFn
+    from ..runtime import root_of
+    if not isinstance(loss, DebiasLossFn):
+        raise TypeError("attach_debias_loss: expected a module.vqa_debias_loss_functions loss, got %s" % type(loss).__name__)
+    root = root_of(model)
+    if getattr(root, "_xg_rt", None) is not None:
+        raise RuntimeError("attach_debias_loss must run before the first forward: the parameter arena has been laid out "
+                           "and the loss's parameters can no longer join it")
+    p = next(model.parameters(), None)
+    if p is not None:
+        loss.to(p.device)
+    model.debias_loss = loss
+    return model
+
+
+def _head_loss(model, bce_loss, hidden, logit, target, bias, bias_index, **slot):
+    """the answer-head loss of a pass at the scale BCE x answers: the attached debias loss, else ``bce_loss``"""
+    dl = getattr(model, "debias_loss", None)
+    if dl is None:
+        return bce_loss(logit, target, scale=target.size(1), **slot)
+    if dl.needs_bias and bias is None and bias_index is None:
+        raise ValueError("the model has a %s attached: the batch needs \"bias\" ([B, A] fp32) or \"bias_index\" ([B] int64)"
+                         % type(dl).__name__)
+    return dl(hidden, logit, bias, target, bias_index=bias_index, **slot)
+
+
+def _head_inputs(model, x):
+    """(input of ``logit_fc``, ``hidden`` of the attached loss): two consumers of one tensor go through ``XF.fan_out``"""
+    dl = getattr(model, "debias_loss", None)
+    if dl is not None and dl.needs_hidden:
+        return XF.fan_out(x, 2)
+    return x, None
+
+
+def forward_backward_plain(model, bce_loss, feats, boxes, sent, target, between=None, bias=None, bias_index=None):
     """step A up to backward: src/vqa/vqacpv2.py:170-174.  ``between``: callback between the two backward
-    stages when the runtime cuts the graph (Runtime.backward)."""
+    stages when the runtime cuts the graph (Runtime.backward).  ``bias`` / ``bias_index``: for an attached debias loss
+    (``attach_debias_loss``)."""
     model.zero_grad()
     rt = runtime_of(model)
     _, _, x = model(feats, boxes, sent)
+    x, hidden = _head_inputs(model, x)
     logit = model.logit_fc(x)
-    loss = bce_loss(logit, target, scale=target.size(1))
+    loss = _head_loss(model, bce_loss, hidden, logit, target, bias, bias_index)
     rt.backward(loss, between)
     return loss.detach(), logit.detach()
 
 
 def forward_backward_ggm(model, bce_loss, feats, boxes, sent, target, adj_true, branch, sigma=1.0, kl_weight=8.0,
-                         randn=None, between=None):
+                         randn=None, between=None, bias=None, bias_index=None):
     """step B up to backward: relation generation (branch 'rel', src/vqa/vqacpv2.py:195-222) or
     representation generation ('node', :228-251).  ``randn`` injects the Gaussian draw
     (parity tests); None = in-kernel Philox."""
@@ -178,9 +231,9 @@ def forward_backward_ggm(model, bce_loss, feats, boxes, sent, target, adj_true, 
         loss_grad = loss_func(node_dsm, feat_grad, sigma=sigma, scale=w_dsm, slot=rt.scalar_slot())
     else:
         raise ValueError(branch)
-    x_gen = model.fusion_fc(XF.PoolConcatFn.apply(x_fuse, node_feats))
+    x_gen, hidden = _head_inputs(model, model.fusion_fc(XF.PoolConcatFn.apply(x_fuse, node_feats)))
     logit = model.logit_fc(x_gen)
-    bce = bce_loss(logit, target, scale=A, slot=rt.scalar_slot())
+    bce = _head_loss(model, bce_loss, hidden, logit, target, bias, bias_index, slot=rt.scalar_slot())
     loss = XF.LossSumFn.apply(bce, d_loss, loss_grad)
     rt.backward(loss, between)
     # reported as the reference logs them: bce = BCE * A, d_loss = KL * A, loss_grad = the unweighted DSM term
@@ -237,9 +290,10 @@ def log_pass(train_log, model, optim, kind, loss, total, terms=None):
     ops.train_log_append(train_log, T.KIND_OF[kind], cols, mul, step=None if gi is None else arena.steps[gi:gi + 1])
 
 
-def plain_pass(model, optim, bce_loss, feats, boxes, sent, target, clip=5.0, advance=False, train_log=None):
+def plain_pass(model, optim, bce_loss, feats, boxes, sent, target, clip=5.0, advance=False, train_log=None, bias=None,
+               bias_index=None):
     """``train_log`` = an ``engine.TrainLog``: the pass ends with one ``log_pass`` behind its update (None: no launch)"""
-    out = forward_backward_plain(model, bce_loss, feats, boxes, sent, target)
+    out = forward_backward_plain(model, bce_loss, feats, boxes, sent, target, bias=bias, bias_index=bias_index)
     _sync_grads(model)
     total = clip_and_step(model, optim, clip, advance)
     if train_log is not None:
@@ -248,8 +302,9 @@ def plain_pass(model, optim, bce_loss, feats, boxes, sent, target, clip=5.0, adv
 
 
 def ggm_pass(model, optim, bce_loss, feats, boxes, sent, target, adj_true, branch, sigma=1.0, kl_weight=8.0,
-             randn=None, clip=5.0, advance=False, train_log=None):
-    out = forward_backward_ggm(model, bce_loss, feats, boxes, sent, target, adj_true, branch, sigma, kl_weight, randn)
+             randn=None, clip=5.0, advance=False, train_log=None, bias=None, bias_index=None):
+    out = forward_backward_ggm(model, bce_loss, feats, boxes, sent, target, adj_true, branch, sigma, kl_weight, randn,
+                               bias=bias, bias_index=bias_index)
     _sync_grads(model)
     total = clip_and_step(model, optim, clip, advance)
     if train_log is not None:
@@ -280,15 +335,16 @@ def train_iteration(model, optim, bce_loss, batch, delta=5, sigma=1.0, order="vq
     if branch is None:
         branch = pick_branch(delta, model=model)
     args = (batch["feats"], batch["boxes"], batch["sent"], batch["target"])
+    kw = dict(clip=clip, advance=True, train_log=train_log)
+    if getattr(model, "debias_loss", None) is not None:  # the bias of the attached loss travels in the batch
+        kw.update(bias=batch.get("bias"), bias_index=batch.get("bias_index"))
     out = {}
     if order == "vqa":
-        out["loss_plain"], out["logit"] = plain_pass(model, optim, bce_loss, *args, clip=clip, advance=True, train_log=train_log)
-        out["loss_ggm"], _, ex = ggm_pass(model, optim, bce_loss, *args, batch["adj_true"], branch, sigma, 8.0,
-                                          clip=clip, advance=True, train_log=train_log)
+        out["loss_plain"], out["logit"] = plain_pass(model, optim, bce_loss, *args, **kw)
+        out["loss_ggm"], _, ex = ggm_pass(model, optim, bce_loss, *args, batch["adj_true"], branch, sigma, 8.0, **kw)
     else:
-        out["loss_ggm"], _, ex = ggm_pass(model, optim, bce_loss, *args, batch["adj_true"], branch, sigma, 12.0,
-                                          clip=clip, advance=True, train_log=train_log)
-        out["loss_plain"], out["logit"] = plain_pass(model, optim, bce_loss, *args, clip=clip, advance=True, train_log=train_log)
+        out["loss_ggm"], _, ex = ggm_pass(model, optim, bce_loss, *args, batch["adj_true"], branch, sigma, 12.0, **kw)
+        out["loss_plain"], out["logit"] = plain_pass(model, optim, bce_loss, *args, **kw)
     out.update((k, v) for k, v in ex.items() if k != "bce")  # the BCE slot is ``log_pass``'s: the keys stay the reference's
     out["branch"] = branch
     _tick_guard(model)
@@ -345,6 +401,24 @@ def split_param_names(names, lr, no_decay=None, layer_decay=None, llayers=9, xla
             g["weight_decay"] = 0.0
         out.append(g)
     return out
+
+
+def answer_prior_table(targets, group_ids, n_groups):
+    """the usual bias of the ensemble losses: per group (question type) the mean target score of every answer over the
+    group's training samples.  ``targets``: [n, A] soft scores, ``group_ids``: [n] ints in [0, n_groups) -> fp32
+    [n_groups, A]; a group without samples gets zeros.  Host side, numpy: run once over the training set, hand the table
+    to ``loss.set_bias_table`` and put each sample's group id into the batch as ``"bias_index"``."""
+    import numpy as np
+    targets = np.asarray(targets, dtype=np.float64)
+    group_ids = np.asarray(group_ids, dtype=np.int64).reshape(-1)
+    if targets.ndim != 2 or group_ids.shape[0] != targets.shape[0]:
+        raise ValueError("answer_prior_table: targets %s and group_ids %s do not match" % (targets.shape, group_ids.shape))
+    if group_ids.size and (group_ids.min() < 0 or group_ids.max() >= n_groups):
+        raise ValueError("answer_prior_table: group ids must lie in [0, %d)" % n_groups)
+    sums = np.zeros((int(n_groups), targets.shape[1]), dtype=np.float64)
+    np.add.at(sums, group_ids, targets)
+    counts = np.bincount(group_ids, minlength=int(n_groups)).astype(np.float64)
+    return (sums / np.maximum(counts, 1.0)[:, None]).astype(np.float32)
 
 
 def make_optimizer(model, lr, t_total, warmup=0.1, optim='bert', no_decay=None, layer_decay=None):
