@@ -602,6 +602,50 @@ int xggm_debias_fwd_f32(const xggm_debias_args* args, xggm_stream_t stream);
 int xggm_debias_fwd_bf16(const xggm_debias_args* args, xggm_stream_t stream);
 int xggm_debias_bwd_f32(const xggm_debias_args* args, xggm_stream_t stream);
 int xggm_debias_bwd_bf16(const xggm_debias_args* args, xggm_stream_t stream);
+/* Answer losses with a softmax over the answer axis: Focal of src/module/vqa_debias_loss_functions.py:74-81 and the
+ * nn.CrossEntropyLoss(ignore_index=-1) of --mceLoss (src/param.py:78, src/gqa/gqa_ood.py:116).  z = logits, y = labels
+ * (fp32 [B, A], rows 4-byte aligned are enough), p = softmax(z) over a row:
+ *   FOCAL   c = (1 - softmax(b))^2, b the sample's bias row (bias, bias_row_stride, bias_rows, bias_index as in
+ *           xggm_debias_args: row bias_index[r], clamped into [0, bias_rows), of a small prior table);  f = log(p + 1e-5) c
+ *           *loss += (1 / B) sum_{r,a} [max(f, 0) - f y + log1p(exp(-|f|))]     (BCEWithLogits(f, y), mean, times A: :79-80)
+ *           d_logit[r][j] = u_j - p_j sum_a u_a,  u = *gout (sigmoid(f) - y) / B * c p / (p + 1e-5); bias and labels get none.
+ *           `scale`, `ignore_index` and `label_index` are not read.
+ *   CE      label_r = label_index[r] when label_index is given, else the FIRST index of the maximum of labels[r]
+ *           (torch.max(1)), or ignore_index when that maximum is <= 0 (an answer outside the vocabulary).  Rows whose label
+ *           equals ignore_index are ignored; a label_index entry outside [0, A) that is not ignore_index cannot be refused
+ *           from the host: the kernel treats that row as ignored too.
+ *           *loss += scale * sum_valid (logsumexp(z_r) - z_r[label_r]) / n_valid
+ *           d_logit = *gout * scale / n_valid * (p - onehot(label)) on valid rows, exactly 0 on ignored rows.
+ *           No valid row: the loss is NaN (0 / 0, torch's mean over nothing) and d_logit all zero.
+ * forward: ONE launch of min(B, 128) workgroups; needs loss, ws (XGGM_SUM_WS_FLOATS floats, ws[0] == 0 at launch, left 0)
+ * and save (5 B + 1 floats: per row max z, log sum exp(z - max), max b, sum exp(b - max b); B int32 labels, -1 = ignored;
+ * n_valid).  backward: ONE launch that reads `save`; accumulate != 0 adds to d_logit instead of overwriting.
+ * No floating-point atomics, every sum in a fixed order; no allocation, no host synchronisation: legal inside a stream
+ * capture.  Refused before any launch: a null struct, unknown kind, B or A <= 0, null logits, CE with neither labels nor
+ * label_index, FOCAL without labels or bias, a bias_row_stride < A, a bias of fewer than B rows without bias_index, a
+ * missing save; forward without loss or ws; backward without d_logit or gout. */
+#define XGGM_SOFTMAX_FOCAL 1
+#define XGGM_SOFTMAX_CE 2
+typedef struct xggm_softmax_loss_args {
+    const float* logits;        /* [B, A] */
+    const float* labels;        /* [B, A] soft scores; CE: may be NULL when label_index is given */
+    const int64_t* label_index; /* CE: [B] class per sample (takes precedence over labels), or NULL */
+    const float* bias;          /* FOCAL: [bias_rows, >= A] */
+    int64_t bias_row_stride;    /* floats between two rows of bias, >= A */
+    int64_t bias_rows;          /* rows of bias: B, or the groups of a prior table */
+    const int64_t* bias_index;  /* [B] row of bias per sample, or NULL */
+    int64_t ignore_index;       /* CE: the label of rows that do not count */
+    float scale;                /* CE: factor on the mean */
+    int kind, B, A;
+    float* loss;                /* forward: the slot the loss is added to */
+    float* ws;                  /* forward: XGGM_SUM_WS_FLOATS floats */
+    float* save;                /* 5 B + 1 floats: written by the forward, read by the backward */
+    const float* gout;          /* backward: upstream gradient, DEVICE scalar */
+    float* d_logit;             /* backward: [B, A] fp32 */
+    int accumulate;
+} xggm_softmax_loss_args;
+int xggm_softmax_loss_fwd_f32(const xggm_softmax_loss_args* args, xggm_stream_t stream);
+int xggm_softmax_loss_bwd_f32(const xggm_softmax_loss_args* args, xggm_stream_t stream);
 
 /* ---- preprocessing that feeds the path ----------------------------------------------------
  * adj_true of every sample: data/preprocess/vqa/compute_adjacency.py:38-45 (compute_cosin_sim_v2) + :90.

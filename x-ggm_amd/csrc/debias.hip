@@ -37,38 +37,6 @@ __device__ __forceinline__ float sigmoid_stable(float x) {
     return x >= 0.f ? r : t * r;
 }
 
-// ordered_grid_sum (common.h) for TWO values per workgroup: partials in ws[HEAD + 2 blk], ws[HEAD + 2 blk + 1], the
-// workgroup that draws the last ticket adds them in index order.  nblk <= ROW_GRID.  Call from every thread of every
-// workgroup; a, b are read from thread 0; true on thread 0 of the finishing workgroup.
-__device__ __forceinline__ bool ordered_grid_sum2(float a, float b, float* ws, int nblk, int blk, float& ta, float& tb) {
-    __shared__ int s_last;
-    __shared__ float s_part[2 * ROW_GRID];
-    unsigned* counter = reinterpret_cast<unsigned*>(ws);
-    if (threadIdx.x == 0) {
-        __hip_atomic_store(ws + SUM_WS_HEAD + 2 * blk, a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(ws + SUM_WS_HEAD + 2 * blk + 1, b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // both stores acknowledged before the ticket (see common.h)
-        const unsigned t = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        s_last = (t == (unsigned)nblk - 1u) ? 1 : 0;
-    }
-    __syncthreads();
-    if (!s_last) return false;
-    if ((int)threadIdx.x < 2 * nblk)
-        s_part[threadIdx.x] = __hip_atomic_load(ws + SUM_WS_HEAD + threadIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __syncthreads();
-    if (threadIdx.x != 0) return false;
-    float ra = 0.f, rb = 0.f;
-    for (int i = 0; i < nblk; ++i) {  // index order, one thread
-        ra += s_part[2 * i];
-        rb += s_part[2 * i + 1];
-    }
-    __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // ready for the next launch
-    ta = ra;
-    tb = rb;
-    return true;
-}
-
 struct Args {  // xggm_debias_args by value, pointers typed
     const float *logits, *labels, *bias;
     const int64_t* bias_index;

@@ -227,7 +227,8 @@ class CapturedTrainer:
             raise ValueError("CapturedTrainer: answer_log needs scores (AnswerLog(with_scores=True))")
         self.rt = runtime_of(model)
         self.static_flat = None
-        if packed_spec is not None and getattr(model, "debias_loss", None) is not None:
+        # (a loss that reads no bias -- Plain, CrossEntropy -- needs nothing beyond the loader's fields)
+        if packed_spec is not None and getattr(getattr(model, "debias_loss", None), "needs_bias", False):
             raise ValueError("CapturedTrainer: packed_spec carries no bias for the attached debias loss; hand batches over "
                              "with load_batch")
         if packed_spec is not None:

@@ -1052,6 +1052,24 @@ class DebiasFn(Function):
         return (None, d_logit if need[1] else None, None, None, None, d_hidden, d_w, d_b, d_s, None, None, None)
 
 
+class SoftmaxLossFn(Function):
+    """Focal (src/module/vqa_debias_loss_functions.py:74-81) / cross-entropy with ignore_index (src/gqa/gqa_ood.py:116) on
+    fp32 logits: one launch forward, one backward (xggm_softmax_loss_* in xggm.h).  The gradient goes to the logits only;
+    ``labels`` is [B, A] soft scores or, for cross-entropy, [B] int64 classes."""
+
+    @staticmethod
+    def forward(ctx, kind, logits, labels, bias=None, bias_index=None, ignore_index=-1, scale=1.0, slot=None):
+        logits, labels = logits.contiguous(), labels.contiguous()
+        index = labels if labels.dim() == 1 else None
+        loss, ctx.pr = ops.softmax_loss_fwd(kind, logits, None if index is not None else labels, index, bias, bias_index,
+                                            ignore_index, scale, out=slot.t if slot is not None else None)
+        return loss
+
+    @staticmethod
+    def backward(ctx, gout):
+        return (None, ops.softmax_loss_bwd(ctx.pr, gout.contiguous())) + (None,) * 6
+
+
 class LossSumFn(Function):
     """loss = sum of the (already weighted) loss terms of a pass (src/vqa/vqacpv2.py:220-221, 249-250): one kernel
     instead of a framework add per ``+``; the backward hands the upstream gradient to every term unchanged."""

@@ -2,7 +2,7 @@
 pass second.  Thin front-end over xggm_amd.vqa.vqacpv2."""
 from ..vqa.vqacpv2 import (loss_func, compute_kl_loss, BCEWithLogitsLoss, plain_pass, ggm_pass, predict, evaluate,  # noqa: F401
                            train_iteration as _train_iteration, make_optimizer, attach_debias_loss,  # noqa: F401
-                           answer_prior_table)  # noqa: F401
+                           answer_prior_table, make_answer_loss)  # noqa: F401
 
 
 def train_iteration(model, optim, bce_loss, batch, delta=5, sigma=1.0, branch=None, clip=5.0, train_log=None):

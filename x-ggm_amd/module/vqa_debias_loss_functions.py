@@ -3,7 +3,8 @@
 Constructor signatures and defaults, ``to_json()`` and the ``state_dict`` keys (``bias_lin.weight``, ``bias_lin.bias``,
 ``smooth_param``) are the reference's; the arithmetic is one fused HIP forward and one fused backward
 (``functional.DebiasFn`` / xggm_debias_* in xggm.h), ``Plain`` is the existing ``BCEFn`` with ``scale = A``.
-``Focal`` (:74-81) is left out: it needs row softmaxes, a different kernel.
+``Focal`` (:74-81) needs row softmaxes, a different kernel family: it lives beside cross-entropy in ``module.answer_losses``
+(a ``DebiasLossFn`` like the classes here, attached the same way).
 
 ``forward(hidden, logits, bias, labels, *, bias_index=None, slot=None)`` keeps the reference's four positional
 arguments.  ``bias_index`` (int64 [B]): row of ``bias`` per sample -- ``bias`` is then a small [groups, A] prior table

@@ -1270,6 +1270,115 @@ def debias_bwd(pr, gout=None, need_hidden=True, need_params=True, dlogit_dtype=N
     return d_logit, d_hidden, d_w, d_b, d_s
 
 
+SOFTMAX_FOCAL, SOFTMAX_CE = 1, 2  # XGGM_SOFTMAX_* (include/xggm.h)
+
+
+class SoftmaxLossArgs(_ct.Structure):
+    """mirror of ``xggm_softmax_loss_args`` (include/xggm.h)"""
+    _fields_ = [("logits", _ct.c_void_p), ("labels", _ct.c_void_p), ("label_index", _ct.c_void_p), ("bias", _ct.c_void_p),
+                ("bias_row_stride", _ct.c_int64), ("bias_rows", _ct.c_int64), ("bias_index", _ct.c_void_p),
+                ("ignore_index", _ct.c_int64), ("scale", _ct.c_float), ("kind", _ct.c_int), ("B", _ct.c_int), ("A", _ct.c_int),
+                ("loss", _ct.c_void_p), ("ws", _ct.c_void_p), ("save", _ct.c_void_p), ("gout", _ct.c_void_p),
+                ("d_logit", _ct.c_void_p), ("accumulate", _ct.c_int)]
+
+
+class SoftmaxLossProblem:
+    """the operands of one softmax answer loss (``softmax_loss_fwd`` makes it, ``softmax_loss_bwd`` reads it): checked on
+    the host once.  ``save``: what the forward left for the backward (5 B + 1 floats, xggm.h)."""
+
+    def __init__(self, kind, logits, labels, label_index, bias, bias_index, ignore_index, scale):
+        _c(logits, F32, "logits")
+        if logits.dim() != 2:
+            raise ValueError("softmax_loss: logits %s must be [B, A]" % (tuple(logits.shape),))
+        B, A = logits.shape
+        if kind not in (SOFTMAX_FOCAL, SOFTMAX_CE):
+            raise ValueError("softmax_loss: unknown kind %r" % (kind,))
+        if labels is not None:
+            _c(labels, F32, "labels")
+            if labels.shape != logits.shape:
+                raise ValueError("softmax_loss: labels %s do not fit logits %s" % (tuple(labels.shape), tuple(logits.shape)))
+        if label_index is not None:
+            _c(label_index, torch.int64, "label_index")
+            if kind != SOFTMAX_CE or label_index.numel() != B:
+                raise ValueError("softmax_loss: label_index is cross-entropy's [B] int64 (%d entries, %d samples)"
+                                 % (label_index.numel(), B))
+        if kind == SOFTMAX_CE:
+            if labels is None and label_index is None:
+                raise ValueError("softmax_loss: cross-entropy needs labels [B, A] or label_index [B]")
+            bias = bias_index = None
+        elif labels is None or bias is None:
+            raise ValueError("softmax_loss: Focal needs labels and bias")
+        self.bias_ld = self.bias_rows = 0
+        if bias is not None:
+            _chk(bias, F32, "bias")
+            rows, ba, ld = _rows(bias)
+            if ba != A or (rows > 1 and ld < A):
+                raise ValueError("softmax_loss: bias %s does not have the %d answers of the logits" % (tuple(bias.shape), A))
+            if bias_index is not None:
+                _c(bias_index, torch.int64, "bias_index")
+                if bias_index.numel() != B:
+                    raise ValueError("softmax_loss: bias_index holds %d entries for %d samples" % (bias_index.numel(), B))
+            elif rows != B:
+                raise ValueError("softmax_loss: bias has %d rows for %d samples (a prior table needs bias_index)" % (rows, B))
+            self.bias_ld, self.bias_rows = max(ld, A), rows
+        for t in (labels, label_index, bias, bias_index):
+            if t is not None and t.device != logits.device:
+                raise RuntimeError("softmax_loss: all operands must live on one device")
+        self.kind, self.B, self.A = int(kind), B, A
+        self.ignore_index, self.scale = int(ignore_index), float(scale)
+        self.t = dict(logits=logits, labels=labels, label_index=label_index, bias=bias, bias_index=bias_index)
+        self.save = None
+
+    def args(self):
+        a = SoftmaxLossArgs()
+        for k, v in self.t.items():
+            setattr(a, k, ptr(v))
+        a.bias_row_stride, a.bias_rows, a.ignore_index, a.scale = self.bias_ld, self.bias_rows, self.ignore_index, self.scale
+        a.kind, a.B, a.A, a.save = self.kind, self.B, self.A, ptr(self.save)
+        return a
+
+    def labels_int32(self):
+        """the int32 label per row the forward left in ``save`` (cross-entropy; -1: ignored)"""
+        return self.save[4 * self.B:5 * self.B].view(torch.int32)
+
+    def n_valid(self):
+        return self.save[5 * self.B]
+
+
+def softmax_loss_fwd(kind, logits, labels=None, label_index=None, bias=None, bias_index=None, ignore_index=-1, scale=1.0,
+                     out=None, save=None):
+    """Focal / cross-entropy (``SOFTMAX_*``) on fp32 logits; contract: xggm_softmax_loss_fwd_f32 in xggm.h.  One launch.
+    -> (0-dim loss, SoftmaxLossProblem for ``softmax_loss_bwd``).  ``out``: a zeroed 1-element slot to accumulate into;
+    ``save``: the 5 B + 1 floats between forward and backward when the caller owns them."""
+    pr = SoftmaxLossProblem(kind, logits, labels, label_index, bias, bias_index, ignore_index, scale)
+    if save is None:
+        save = torch.empty(5 * pr.B + 1, device=logits.device, dtype=F32)
+    _c(save, F32, "save")
+    assert save.numel() >= 5 * pr.B + 1 and save.device == logits.device
+    pr.save = save
+    loss = _scalar(out, logits.device)
+    a = pr.args()
+    a.loss, a.ws = ptr(loss), ptr(sum_ws(logits.device))
+    call("xggm_softmax_loss_fwd_f32", _ct.addressof(a), stream())
+    return loss, pr
+
+
+def softmax_loss_bwd(pr, gout, d_logit=None):
+    """backward of ``softmax_loss_fwd``: -> d_logit [B, A] fp32 (``*gout`` x d loss / d logits; exactly 0 on the rows
+    cross-entropy ignores).  ``d_logit``: an existing fp32 [B, A] gradient to ADD to (None: a fresh tensor, overwritten).
+    One launch."""
+    a = pr.args()
+    if d_logit is None:
+        d_logit = torch.empty((pr.B, pr.A), device=pr.t["logits"].device, dtype=F32)
+    else:
+        _c(d_logit, F32, "d_logit")
+        assert tuple(d_logit.shape) == (pr.B, pr.A) and d_logit.device == pr.t["logits"].device
+        a.accumulate = 1
+    a.d_logit, a.gout = ptr(d_logit), ptr(_c(gout, F32, "gout"))
+    call("xggm_softmax_loss_bwd_f32", _ct.addressof(a), stream())
+    return d_logit
+
+
 # ----------------------------------------------------------------------------- optimiser / utils
 def zero_ranges(buf, ranges, rows=None):
     """zero buf[s:e] for up to 16 (s, e) element ranges per launch (all float4-aligned).  ``rows`` = (table [R, H] fp32,

@@ -33,6 +33,7 @@ def build_parser():
     p.add_argument("--delta", type=int, default=5)
     p.add_argument("--fromScratch", dest="from_scratch", action="store_const", default=False, const=True)
     p.add_argument("--multiGPU", action="store_const", default=False, const=True)
+    p.add_argument("--mceLoss", dest="mce_loss", action="store_const", default=False, const=True)  # src/param.py:78
     p.add_argument("--vocab", dest="vocab_path", type=str, default=None,
                    help="local BERT vocab.txt (the reference downloads it; offline it must be given)")
     return p

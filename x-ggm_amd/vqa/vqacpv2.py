@@ -135,7 +135,8 @@ def _sync_grads(model):
 
 def attach_debias_loss(model, loss):
     """train ``model`` (a VQAModel / GQAModel) with a debias answer loss -- a ``module.vqa_debias_loss_functions``
-    instance (Plain, ReweightByInvBias, BiasProduct, LearnedMixin) -- in place of BCEWithLogits x answers: sets
+    instance (Plain, ReweightByInvBias, BiasProduct, LearnedMixin) or one of ``module.answer_losses`` (Focal; CrossEntropy,
+    the reference's --mceLoss, ``make_answer_loss``) -- in place of BCEWithLogits x answers: sets
     ``model.debias_loss = loss``.  Every pass (``forward_backward_plain`` / ``_ggm``, ``plain_pass``, ``ggm_pass``,
     ``train_iteration``, ``engine.CapturedTrainer``) then hands the loss the tensor that enters ``logit_fc`` as ``hidden``,
     the logits, the target and the batch's ``"bias"`` ([B, A] fp32) or ``"bias_index"`` ([B] int64 rows of
@@ -145,8 +146,8 @@ def attach_debias_loss(model, loss):
     gradient, no bf16 shadow read -- and the fused update trains them.  Afterwards the arena's layout is fixed:
     RuntimeError.  Under ``make_optimizer(..., no_decay=NO_DECAY)`` all three names contain "bias" (de-bias-loss) and land
     in the undecayed group: intended, they are a bias, a gate and a scalar.
-    Not supported together with the sharded update (``enable_data_parallel(zero1=True)``) or
-    ``CapturedTrainer(packed_spec=)``; replicated data parallelism works."""
+    Not supported together with the sharded update (``enable_data_parallel(zero1=True)``); ``CapturedTrainer(packed_spec=)``
+    takes the losses that read no bias (Plain, CrossEntropy) only; replicated data parallelism works."""
     from ..module.vqa_debias_loss_functions import DebiasLossFn
     from ..runtime import root_of
     if not isinstance(loss, DebiasLossFn):
@@ -160,6 +161,15 @@ def attach_debias_loss(model, loss):
         loss.to(p.device)
     model.debias_loss = loss
     return model
+
+
+def make_answer_loss(args):
+    """the loss to attach for the parsed flags ``args`` (``param.parse_args``): ``CrossEntropy()`` -- the reference's
+    nn.CrossEntropyLoss(ignore_index=-1), src/gqa/gqa_ood.py:116 -- under ``--mceLoss``, else None (BCEWithLogits x answers)"""
+    if getattr(args, "mce_loss", False):
+        from ..module.answer_losses import CrossEntropy
+        return CrossEntropy()
+    return None
 
 
 def _head_loss(model, bce_loss, hidden, logit, target, bias, bias_index, **slot):
