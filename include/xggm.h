@@ -647,6 +647,113 @@ typedef struct xggm_softmax_loss_args {
 int xggm_softmax_loss_fwd_f32(const xggm_softmax_loss_args* args, xggm_stream_t stream);
 int xggm_softmax_loss_bwd_f32(const xggm_softmax_loss_args* args, xggm_stream_t stream);
 
+/* Losses of LXMERT pre-training: LXRTPretraining.forward, src/lxrt/modeling.py:955-1061 (trained by
+ * src/pretrain/lxmert_pretrain.py:221-306).  The matched loss (:1017-1023) and the QA loss (:1047-1059) are
+ * xggm_softmax_loss_*_f32 with XGGM_SOFTMAX_CE; the masked-LM loss (:1009-1016) and the object losses (:1024-1046) are here.
+ *
+ * xggm_mlm_select: the rows of x [M, H] (M = B T, the language stream) whose masked_lm_label counts, in ascending row
+ * order: row_index[j], label[j] (int32 [cap]) for j < *n, -1 behind; out [cap, H] holds those rows of x and exact zeros in
+ * rows [*n, cap), so a product over all cap rows is harmless.  A row counts when its label is not ignore_index AND lies in
+ * [0, V): as in XGGM_SOFTMAX_CE, a label outside the vocabulary cannot be refused from the host and the row is ignored.
+ * The order comes from a prefix count (integers, no atomics): the same labels give the same list.  The host reads nothing.
+ * More than cap rows: *n = cap, the list holds the FIRST cap rows and *overflow = 1 (else 0); xggm_vocab_ce_fwd_* turns
+ * that flag into a NaN loss, so a capacity that is too small is never a silent truncation.
+ * One launch of ceil(M / 256) workgroups; each counts the labels in front of its chunk itself, so the cost grows with
+ * M^2 / 256 label reads: M = B T is a few thousand in pre-training, and M above XGGM_MLM_SELECT_MAX_ROWS is refused.  x and out 16-byte aligned, H * sizeof(element) a multiple of 16.
+ * xggm_mlm_scatter_*: the gather's backward -- out [M, H] = row j of src [cap, H] at row row_index[j] (j < *n), exact zeros
+ * elsewhere; one launch, every row written once. */
+#define XGGM_MLM_SELECT_MAX_ROWS 65536
+typedef struct xggm_mlm_select_args {
+    const int64_t* labels;  /* [M] masked_lm_labels */
+    const void* x;          /* [M, H] */
+    int M, H, cap, V;
+    int64_t ignore_index;
+    int* row_index;         /* [cap] */
+    int* label;             /* [cap] */
+    int* n;                 /* [1] min(rows that count, cap) */
+    int* overflow;          /* [1] 1 when more than cap rows count */
+    void* out;              /* [cap, H] */
+} xggm_mlm_select_args;
+int xggm_mlm_select_f32(const xggm_mlm_select_args* args, xggm_stream_t stream);
+int xggm_mlm_select_bf16(const xggm_mlm_select_args* args, xggm_stream_t stream);
+int xggm_mlm_scatter_f32(const void* src, const int* row_index, const int* n, void* out, int M, int H, int cap,
+                         xggm_stream_t stream);
+int xggm_mlm_scatter_bf16(const void* src, const int* row_index, const int* n, void* out, int M, int H, int cap,
+                          xggm_stream_t stream);
+/* xggm_vocab_ce_*: nn.CrossEntropyLoss(ignore_index=-1) over the vocabulary (src/lxrt/modeling.py:1009-1016) on the
+ * compacted rows: logits [cap, ld] in the suffix's type with ld >= V a multiple of 16 bytes (30522 -> 30528) and a 16-byte
+ * aligned base; label int32 [cap] and *n as xggm_mlm_select left them (n is clamped into [0, cap]).
+ *   forward   *loss += sum_{r < n} (logsumexp(z_r[0:V]) - z_r[label_r]) / n;  save[2 r] = max, save[2 r + 1] = log sum
+ *             exp(z - max) of row r < n.  Every row is read once: up to XGGM_VOCAB_CE_REG_MAX columns it stays in the
+ *             registers of a 1024-thread workgroup, a longer row is folded online.  *overflow != 0 (NULL: not looked at):
+ *             the loss is NaN.  n == 0: the loss is NaN (0 / 0, torch's mean over nothing, the convention of
+ *             XGGM_SOFTMAX_CE) and the gradient all zero.
+ *   backward  ONE launch that OVERWRITES the logits with *gout (p - onehot(label)) / n in their own type, exact zeros on
+ *             rows >= n and in the columns [V, ld).  *overflow != 0: the rows < n get NaN instead -- a truncated list yields
+ *             neither a usable loss nor a usable gradient.
+ * A label entry outside [0, V) (xggm_mlm_select writes none) adds nothing to the loss and gets a zero row.
+ * No floating-point atomics, every sum in a fixed order; no allocation, no host synchronisation.  Refused before any
+ * launch: a null struct, cap <= 0, V <= 0, ld < V or not a multiple of 16 bytes, null or misaligned logits, null label / n /
+ * save; forward without loss or ws; backward without gout. */
+#define XGGM_VOCAB_CE_REG_MAX 32768
+#define XGGM_VOCAB_CE_FWD_GRID 1024 /* workgroups of the forward: more rows are walked */
+#define XGGM_VOCAB_CE_BWD_GRID 2048 /* workgroups of the backward */
+typedef struct xggm_vocab_ce_args {
+    void* logits;         /* [cap, ld]; the backward overwrites it with the gradient */
+    const int* label;     /* [cap] */
+    const int* n;         /* [1] device */
+    const int* overflow;  /* [1] device, or NULL */
+    int cap, V;
+    int64_t ld;           /* elements between two rows */
+    float* loss;          /* forward: the slot the loss is added to */
+    float* ws;            /* forward: XGGM_SUM_WS_FLOATS floats */
+    float* save;          /* 2 cap floats: written by the forward, read by the backward */
+    const float* gout;    /* backward: upstream gradient, DEVICE scalar */
+} xggm_vocab_ce_args;
+int xggm_vocab_ce_fwd_f32(const xggm_vocab_ce_args* args, xggm_stream_t stream);
+int xggm_vocab_ce_fwd_bf16(const xggm_vocab_ce_args* args, xggm_stream_t stream);
+int xggm_vocab_ce_bwd_f32(const xggm_vocab_ce_args* args, xggm_stream_t stream);
+int xggm_vocab_ce_bwd_bf16(const xggm_vocab_ce_args* args, xggm_stream_t stream);
+/* xggm_visual_loss_*: the object losses of src/lxrt/modeling.py:1024-1046, up to XGGM_VISUAL_MAX_JOBS of them in one
+ * launch over the same R = B * objects rows (--visualLosses may name any subset of obj, attr, feat).  Per job, with
+ * c_r = mask_conf[r] (fp32 [R]) and scores [R, W] in the suffix's type:
+ *   XGGM_VISUAL_CE  l_r = logsumexp(s_r) - s_r[label_index[r]], 0 where the label is ignore_index (or outside [0, W))
+ *   XGGM_VISUAL_L2  l_r = mean_i SmoothL1(s_r[i] - target[r][i]), beta = 1, target fp32 [R, W]
+ *   *loss += weight * (1 / R) sum_r l_r c_r          (the mean runs over ALL rows, ignored ones included)
+ *   d_score = *gout * weight * c_r / R * (softmax(s_r) - onehot)   or   ... / (R W) * clamp(s - target, -1, 1);
+ *   exact zeros on ignored rows and on rows of confidence 0.
+ * forward: ONE launch of min(R, 128) workgroups; needs ws (XGGM_SUM_WS_FLOATS floats, ws[0] == 0 at launch, left 0), a loss
+ * slot per job and save (2 * XGGM_VISUAL_MAX_JOBS * R floats).  backward: ONE launch, d_score per job in the scores' type.
+ * No floating-point atomics, every sum in a fixed order.  Refused before any launch: a null struct, n_jobs outside
+ * [1, XGGM_VISUAL_MAX_JOBS], R <= 0, an unknown kind, W <= 0, null scores / mask_conf, CE without label_index, L2 without
+ * target, a missing save; forward without ws or a loss slot; backward without gout or d_score. */
+#define XGGM_VISUAL_CE 1
+#define XGGM_VISUAL_L2 2
+#define XGGM_VISUAL_MAX_JOBS 3
+#define XGGM_VISUAL_LOSS_GRID 128 /* workgroups of either launch: more rows are walked */
+typedef struct xggm_visual_job {
+    int kind, W;
+    const void* scores;          /* [R, W] */
+    const int64_t* label_index;  /* CE: [R] */
+    const float* target;         /* L2: [R, W] */
+    const float* mask_conf;      /* [R] */
+    float weight;
+    float* loss;                 /* forward: the slot this job's loss is added to */
+    void* d_score;               /* backward: [R, W] */
+} xggm_visual_job;
+typedef struct xggm_visual_loss_args {
+    xggm_visual_job job[XGGM_VISUAL_MAX_JOBS];
+    int n_jobs, R;
+    int64_t ignore_index;
+    float* ws;          /* forward: XGGM_SUM_WS_FLOATS floats */
+    float* save;        /* 2 * XGGM_VISUAL_MAX_JOBS * R floats: written by the forward, read by the backward */
+    const float* gout;  /* backward: upstream gradient, DEVICE scalar */
+} xggm_visual_loss_args;
+int xggm_visual_loss_fwd_f32(const xggm_visual_loss_args* args, xggm_stream_t stream);
+int xggm_visual_loss_fwd_bf16(const xggm_visual_loss_args* args, xggm_stream_t stream);
+int xggm_visual_loss_bwd_f32(const xggm_visual_loss_args* args, xggm_stream_t stream);
+int xggm_visual_loss_bwd_bf16(const xggm_visual_loss_args* args, xggm_stream_t stream);
+
 /* ---- preprocessing that feeds the path ----------------------------------------------------
  * adj_true of every sample: data/preprocess/vqa/compute_adjacency.py:38-45 (compute_cosin_sim_v2) + :90.
  *   c[i][j] = cos(cls[i], attr[j]) for j >= i, 0 below the diagonal  (torch.cosine_similarity, eps 1e-6: each

@@ -1070,6 +1070,78 @@ class SoftmaxLossFn(Function):
         return (None, ops.softmax_loss_bwd(ctx.pr, gout.contiguous())) + (None,) * 6
 
 
+class Holder:
+    """what a pre-training loss Function leaves for its caller beside the tensor autograd sees"""
+    __slots__ = ("sel", "losses")
+
+    def __init__(self):
+        self.sel = self.losses = None
+
+
+class MlmSelectFn(Function):
+    """the rows of the language stream whose masked_lm_label counts, compacted on the device (xggm_mlm_select_*,
+    src/lxrt/modeling.py:1009-1016); the backward scatters the row gradients back, exact zeros elsewhere"""
+
+    @staticmethod
+    def forward(ctx, x, labels, cap, V, overflow, holder):
+        x2 = x.reshape(-1, x.shape[-1]).contiguous()
+        sel = ops.mlm_select(labels.reshape(-1).contiguous(), x2, cap, V, overflow=overflow)
+        ctx.sel, ctx.xshape = sel, x.shape
+        holder.sel = sel
+        return sel.x
+
+    @staticmethod
+    def backward(ctx, d):
+        return (ops.mlm_scatter(ctx.sel, d.contiguous()).view(ctx.xshape),) + (None,) * 5
+
+
+class MlmDecoderFn(Function):
+    """tied decoder + bias + cross-entropy over the vocabulary on the compacted rows (BertLMPredictionHead.decoder,
+    src/lxrt/modeling.py:642-659, :1009-1016).  The word table gets TWO gradients per pass, added in one fixed order: this
+    backward runs first (the heads sit above the encoder), takes the table's cleared gradient (``atomic_target``: the
+    table is of the arena's vector class) and adds d_z^T t; the embedding backward then adds its rows to the same view
+    (``ParamArena``: a parameter that already has a gradient gets the new contribution ADDED)."""
+
+    @staticmethod
+    def forward(ctx, rt, head, holder, t, slot, *params):
+        from . import pretrain_heads as PH
+        ctx.np = len(params)
+        a = rt.arena
+        loss, ctx.st = PH.mlm_decoder_fwd(holder.sel, t.contiguous(), a.w(head.decoder.weight), head.bias.data,
+                                          out=slot.t if slot is not None else None)
+        ctx.rt, ctx.head = rt, head
+        return loss
+
+    @staticmethod
+    def backward(ctx, gout):
+        from . import pretrain_heads as PH
+        a, head = ctx.rt.arena, ctx.head
+        g_table = a.atomic_target(head.decoder.weight)
+        d_t = PH.mlm_decoder_bwd(ctx.st, gout.contiguous(), g_table, True, a.atomic_target(head.bias))
+        return (None, None, None, d_t, None) + (None,) * ctx.np
+
+
+class VisualLossFn(Function):
+    """the object losses of src/lxrt/modeling.py:1024-1046 in one launch each way (xggm_visual_loss_*): returns their SUM
+    (total_visn_loss); the per-job values are left in ``holder.losses`` for the log"""
+
+    @staticmethod
+    def forward(ctx, holder, spec, ignore_index, *tensors):
+        k = len(spec)
+        scores, labels, confs = tensors[:k], tensors[k:2 * k], tensors[2 * k:3 * k]
+        jobs = [(kind, s.contiguous(), l.contiguous(), c.contiguous(), w) for (kind, w), s, l, c in zip(spec, scores, labels, confs)]
+        losses, ctx.pr = ops.visual_loss_fwd(jobs, ignore_index)
+        holder.losses = losses
+        ctx.k, ctx.shapes = k, [s.shape for s in scores]
+        parts = [losses[q:q + 1].view(()) for q in range(k)]
+        return ops.add_scalars(parts) if k > 1 else parts[0].clone()
+
+    @staticmethod
+    def backward(ctx, gout):
+        ds = ops.visual_loss_bwd(ctx.pr, gout.contiguous())
+        return (None, None, None) + tuple(d.view(sh) for d, sh in zip(ds, ctx.shapes)) + (None,) * (2 * ctx.k)
+
+
 class LossSumFn(Function):
     """loss = sum of the (already weighted) loss terms of a pass (src/vqa/vqacpv2.py:220-221, 249-250): one kernel
     instead of a framework add per ``+``; the backward hands the upstream gradient to every term unchanged."""

@@ -42,6 +42,11 @@ class VisualConfig(object):
         self.obj_id_num = 1600
         self.attr_id_num = 400
         self.visual_losses = self.VISUAL_LOSSES
+        self.visual_loss_config = {
+            'obj': (self.obj_id_num, 'ce', (-1,), 1 / 0.15),
+            'attr': (self.attr_id_num, 'ce', (-1,), 1 / 0.15),
+            'feat': (2048, 'l2', (-1, 2048), 1 / 0.15),
+        }
 
     def set_visual_dims(self, feat_dim, pos_dim):
         self.visual_feat_dim = feat_dim
@@ -504,6 +509,185 @@ class LXRTModel(BertPreTrainedModel):
                                               visn_attention_mask=extended_visual_attention_mask)
         pooled_output = self.pooler(lang_feats)
         return (lang_feats, visn_feats), pooled_output
+
+
+class BertPredictionHeadTransform(nn.Module):
+    """ref: src/lxrt/modeling.py:623-639 (dense, GELU, LayerNorm): one fused block"""
+
+    def __init__(self, config):
+        super().__init__()
+        self.dense = nn.Linear(config.hidden_size, config.hidden_size)
+        self.transform_act_fn = GeLU()
+        self.LayerNorm = BertLayerNorm(config.hidden_size, eps=1e-12)
+
+    def forward(self, hidden_states):
+        rt = runtime_of(self)
+        return XF.MLPFn.apply(rt, self.dense, self.LayerNorm, 1e-12, hidden_states, *self.dense.parameters(),
+                              *self.LayerNorm.parameters())
+
+
+class _TiedLinear:
+    """the decoder's weight with the head's own bias, as LinearActFn reads a Linear"""
+
+    def __init__(self, weight, bias):
+        self.weight, self.bias = weight, bias
+
+
+class BertLMPredictionHead(nn.Module):
+    """ref: src/lxrt/modeling.py:642-659.  ``decoder.weight`` IS the word-embedding table.  ``forward`` gives the scores of
+    every row, as the reference does; training goes through ``masked_lm_loss``, which never forms them."""
+
+    def __init__(self, config, bert_model_embedding_weights):
+        super().__init__()
+        self.transform = BertPredictionHeadTransform(config)
+        self.decoder = nn.Linear(bert_model_embedding_weights.size(1), bert_model_embedding_weights.size(0), bias=False)
+        self.decoder.weight = bert_model_embedding_weights
+        self.bias = nn.Parameter(torch.zeros(bert_model_embedding_weights.size(0)))
+
+    def forward(self, hidden_states):
+        rt = runtime_of(self)
+        h = self.transform(hidden_states)
+        return XF.LinearActFn.apply(rt, _TiedLinear(self.decoder.weight, self.bias), h, ops.ACT_NONE, True,
+                                    self.decoder.weight, self.bias)
+
+    def masked_lm_loss(self, hidden_states, masked_lm_labels, mlm_capacity=None, overflow=None):
+        """CrossEntropyLoss(ignore_index=-1) of the scores against the labels (:1009-1016) over the rows that carry a
+        label only: select -> transform -> tied decoder -> loss, all on ``mlm_capacity`` compacted rows"""
+        from .. import pretrain_heads as PH
+        rt = runtime_of(self)
+        M = masked_lm_labels.numel()
+        holder = XF.Holder()
+        rows = XF.MlmSelectFn.apply(hidden_states, masked_lm_labels, PH.mlm_capacity(M, mlm_capacity),
+                                    self.decoder.weight.shape[0], overflow, holder)
+        t = self.transform(rows)
+        return XF.MlmDecoderFn.apply(rt, self, holder, t, rt.scalar_slot(), self.decoder.weight, self.bias)
+
+
+class BertVisualAnswerHead(nn.Module):
+    """ref: src/lxrt/modeling.py:662-674"""
+
+    def __init__(self, config, num_answers):
+        super().__init__()
+        hid_dim = config.hidden_size
+        self.logit_fc = nn.Sequential(nn.Linear(hid_dim, hid_dim * 2), GeLU(), BertLayerNorm(hid_dim * 2, eps=1e-12),
+                                      nn.Linear(hid_dim * 2, num_answers))
+
+    def forward(self, hidden_states):
+        rt = runtime_of(self)
+        fc = self.logit_fc
+        y = XF.MLPFn.apply(rt, fc[0], fc[2], 1e-12, hidden_states, *fc[0].parameters(), *fc[2].parameters())
+        return XF.LinearActFn.apply(rt, fc[3], y, ops.ACT_NONE, True, *fc[3].parameters())
+
+
+class BertVisualObjHead(nn.Module):
+    """ref: src/lxrt/modeling.py:677-701"""
+
+    def __init__(self, config, visual_losses):
+        super().__init__()
+        self.transform = BertPredictionHeadTransform(config)
+        visual_losses = visual_losses.split(",")
+        for loss in visual_losses:
+            assert loss in VISUAL_CONFIG.VISUAL_LOSSES
+        self.visual_losses = visual_losses
+        self.decoder_dict = nn.ModuleDict({key: nn.Linear(config.hidden_size, VISUAL_CONFIG.visual_loss_config[key][0])
+                                           for key in self.visual_losses})
+
+    def forward(self, hidden_states):
+        rt = runtime_of(self)
+        hs = XF.fan_out(self.transform(hidden_states), len(self.visual_losses))
+        return {key: XF.LinearActFn.apply(rt, self.decoder_dict[key], h, ops.ACT_NONE, False,
+                                          *self.decoder_dict[key].parameters())
+                for key, h in zip(self.visual_losses, hs)}
+
+
+class BertPreTrainingHeads(nn.Module):
+    """ref: src/lxrt/modeling.py:704-714"""
+
+    def __init__(self, config, bert_model_embedding_weights):
+        super().__init__()
+        self.predictions = BertLMPredictionHead(config, bert_model_embedding_weights)
+        self.seq_relationship = nn.Linear(config.hidden_size, 2)
+
+    def relationship(self, pooled_output):
+        rt = runtime_of(self)
+        return XF.LinearActFn.apply(rt, self.seq_relationship, pooled_output, ops.ACT_NONE, True,
+                                    *self.seq_relationship.parameters())
+
+    def forward(self, sequence_output, pooled_output):
+        return self.predictions(sequence_output), self.relationship(pooled_output)
+
+
+class LXRTPretraining(BertPreTrainedModel):
+    """ref: src/lxrt/modeling.py:955-1061.  ``mlm_capacity``: slots of the compacted masked-LM rows -- None = B T (can
+    never overflow), an int fixes them; more labelled rows than slots raise the device flag ``mlm_overflow`` and make
+    the masked-LM loss NaN.  The word table's gradient is dense here (the decoder's share), so the arena's row-sparse
+    bookkeeping of it is switched off."""
+
+    def __init__(self, config, task_mask_lm=True, task_matched=True, task_obj_predict=True, visual_losses='',
+                 task_qa=True, num_answers=2, mlm_capacity=None, compute_dtype=None):
+        super().__init__(config)
+        self.config = config
+        self.num_answers = num_answers
+        self.task_mask_lm = task_mask_lm
+        self.task_obj_predict = task_obj_predict
+        self.task_matched = task_matched
+        self.task_qa = task_qa
+        self.mlm_capacity = mlm_capacity
+        self.mlm_overflow = None
+        self.bert = LXRTModel(config)
+        self.cls = BertPreTrainingHeads(config, self.bert.embeddings.word_embeddings.weight)
+        if self.task_obj_predict:
+            self.obj_predict_head = BertVisualObjHead(config, visual_losses)
+        if self.task_qa:
+            self.answer_head = BertVisualAnswerHead(config, self.num_answers)
+        self.apply(self.init_bert_weights)
+        bind_root(self, compute_dtype)
+
+    def forward(self, input_ids, token_type_ids=None, attention_mask=None, masked_lm_labels=None, visual_feats=None,
+                pos=None, obj_labels=None, matched_label=None, ans=None):
+        rt = runtime_of(self)
+        rt.arena.row_list_enabled = False
+        dev = input_ids.device
+        if self.mlm_overflow is None or self.mlm_overflow.device != dev:
+            self.mlm_overflow = torch.zeros(1, device=dev, dtype=torch.int32)
+        (lang_output, visn_output), pooled_output = self.bert(input_ids, token_type_ids, attention_mask,
+                                                              visual_feats=(visual_feats, pos))
+        p_rel, p_qa = XF.fan_out(pooled_output, 2)
+        if self.task_qa:
+            answer_score = self.answer_head(p_qa)
+        else:
+            answer_score = pooled_output[0][0]
+        rt.begin_losses(4)
+        ce = lambda z, y: XF.SoftmaxLossFn.apply(ops.SOFTMAX_CE, z, y.view(-1), None, None, -1, 1.0, rt.scalar_slot())
+        terms, losses = [], ()
+        if masked_lm_labels is not None and self.task_mask_lm:
+            l = self.cls.predictions.masked_lm_loss(lang_output, masked_lm_labels, self.mlm_capacity, self.mlm_overflow)
+            terms.append(l)
+            losses += (l.detach(),)
+        if matched_label is not None and self.task_matched:
+            l = ce(self.cls.relationship(p_rel).view(-1, 2), matched_label)
+            terms.append(l)
+            losses += (l.detach(),)
+        if obj_labels is not None and self.task_obj_predict:
+            scores = self.obj_predict_head(visn_output)
+            kinds = {'ce': ops.VISUAL_CE, 'l2': ops.VISUAL_L2}
+            spec, ss, ls, cs = [], [], [], []
+            for key in VISUAL_CONFIG.visual_losses:
+                label, mask_conf = obj_labels[key]
+                output_dim, loss_fct_name, label_shape, weight = VISUAL_CONFIG.visual_loss_config[key]
+                spec.append((kinds[loss_fct_name], weight))
+                ss.append(scores[key].view(-1, output_dim))
+                ls.append(label.view(*label_shape) if loss_fct_name == 'ce' else label.view(*label_shape).float())
+                cs.append(mask_conf.view(-1).float())
+            holder = XF.Holder()
+            terms.append(XF.VisualLossFn.apply(holder, spec, -1, *ss, *ls, *cs))
+            losses += tuple(holder.losses[q].detach() for q in range(len(spec)))
+        if ans is not None and self.task_qa:
+            l = ce(answer_score.view(-1, self.num_answers), ans)
+            terms.append(l)
+            losses += (l.detach(),)
+        total_loss = XF.LossSumFn.apply(*terms) if len(terms) > 1 else terms[0]
+        return total_loss, torch.stack(losses).unsqueeze(0), answer_score.detach()
 
 
 class LXRTFeatureExtraction(BertPreTrainedModel):

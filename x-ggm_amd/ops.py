@@ -1379,6 +1379,235 @@ def softmax_loss_bwd(pr, gout, d_logit=None):
     return d_logit
 
 
+# ----------------------------------------------------------------------------- pre-training heads (LXRTPretraining)
+VISUAL_CE, VISUAL_L2, VISUAL_MAX_JOBS = 1, 2, 3  # XGGM_VISUAL_* (include/xggm.h)
+VOCAB_CE_REG_MAX = 32768  # XGGM_VOCAB_CE_REG_MAX: the longest row the forward keeps in registers
+VOCAB_CE_FWD_GRID, VOCAB_CE_BWD_GRID, VISUAL_LOSS_GRID = 1024, 2048, 128  # XGGM_*_GRID: rows beyond them are walked
+MLM_SELECT_MAX_ROWS = 65536  # XGGM_MLM_SELECT_MAX_ROWS
+
+
+class MlmSelectArgs(_ct.Structure):
+    """mirror of ``xggm_mlm_select_args`` (include/xggm.h)"""
+    _fields_ = [("labels", _ct.c_void_p), ("x", _ct.c_void_p), ("M", _ct.c_int), ("H", _ct.c_int), ("cap", _ct.c_int),
+                ("V", _ct.c_int), ("ignore_index", _ct.c_int64), ("row_index", _ct.c_void_p), ("label", _ct.c_void_p),
+                ("n", _ct.c_void_p), ("overflow", _ct.c_void_p), ("out", _ct.c_void_p)]
+
+
+class VocabCeArgs(_ct.Structure):
+    """mirror of ``xggm_vocab_ce_args`` (include/xggm.h)"""
+    _fields_ = [("logits", _ct.c_void_p), ("label", _ct.c_void_p), ("n", _ct.c_void_p), ("overflow", _ct.c_void_p),
+                ("cap", _ct.c_int), ("V", _ct.c_int), ("ld", _ct.c_int64), ("loss", _ct.c_void_p), ("ws", _ct.c_void_p),
+                ("save", _ct.c_void_p), ("gout", _ct.c_void_p)]
+
+
+class VisualJob(_ct.Structure):
+    """mirror of ``xggm_visual_job`` (include/xggm.h)"""
+    _fields_ = [("kind", _ct.c_int), ("W", _ct.c_int), ("scores", _ct.c_void_p), ("label_index", _ct.c_void_p),
+                ("target", _ct.c_void_p), ("mask_conf", _ct.c_void_p), ("weight", _ct.c_float), ("loss", _ct.c_void_p),
+                ("d_score", _ct.c_void_p)]
+
+
+class VisualLossArgs(_ct.Structure):
+    """mirror of ``xggm_visual_loss_args`` (include/xggm.h)"""
+    _fields_ = [("job", VisualJob * VISUAL_MAX_JOBS), ("n_jobs", _ct.c_int), ("R", _ct.c_int), ("ignore_index", _ct.c_int64),
+                ("ws", _ct.c_void_p), ("save", _ct.c_void_p), ("gout", _ct.c_void_p)]
+
+
+def vocab_ld(V, dt):
+    """row stride of masked-LM logits of ``V`` columns: the next multiple of 16 bytes (30522 -> 30528)"""
+    g = 16 // torch.empty((), dtype=dt).element_size()
+    return (int(V) + g - 1) // g * g
+
+
+class MlmSelection:
+    """what ``mlm_select`` left on the device: ``row_index`` / ``label`` int32 [cap], ``n`` and ``overflow`` int32 [1], the
+    gathered rows ``x`` [cap, H]; nothing of it is read by the host"""
+
+    def __init__(self, M, H, cap, V, row_index, label, n, overflow, x):
+        self.M, self.H, self.cap, self.V = M, H, cap, V
+        self.row_index, self.label, self.n, self.overflow, self.x = row_index, label, n, overflow, x
+
+
+def mlm_select(labels, x, cap, V, ignore_index=-1, overflow=None):
+    """rows of ``x`` [M, H] whose ``labels`` [M] (int64) count, compacted in ascending row order into ``cap`` slots;
+    contract: xggm_mlm_select_* in xggm.h.  One launch, no host read.  ``overflow``: an int32 [1] flag the caller owns."""
+    _c(labels, torch.int64, "masked_lm_labels"), _c(x)
+    sfx(x.dtype)
+    if x.dim() != 2 or labels.numel() != x.shape[0]:
+        raise ValueError("mlm_select: %d labels for activations %s" % (labels.numel(), tuple(x.shape)))
+    M, H = x.shape
+    cap, V = int(cap), int(V)
+    if cap <= 0 or V <= 0:
+        raise ValueError("mlm_select: capacity %d and vocabulary %d must be positive" % (cap, V))
+    if M > MLM_SELECT_MAX_ROWS:
+        raise ValueError("mlm_select: %d rows, at most %d (every workgroup counts the labels in front of its chunk)"
+                         % (M, MLM_SELECT_MAX_ROWS))
+    if (H * x.element_size()) % 16:
+        raise ValueError("mlm_select: rows of %d bytes are no multiple of 16" % (H * x.element_size()))
+    if labels.device != x.device:
+        raise RuntimeError("mlm_select: all operands must live on one device")
+    dev = x.device
+    idx = torch.empty(2 * cap + 1, device=dev, dtype=torch.int32)
+    if overflow is None:
+        overflow = torch.empty(1, device=dev, dtype=torch.int32)
+    _c(overflow, torch.int32, "overflow")
+    out = torch.empty((cap, H), device=dev, dtype=x.dtype)
+    a = MlmSelectArgs()
+    a.labels, a.x, a.M, a.H, a.cap, a.V, a.ignore_index = ptr(labels), ptr(x), M, H, cap, V, int(ignore_index)
+    sel = MlmSelection(M, H, cap, V, idx[:cap], idx[cap:2 * cap], idx[2 * cap:], overflow, out)
+    a.row_index, a.label, a.n, a.overflow, a.out = ptr(sel.row_index), ptr(sel.label), ptr(sel.n), ptr(overflow), ptr(out)
+    call("xggm_mlm_select_" + sfx(x.dtype), _ct.addressof(a), stream())
+    return sel
+
+
+def mlm_scatter(sel, src):
+    """backward of the gather of ``mlm_select``: -> [M, H] with row j of ``src`` [cap, H] at row ``row_index[j]``, exact
+    zeros elsewhere.  One launch."""
+    _c(src)
+    if tuple(src.shape) != (sel.cap, sel.H) or src.device != sel.n.device:
+        raise ValueError("mlm_scatter: src %s does not fit the selection [%d, %d]" % (tuple(src.shape), sel.cap, sel.H))
+    out = torch.empty((sel.M, sel.H), device=src.device, dtype=src.dtype)
+    call("xggm_mlm_scatter_" + sfx(src.dtype), ptr(src), ptr(sel.row_index), ptr(sel.n), ptr(out), sel.M, sel.H, sel.cap,
+         stream())
+    return out
+
+
+class VocabCeProblem:
+    """the operands of one masked-LM cross-entropy (``vocab_ce_fwd`` makes it, ``vocab_ce_bwd`` reads it): checked on the
+    host once.  ``logits`` [cap, ld] with ld >= V a multiple of 16 bytes (``vocab_ld``); a [cap, V] view of such a buffer
+    is what the decoder's product writes."""
+
+    def __init__(self, logits, label, n, V, overflow):
+        _chk(logits)
+        sfx(logits.dtype)
+        cap, cols, ld = _rows(logits)
+        V = int(V)
+        if cols != V and cols != ld:
+            raise ValueError("vocab_ce: logits %s are neither the [cap, V] view nor the padded [cap, ld] buffer (V=%d)"
+                             % (tuple(logits.shape), V))
+        if cap == 1:
+            ld = max(ld, cols)
+        g = 16 // logits.element_size()
+        if V <= 0 or ld < V or ld % g:
+            raise ValueError("vocab_ce: row stride %d must be >= V=%d and a multiple of %d elements" % (ld, V, g))
+        _c(label, torch.int32, "label"), _c(n, torch.int32, "n")
+        if label.numel() != cap or n.numel() != 1:
+            raise ValueError("vocab_ce: %d labels and %d counters for %d rows" % (label.numel(), n.numel(), cap))
+        if overflow is not None:
+            _c(overflow, torch.int32, "overflow")
+        for t in (label, n, overflow):
+            if t is not None and t.device != logits.device:
+                raise RuntimeError("vocab_ce: all operands must live on one device")
+        self.cap, self.V, self.ld = cap, V, ld
+        self.t = dict(logits=logits, label=label, n=n, overflow=overflow)
+        self.save = None
+
+    def args(self):
+        a = VocabCeArgs()
+        for k, v in self.t.items():
+            setattr(a, k, ptr(v))
+        a.cap, a.V, a.ld, a.save = self.cap, self.V, self.ld, ptr(self.save)
+        return a
+
+
+def vocab_ce_fwd(logits, label, n, V, overflow=None, out=None):
+    """cross-entropy over the vocabulary on compacted rows (fp32 or bf16 logits); contract: xggm_vocab_ce_fwd_* in xggm.h.
+    One launch.  -> (0-dim loss, VocabCeProblem for ``vocab_ce_bwd``).  ``out``: a zeroed 1-element slot to accumulate into."""
+    pr = VocabCeProblem(logits, label, n, V, overflow)
+    pr.save = torch.empty(2 * pr.cap, device=logits.device, dtype=F32)
+    loss = _scalar(out, logits.device)
+    a = pr.args()
+    a.loss, a.ws = ptr(loss), ptr(sum_ws(logits.device))
+    call("xggm_vocab_ce_fwd_" + sfx(logits.dtype), _ct.addressof(a), stream())
+    return loss, pr
+
+
+def vocab_ce_bwd(pr, gout):
+    """backward of ``vocab_ce_fwd``: OVERWRITES the logits with ``*gout`` (p - onehot) / n in their own dtype (exact zeros
+    on rows >= n and in the padding columns) and returns them.  One launch."""
+    a = pr.args()
+    a.gout = ptr(_c(gout, F32, "gout"))
+    call("xggm_vocab_ce_bwd_" + sfx(pr.t["logits"].dtype), _ct.addressof(a), stream())
+    return pr.t["logits"]
+
+
+class VisualLossProblem:
+    """the jobs of one object-loss launch (``visual_loss_fwd`` makes it, ``visual_loss_bwd`` reads it): checked on the host
+    once.  ``jobs``: up to three of (kind, scores [R, W], label, mask_conf [R] fp32, weight) with label = int64 [R] class
+    indices for ``VISUAL_CE`` and fp32 [R, W] targets for ``VISUAL_L2``."""
+
+    def __init__(self, jobs, ignore_index):
+        if not 1 <= len(jobs) <= VISUAL_MAX_JOBS:
+            raise ValueError("visual_loss: %d jobs (1 to %d per launch)" % (len(jobs), VISUAL_MAX_JOBS))
+        self.jobs, self.R, self.dt, dev = [], None, None, None
+        for kind, scores, label, conf, weight in jobs:
+            if kind not in (VISUAL_CE, VISUAL_L2):
+                raise ValueError("visual_loss: unknown kind %r" % (kind,))
+            _c(scores), _c(conf, F32, "mask_conf")
+            if scores.dim() != 2:
+                raise ValueError("visual_loss: scores %s must be [R, W]" % (tuple(scores.shape),))
+            R, W = scores.shape
+            if self.R is None:
+                self.R, self.dt, dev = R, scores.dtype, scores.device
+                sfx(self.dt)
+            if R != self.R or scores.dtype != self.dt or conf.numel() != R:
+                raise ValueError("visual_loss: every job has the same rows and dtype (%s %s, %d confidences; R=%d %s)"
+                                 % (tuple(scores.shape), scores.dtype, conf.numel(), self.R, self.dt))
+            if kind == VISUAL_CE:
+                _c(label, torch.int64, "label")
+                if label.numel() != R:
+                    raise ValueError("visual_loss: %d labels for %d rows" % (label.numel(), R))
+            else:
+                _c(label, F32, "target")
+                if label.numel() != R * W:
+                    raise ValueError("visual_loss: target %s does not fit scores %s" % (tuple(label.shape), tuple(scores.shape)))
+            if label.device != dev or conf.device != dev or scores.device != dev:
+                raise RuntimeError("visual_loss: all operands must live on one device")
+            self.jobs.append((int(kind), W, scores, label, conf, float(weight)))
+        self.ignore_index = int(ignore_index)
+        self.device = dev
+        self.save = None
+
+    def args(self, losses=None, d_scores=None):
+        a = VisualLossArgs()
+        for q, (kind, W, scores, label, conf, weight) in enumerate(self.jobs):
+            j = a.job[q]
+            j.kind, j.W, j.scores, j.mask_conf, j.weight = kind, W, ptr(scores), ptr(conf), weight
+            if kind == VISUAL_CE:
+                j.label_index = ptr(label)
+            else:
+                j.target = ptr(label)
+            if losses is not None:
+                j.loss = losses[q:].data_ptr()
+            if d_scores is not None:
+                j.d_score = ptr(d_scores[q])
+        a.n_jobs, a.R, a.ignore_index, a.save = len(self.jobs), self.R, self.ignore_index, ptr(self.save)
+        return a
+
+
+def visual_loss_fwd(jobs, ignore_index=-1, out=None):
+    """the object losses of pre-training, up to three per launch; contract: xggm_visual_loss_fwd_* in xggm.h.
+    -> (losses fp32 [len(jobs)], VisualLossProblem for ``visual_loss_bwd``).  ``out``: zeroed slots to accumulate into."""
+    pr = VisualLossProblem(jobs, ignore_index)
+    pr.save = torch.empty(2 * VISUAL_MAX_JOBS * pr.R, device=pr.device, dtype=F32)
+    losses = out if out is not None else zeros_f32(len(pr.jobs), pr.device)
+    _c(losses, F32, "losses")
+    assert losses.numel() == len(pr.jobs) and losses.device == pr.device
+    a = pr.args(losses=losses)
+    a.ws = ptr(sum_ws(pr.device))
+    call("xggm_visual_loss_fwd_" + sfx(pr.dt), _ct.addressof(a), stream())
+    return losses, pr
+
+
+def visual_loss_bwd(pr, gout):
+    """backward of ``visual_loss_fwd``: -> the d_score [R, W] of every job, in the scores' dtype.  One launch."""
+    ds = [torch.empty_like(j[2]) for j in pr.jobs]
+    a = pr.args(d_scores=ds)
+    a.gout = ptr(_c(gout, F32, "gout"))
+    call("xggm_visual_loss_bwd_" + sfx(pr.dt), _ct.addressof(a), stream())
+    return ds
+
+
 # ----------------------------------------------------------------------------- optimiser / utils
 def zero_ranges(buf, ranges, rows=None):
     """zero buf[s:e] for up to 16 (s, e) element ranges per launch (all float4-aligned).  ``rows`` = (table [R, H] fp32,

@@ -117,3 +117,57 @@ def debias_case(B, A, Hd=0, seed=0, bias_max=None):
         out["lin_w"] = (0.05 * r.standard_normal((1, Hd), dtype=np.float32)).astype(np.float32)
         out["lin_b"] = (0.3 * r.standard_normal((1,), dtype=np.float32)).astype(np.float32)
     return out
+
+
+def pretrain_case(B, T=20, O=36, F=2048, vocab=30522, n_obj=1600, n_attr=400, n_ans=9500, seed=0, mask_rate=0.15):
+    """One synthetic pre-training batch shaped like what src/pretrain/lxmert_pretrain.py:146-215 hands to
+    ``LXRTPretraining.forward`` (the host-side ``random_word`` / ``random_feat`` masking is not restated: labels,
+    confidences and already-masked inputs are drawn directly).  ``[CLS] ids [SEP]`` padded to T; masked_lm_labels -1
+    except on about ``mask_rate`` of the real tokens; every edge the parity cases need is forced when B >= 3: sample 0
+    has NO masked token, sample 1 masks position 1 and its last real token, both matched classes occur, ``ans`` holds a
+    -1, one object label is -1 under a positive confidence, one object row has confidence 0 in all three losses, and
+    the feature targets lie on both sides of |prediction - target| = 1 of anything near zero.  All float32 / int64."""
+    r = _rng(seed, "pretrain_case:%d:%d:%d" % (B, T, O))
+    ids = np.zeros((B, T), dtype=np.int64)
+    mask = np.zeros((B, T), dtype=np.int64)
+    labels = np.full((B, T), -1, dtype=np.int64)
+    lo = min(1000, vocab // 2)
+    for b in range(B):
+        L = int(r.integers(min(5, T - 1), T)) if T > 5 else T
+        ids[b, 0] = min(101, vocab - 2)
+        ids[b, 1:L - 1] = r.integers(lo, vocab, size=L - 2)
+        ids[b, L - 1] = min(102, vocab - 1)
+        mask[b, :L] = 1
+        pick = r.random(L) < mask_rate
+        pick[0] = False
+        labels[b, :L][pick] = r.integers(0, vocab, size=int(pick.sum()))
+        if b == 0:
+            labels[b] = -1
+        elif b == 1:
+            labels[b, 1] = 0
+            labels[b, L - 1] = vocab - 1
+    feats = (3.0 * r.random((B, O, F), dtype=np.float32)).astype(np.float32)
+    boxes = r.random((B, O, 4), dtype=np.float32)
+    matched = r.integers(0, 2, size=B).astype(np.int64)
+    ans = r.integers(0, n_ans, size=B).astype(np.int64)
+    obj_label = r.integers(0, n_obj, size=(B, O)).astype(np.int64)
+    attr_label = r.integers(0, n_attr, size=(B, O)).astype(np.int64)
+    obj_conf = r.random((B, O), dtype=np.float32)
+    attr_conf = r.random((B, O), dtype=np.float32)
+    feat_conf = (r.random((B, O)) < 0.5).astype(np.float32)
+    # regression targets around zero, where a freshly initialised head predicts: |d| on both sides of 1
+    feat_label = (1.2 * r.standard_normal((B, O, F), dtype=np.float32)).astype(np.float32)
+    if B >= 2:
+        matched[0], matched[1] = 1, 0
+        ans[1] = -1
+    obj_label[0, 0] = -1
+    obj_conf[0, 0] = 0.75
+    attr_label[B - 1, O - 1] = -1
+    attr_conf[B - 1, O - 1] = 0.5
+    feat_conf[0, 0] = 1.0
+    for c in (obj_conf, attr_conf, feat_conf):
+        c[0, O - 1] = 0.0
+    seg = np.zeros((B, T), dtype=np.int64)
+    return dict(input_ids=ids, input_mask=mask, segment_ids=seg, masked_lm_labels=labels, feats=feats, boxes=boxes,
+                matched_label=matched, ans=ans, obj_label=obj_label, obj_conf=obj_conf, attr_label=attr_label,
+                attr_conf=attr_conf, feat_label=feat_label, feat_conf=feat_conf)
