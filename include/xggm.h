@@ -754,6 +754,68 @@ int xggm_visual_loss_fwd_bf16(const xggm_visual_loss_args* args, xggm_stream_t s
 int xggm_visual_loss_bwd_f32(const xggm_visual_loss_args* args, xggm_stream_t stream);
 int xggm_visual_loss_bwd_bf16(const xggm_visual_loss_args* args, xggm_stream_t stream);
 
+/* xggm_pretrain_corrupt_*: the corruption src/pretrain/lxmert_pretrain.py:76-215 applies to every example on the host --
+ * random_word (:76-112), random_feat (:115-136) and the QA answer draw (:186-199) -- for a whole batch that is already on the
+ * device, in ONE launch.  The suffix is the type of the features.  The outputs are the arguments of LXRTPretraining.forward
+ * (:302-305) that the corruption produces; nothing is changed in place.
+ *   object rows  r = (b, o) of feats [B, O, F], draw u = u_obj[r]:
+ *                u < obj_mask_rate: feat_mask[r] = 1 and, with p = u / obj_mask_rate,  p < 0.8: masked_feat[r] = 0 (feats
+ *                is not read);  p < 0.9: masked_feat[r] = pool[floor(u_obj_pick[r] * P)];  else a copy.
+ *                u >= obj_mask_rate: a copy, feat_mask[r] = 0.
+ *                pool [P, F] (NULL: the batch's own clean feats as [B O, F]) stands in for the reference's
+ *                torchdset.random_feat(), a random object of a random datum of the whole data set (two integer draws there,
+ *                one row index here): the one deviation.  Rows move as 16-byte vectors when F * sizeof(element) is a
+ *                multiple of 16 and feats / pool / masked_feat are 16-byte aligned, element by element otherwise.
+ *   tokens       position (b, t) is eligible iff t >= 1, input_mask[b, t] == 1, t < T - 1 and input_mask[b, t + 1] == 1 (not
+ *                [CLS], not the last real token [SEP], not padding: :156-172).  Eligible, draw u = u_word[b, t]:
+ *                u < word_mask_rate: masked_lm_labels = the original id and, with p = u / word_mask_rate,  p < 0.8: mask_id;
+ *                p < 0.9: floor(u_word_pick[b, t] * vocab_size);  else the id stays.  Every other position keeps its id and
+ *                gets the label -1.
+ *   answer       label_ids [B, K] (int64, -1 = no key, the keys of example.label in insertion order), label_scores [B, K]:
+ *                no key or is_matched[b] != 1: ans[b] = -1; one key: that key; otherwise the first key k with
+ *                u_ans[b] * sum < s_0 + ... + s_k (sums left to right over the valid keys), the last valid key as the
+ *                fallback.  The reference draws this case with np.random.multinomial(1, s / sum) (:196-199), whose stream
+ *                cannot be fed from outside: same distribution, not the same bits.
+ * Every comparison, u / rate, u2 * n and the running sums are evaluated in double from the fp32 draw -- the IEEE operations the
+ * reference performs on Python floats -- so a decision is the reference's for every fp32 u, the thresholds included.  A
+ * supplied pick draw outside [0, 1) is held inside the table.
+ * Draws: five buffers, u_word [B, T], u_word_pick [B, T], u_obj [B, O], u_obj_pick [B, O], u_ans [B] (fp32 in [0, 1)).  A NULL
+ * buffer number k (0..4 in that order) means philox_uniform(seed, offset, sid_base + k, row-major index) with {seed, offset} =
+ * rng[0..1] -- exactly what xggm_uniform(out, n, rng, sid_base + k) exports.  rng is only read: the caller advances it
+ * (xggm_rng_advance) once per batch.
+ * One launch: min(B O, XGGM_PRETRAIN_CORRUPT_ROW_GRID) workgroups of 256 threads walk the rows, ceil(B T / 256) trailing
+ * workgroups take one token per thread, ceil(B / 256) one sample per thread; no result depends on the geometry.  No atomics,
+ * no allocation, no host synchronisation.  Refused before any launch: a null struct, B, T, O, F or K <= 0, a null required
+ * pointer, rates outside [0, 1], vocab_size <= 0, a NULL draw buffer without rng, masked_feat overlapping feats or pool. */
+#define XGGM_PRETRAIN_CORRUPT_ROW_GRID 65536 /* workgroups of the object rows: more rows are walked */
+typedef struct xggm_pretrain_corrupt_args {
+    const void* feats;             /* [B, O, F] clean features */
+    const void* pool;              /* [P, F] or NULL */
+    void* masked_feat;             /* [B, O, F] out */
+    float* feat_mask;              /* [B, O] out */
+    const int64_t* input_ids;      /* [B, T] */
+    const int64_t* input_mask;     /* [B, T] */
+    int64_t* input_ids_out;        /* [B, T] out */
+    int64_t* masked_lm_labels;     /* [B, T] out */
+    const int64_t* label_ids;      /* [B, K] */
+    const float* label_scores;     /* [B, K] */
+    const int64_t* is_matched;     /* [B] */
+    int64_t* ans;                  /* [B] out */
+    int B, T, O, F, K;
+    int64_t P;                     /* rows of pool (ignored when pool is NULL) */
+    int64_t vocab_size, mask_id;
+    double word_mask_rate, obj_mask_rate;
+    const float* u_word;           /* the five draw buffers, each may be NULL */
+    const float* u_word_pick;
+    const float* u_obj;
+    const float* u_obj_pick;
+    const float* u_ans;
+    const uint64_t* rng;           /* {seed, offset}; needed when a draw buffer is NULL */
+    uint32_t sid_base;
+} xggm_pretrain_corrupt_args;
+int xggm_pretrain_corrupt_f32(const xggm_pretrain_corrupt_args* args, xggm_stream_t stream);
+int xggm_pretrain_corrupt_bf16(const xggm_pretrain_corrupt_args* args, xggm_stream_t stream);
+
 /* ---- preprocessing that feeds the path ----------------------------------------------------
  * adj_true of every sample: data/preprocess/vqa/compute_adjacency.py:38-45 (compute_cosin_sim_v2) + :90.
  *   c[i][j] = cos(cls[i], attr[j]) for j >= i, 0 below the diagonal  (torch.cosine_similarity, eps 1e-6: each
@@ -1091,6 +1153,8 @@ int xggm_cast_f32_to_bf16(const float* x, void* out, int64_t n, xggm_stream_t st
 /* test hooks: the dropout keep-scale (0 or 1/(1-p)) and N(0,1) draw of elements 0..n-1 */
 int xggm_dropout_mask(float* out, int64_t n, float p, const uint64_t* rng, uint32_t sid, xggm_stream_t stream);
 int xggm_normal(float* out, int64_t n, const uint64_t* rng, uint32_t sid, xggm_stream_t stream);
+/* the uniform [0, 1) draw of elements 0..n-1 of stream sid: what a NULL draw buffer of xggm_pretrain_corrupt_* stands for */
+int xggm_uniform(float* out, int64_t n, const uint64_t* rng, uint32_t sid, xggm_stream_t stream);
 
 #ifdef __cplusplus
 }

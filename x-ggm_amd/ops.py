@@ -2184,6 +2184,15 @@ def normal(n, rng, sid, device):
     return out
 
 
+def uniform(n, rng, sid, device=None):
+    """the uniform [0, 1) draws 0..n-1 of Philox stream ``sid`` at the state ``rng``: what a draw buffer that
+    ``pretrain_corrupt`` is not given stands for (``dropout_mask`` does the same for dropout)"""
+    _c(rng, torch.int64, "rng")
+    out = torch.empty(int(n), device=rng.device if device is None else device, dtype=F32)
+    call("xggm_uniform", ptr(out), int(n), ptr(rng), int(sid), stream())
+    return out
+
+
 def make_rng(seed, device):
     """device-resident {seed, offset} pair (int64 storage of the two uint64 words)."""
     return torch.tensor([int(seed) & 0x7FFFFFFFFFFFFFFF, 0], dtype=torch.int64, device=device)
@@ -2194,6 +2203,91 @@ def triu_index(k, N):
     i, j = ctypes.c_int(), ctypes.c_int()
     _lib.check(_lib.lib.xggm_triu_index(k, N, ctypes.byref(i), ctypes.byref(j)), "xggm_triu_index")
     return i.value, j.value
+
+
+# ----------------------------------------------------------------------------- pre-training batch masking
+PRETRAIN_DRAWS = ("u_word", "u_word_pick", "u_obj", "u_obj_pick", "u_ans")  # Philox streams sid_base + 0..4, in this order
+
+
+class PretrainCorruptArgs(_ct.Structure):
+    """mirror of ``xggm_pretrain_corrupt_args`` (include/xggm.h)"""
+    _fields_ = [("feats", _ct.c_void_p), ("pool", _ct.c_void_p), ("masked_feat", _ct.c_void_p), ("feat_mask", _ct.c_void_p),
+                ("input_ids", _ct.c_void_p), ("input_mask", _ct.c_void_p), ("input_ids_out", _ct.c_void_p),
+                ("masked_lm_labels", _ct.c_void_p), ("label_ids", _ct.c_void_p), ("label_scores", _ct.c_void_p),
+                ("is_matched", _ct.c_void_p), ("ans", _ct.c_void_p), ("B", _ct.c_int), ("T", _ct.c_int), ("O", _ct.c_int),
+                ("F", _ct.c_int), ("K", _ct.c_int), ("P", _ct.c_int64), ("vocab_size", _ct.c_int64), ("mask_id", _ct.c_int64),
+                ("word_mask_rate", _ct.c_double), ("obj_mask_rate", _ct.c_double), ("u_word", _ct.c_void_p),
+                ("u_word_pick", _ct.c_void_p), ("u_obj", _ct.c_void_p), ("u_obj_pick", _ct.c_void_p), ("u_ans", _ct.c_void_p),
+                ("rng", _ct.c_void_p), ("sid_base", _ct.c_uint32)]
+
+
+def pretrain_corrupt(input_ids, input_mask, feats, is_matched, label_ids, label_scores, word_mask_rate, obj_mask_rate,
+                     vocab_size, mask_id, rng=None, sid_base=0, pool=None, draws=None, out=None):
+    """random_word / random_feat / the QA answer draw of src/pretrain/lxmert_pretrain.py:76-215 for a batch on the device, one
+    launch; contract: xggm_pretrain_corrupt_* in xggm.h.  ``feats`` [B, O, F] fp32 or bf16, ``input_ids`` / ``input_mask``
+    [B, T] int64, ``label_ids`` [B, K] int64 (-1 padded), ``label_scores`` [B, K] fp32, ``is_matched`` [B] int64.  ``draws``:
+    a dict with any of ``PRETRAIN_DRAWS`` (fp32, row-major); a missing one is drawn from ``rng`` at stream ``sid_base + k``.
+    ``out``: a dict of the five outputs to write into (else they are allocated).
+    -> dict(input_ids, masked_lm_labels, masked_feat, feat_mask, ans)"""
+    _c(feats, None, "feats")
+    sfx(feats.dtype)
+    if feats.dim() != 3 or input_ids.dim() != 2 or label_ids.dim() != 2:
+        raise ValueError("pretrain_corrupt: feats [B, O, F], input_ids [B, T] and label_ids [B, K] expected")
+    B, O, F = feats.shape
+    T, K = input_ids.shape[1], label_ids.shape[1]
+    dev = feats.device
+    _c(input_ids, torch.int64, "input_ids"), _c(input_mask, torch.int64, "input_mask"), _c(is_matched, torch.int64, "is_matched")
+    _c(label_ids, torch.int64, "label_ids"), _c(label_scores, F32, "label_scores")
+    if (tuple(input_ids.shape) != (B, T) or tuple(input_mask.shape) != (B, T) or tuple(label_ids.shape) != (B, K)
+            or tuple(label_scores.shape) != (B, K) or is_matched.numel() != B):
+        raise ValueError("pretrain_corrupt: operands do not share B=%d (T=%d, K=%d)" % (B, T, K))
+    if min(B, T, O, F, K) <= 0:
+        raise ValueError("pretrain_corrupt: empty batch B=%d T=%d O=%d F=%d K=%d" % (B, T, O, F, K))
+    a = PretrainCorruptArgs()
+    if pool is not None:
+        _c(pool, feats.dtype, "pool")
+        if pool.dim() != 2 or pool.shape[1] != F or pool.shape[0] <= 0:
+            raise ValueError("pretrain_corrupt: pool %s is no [P, %d] table" % (tuple(pool.shape), F))
+        a.pool, a.P = ptr(pool), pool.shape[0]
+    draws = dict(draws or {})
+    sizes = dict(u_word=B * T, u_word_pick=B * T, u_obj=B * O, u_obj_pick=B * O, u_ans=B)
+    if set(draws) - set(sizes):
+        raise ValueError("pretrain_corrupt: unknown draws %s" % sorted(set(draws) - set(sizes)))
+    for k, n in sizes.items():
+        d = draws.get(k)
+        if d is not None:
+            _c(d, F32, k)
+            if d.numel() != n:
+                raise ValueError("pretrain_corrupt: %s has %d draws, %d expected" % (k, d.numel(), n))
+        setattr(a, k, ptr(d))
+    if rng is None:
+        if any(draws.get(k) is None for k in sizes):
+            raise ValueError("pretrain_corrupt: a missing draw buffer needs rng")
+    else:
+        _c(rng, torch.int64, "rng")
+    if out is None:
+        out = dict(input_ids=torch.empty_like(input_ids), masked_lm_labels=torch.empty_like(input_ids),
+                   masked_feat=torch.empty_like(feats), feat_mask=torch.empty((B, O), device=dev, dtype=F32),
+                   ans=torch.empty(B, device=dev, dtype=torch.int64))
+    _c(out["input_ids"], torch.int64, "out input_ids"), _c(out["masked_lm_labels"], torch.int64, "out masked_lm_labels")
+    _c(out["masked_feat"], feats.dtype, "out masked_feat"), _c(out["feat_mask"], F32, "out feat_mask")
+    _c(out["ans"], torch.int64, "out ans")
+    if (out["input_ids"].numel() != B * T or out["masked_lm_labels"].numel() != B * T or out["masked_feat"].numel() != B * O * F
+            or out["feat_mask"].numel() != B * O or out["ans"].numel() != B):
+        raise ValueError("pretrain_corrupt: output buffers do not fit B=%d T=%d O=%d F=%d" % (B, T, O, F))
+    for t in (input_ids, input_mask, is_matched, label_ids, label_scores, pool, rng) + tuple(draws.values()) + tuple(out.values()):
+        if t is not None and t.device != dev:
+            raise RuntimeError("pretrain_corrupt: all operands must live on one device")
+    a.feats, a.masked_feat, a.feat_mask = ptr(feats), ptr(out["masked_feat"]), ptr(out["feat_mask"])
+    a.input_ids, a.input_mask = ptr(input_ids), ptr(input_mask)
+    a.input_ids_out, a.masked_lm_labels = ptr(out["input_ids"]), ptr(out["masked_lm_labels"])
+    a.label_ids, a.label_scores, a.is_matched, a.ans = ptr(label_ids), ptr(label_scores), ptr(is_matched), ptr(out["ans"])
+    a.B, a.T, a.O, a.F, a.K = B, T, O, F, K
+    a.vocab_size, a.mask_id = int(vocab_size), int(mask_id)
+    a.word_mask_rate, a.obj_mask_rate = float(word_mask_rate), float(obj_mask_rate)
+    a.rng, a.sid_base = ptr(rng), int(sid_base)
+    call("xggm_pretrain_corrupt_" + sfx(feats.dtype), _ct.addressof(a), stream())
+    return out
 
 
 # ----------------------------------------------------------------------------- graph attention

@@ -34,6 +34,8 @@ def build_parser():
     p.add_argument("--fromScratch", dest="from_scratch", action="store_const", default=False, const=True)
     p.add_argument("--multiGPU", action="store_const", default=False, const=True)
     p.add_argument("--mceLoss", dest="mce_loss", action="store_const", default=False, const=True)  # src/param.py:78
+    p.add_argument("--wordMaskRate", dest="word_mask_rate", default=0.15, type=float)  # src/param.py:102-105
+    p.add_argument("--objMaskRate", dest="obj_mask_rate", default=0.15, type=float)
     p.add_argument("--vocab", dest="vocab_path", type=str, default=None,
                    help="local BERT vocab.txt (the reference downloads it; offline it must be given)")
     return p

@@ -126,7 +126,8 @@ def pretrain_case(B, T=20, O=36, F=2048, vocab=30522, n_obj=1600, n_attr=400, n_
     except on about ``mask_rate`` of the real tokens; every edge the parity cases need is forced when B >= 3: sample 0
     has NO masked token, sample 1 masks position 1 and its last real token, both matched classes occur, ``ans`` holds a
     -1, one object label is -1 under a positive confidence, one object row has confidence 0 in all three losses, and
-    the feature targets lie on both sides of |prediction - target| = 1 of anything near zero.  All float32 / int64."""
+    the feature targets lie on both sides of |prediction - target| = 1 of anything near zero.  All float32 / int64.
+    (The masking itself, on the device: ``xggm_amd.pretrain.lxmert_pretrain.DeviceFeatures``.)"""
     r = _rng(seed, "pretrain_case:%d:%d:%d" % (B, T, O))
     ids = np.zeros((B, T), dtype=np.int64)
     mask = np.zeros((B, T), dtype=np.int64)
