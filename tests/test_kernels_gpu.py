@@ -11,7 +11,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
-from helpers import rel_err  # noqa: E402
+from helpers import assert_excess, gemm_excess, rel_err  # noqa: E402
 
 
 @pytest.fixture(scope="module")
@@ -30,6 +30,15 @@ def tol(dt, f32=2e-5, bf=1.2e-2):
     return f32 if dt == torch.float32 else bf
 
 
+def within_bound(got, ref, a, b, K, out_dtype, what, plus=(), scale=1.0):
+    """every element of ``got`` inside the derived GEMM bound (helpers.gemm_excess) around the fp64 ``ref`` = a @ b
+    (+ the terms of ``plus``); a, b: the fp64 operands as the kernel read them.  The magnitude sum runs on the GPU."""
+    S = (a.abs().to(DEV) @ b.abs().to(DEV)) * scale
+    for t in plus:
+        S = S + t.abs().to(DEV)
+    return assert_excess(gemm_excess(got, ref.to(DEV), S, K, out_dtype), what)
+
+
 def rnd(shape, dt, seed, scale=1.0):
     g = torch.Generator().manual_seed(seed)
     x = (torch.randn(shape, generator=g) * scale).to(dt)
@@ -46,9 +55,11 @@ def test_linear_fwd_dgrad_wgrad(ops, dt, M, N, K):
     y, _ = ops.linear_fwd(x, w, b)
     ref = xr @ wr.t() + b.double().cpu()
     assert rel_err(y, ref) < tol(dt)
+    within_bound(y, ref, xr, wr.t(), K, dt, "linear_fwd", plus=(b.double(),))
     # gelu + preact
     y2, pre = ops.linear_fwd(x, w, b, act=ops.ACT_GELU, want_preact=True)
     assert rel_err(pre, ref) < tol(dt)
+    within_bound(pre, ref, xr, wr.t(), K, dt, "linear_fwd preact", plus=(b.double(),))
     pr = pre.double().cpu()
     assert rel_err(y2, pr * 0.5 * (1 + torch.erf(pr / math.sqrt(2)))) < tol(dt)
     # f32 output with sigmoid
@@ -59,6 +70,7 @@ def test_linear_fwd_dgrad_wgrad(ops, dt, M, N, K):
     res, resr = rnd((M, K), dt, 5)
     dx = ops.linear_dgrad(dy, w, residual=res)
     assert rel_err(dx, dyr @ wr + resr) < tol(dt)
+    within_bound(dx, dyr @ wr + resr, dyr, wr, N, dt, "linear_dgrad", plus=(resr,))
     # dgrad fused with GELU backward
     u, ur = rnd((M, K), dt, 6)
     dxg = ops.linear_dgrad(dy, w, gelu_aux=u)
@@ -75,8 +87,10 @@ def test_linear_fwd_dgrad_wgrad(ops, dt, M, N, K):
     gw = torch.full((N, K), 7.0, device=DEV)
     ops.linear_wgrad(dy, x, gw, accumulate=False)
     assert rel_err(gw, dyr.t() @ xr) < tol(dt, 2e-5, 1e-4)
+    within_bound(gw, dyr.t() @ xr, dyr.t(), xr, M, torch.float32, "linear_wgrad")
     ops.linear_wgrad(dy, x, gw, accumulate=True)
     assert rel_err(gw, 2 * (dyr.t() @ xr)) < tol(dt, 2e-5, 1e-4)
+    within_bound(gw, 2 * (dyr.t() @ xr), dyr.t(), xr, M, torch.float32, "linear_wgrad accumulated", scale=2.0)
     # bias grad
     gb = torch.zeros(N, device=DEV)
     ops.colsum(dy, gb)
@@ -139,10 +153,14 @@ def test_grouped_gemm(ops, dt, group_tile):
     ops.gemm_group(dt, [p1, p2, p3, p4], tile=group_tile)
     pr = pre1.double().cpu()
     assert rel_err(pre1, xlr @ w1r.t() + b1.double().cpu()) < tol(dt)
+    within_bound(pre1, xlr @ w1r.t() + b1.double().cpu(), xlr, w1r.t(), 768, dt, "grouped preact", plus=(b1.double(),))
     assert rel_err(y1, pr * 0.5 * (1 + torch.erf(pr / math.sqrt(2)))) < tol(dt)
     assert rel_err(y2, xvr @ w2r.t()) < tol(dt)
+    within_bound(y2, xvr @ w2r.t(), xvr, w2r.t(), 768, dt, "grouped forward")
     assert rel_err(dx, dyr @ w2r + resr) < tol(dt)
+    within_bound(dx, dyr @ w2r + resr, dyr, w2r, 768, dt, "grouped dgrad", plus=(resr,))
     assert rel_err(gw, 3.0 + dyr.t() @ xvr) < tol(dt, 2e-5, 1e-4)
+    within_bound(gw, 3.0 + dyr.t() @ xvr, dyr.t(), xvr, 1152, torch.float32, "grouped wgrad", plus=(torch.tensor(3.0),))
     # six problems in ONE launch (the cross-attention backward's five, the graph blocks' six read-out problems) give
     # the bits of the same problems launched alone
     def six():

@@ -194,9 +194,15 @@ __device__ __forceinline__ void stage_tile(T* __restrict__ lds, const T* __restr
     }
 }
 
+// GELU for fp32 STORAGE (the generic kernel): x Phi(x) through erfc.  gelu_f's 1 + erf(x / sqrt 2) cancels for x < 0, where
+// the 1.5e-7 of erf_fast is all that is left: at x = -3.1 (gelu = -2.7e-3) the result is off by 2.4e-7, 1e-4 of its value
+// and past 4 ulp of 1 -- invisible behind a bf16 store, the largest error of an fp32 one (tests/test_gemm_edges_gpu.py).
+// erfc has no cancellation; the bf16 kernels keep the cheap form.
+__device__ __forceinline__ float gelu_f32_storage(float x) { return 0.5f * x * erfcf(-x * 0.70710678118654752440f); }
+
 template <typename T> __device__ __forceinline__ float act_apply(int act, float v, float aux) {
     switch (act) {
-        case XGGM_ACT_GELU: return gelu_f(v);
+        case XGGM_ACT_GELU: return sizeof(T) == 4 ? gelu_f32_storage(v) : gelu_f(v);
         case XGGM_ACT_SIGMOID: return sigmoid_f(v);
         case XGGM_ACT_TANH: return tanhf(v);
         case XGGM_ACT_GELU_GRAD: return v * gelu_grad_f(aux);
