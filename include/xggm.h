@@ -816,6 +816,58 @@ typedef struct xggm_pretrain_corrupt_args {
 int xggm_pretrain_corrupt_f32(const xggm_pretrain_corrupt_args* args, xggm_stream_t stream);
 int xggm_pretrain_corrupt_bf16(const xggm_pretrain_corrupt_args* args, xggm_stream_t stream);
 
+/* xggm_pretrain_swap: the matched-sentence swap LXMERTTorchDataset.__getitem__ applies to every example on the host with
+ * Python's random (src/pretrain/lxmert_data.py:173-183) -- with probability 0.5 the sentence is replaced by the sentence of
+ * a random datum of ANOTHER image and is_matched becomes 0 -- for a whole clean batch that is already on the device, in ONE
+ * launch, ahead of xggm_pretrain_corrupt_* (the reference swaps in the data set, then masks: the same order).
+ *   ids, mask [B, T] int64: the clean sentences; img [B] int64: an integer key per image; matched_in [B] int64 or NULL (all 1).
+ *   pool_ids, pool_mask [P, T], pool_img [P]: the sentences a swap draws from (the reference: every datum of the data set);
+ *   all three NULL: the batch's own rows, P = B.
+ *   row b:  matched_in[b] != 1:            a copy, is_matched[b] = matched_in[b] (no draw is looked at);
+ *           else u_swap[b] < rate false:   a copy, is_matched[b] = 1;
+ *           else for r = 0 .. TRIES - 1:   j = min(floor(u_pick[b, r] * P), P - 1); the FIRST j with pool_img[j] != img[b]
+ *                                          wins: out row = pool row j (ids and mask), is_matched[b] = 0;
+ *           all TRIES candidates show img[b]: a copy, is_matched[b] = 1 and *exhausted += 1.
+ * Two deviations from the reference: its `while other_datum['img_id'] == img_id` loop (:181-182) has no bound -- here
+ * XGGM_PRETRAIN_SWAP_TRIES candidates are looked at and a row that finds none stays matched and is COUNTED (a pool of one
+ * image would hang the reference); and its random.randint(0, n - 1) is taken as floor(u * n) of one uniform draw: the same
+ * distribution, not the stream of Python's generator.
+ * u_swap < rate and u_pick * P are evaluated in double from the fp32 draw, as in xggm_pretrain_corrupt_*; a supplied pick
+ * draw outside [0, 1) is held inside the pool.  Rows move as 16-byte vectors when T * 8 is a multiple of 16 and ids, mask,
+ * the pool and the outputs are 16-byte aligned, element by element otherwise.  No floating-point arithmetic touches the
+ * data: every output is exact.
+ * Draws: u_swap [B] and u_pick [B, TRIES] (fp32 in [0, 1)).  A NULL buffer means philox_uniform(seed, offset, sid_base + 5,
+ * b) resp. philox_uniform(seed, offset, sid_base + 6, b * TRIES + r) with {seed, offset} = rng[0..1]: streams 5 and 6 behind
+ * the five of xggm_pretrain_corrupt_* at the same sid_base, exactly what xggm_uniform(out, n, rng, sid_base + 5 / 6) exports.
+ * rng is only read.
+ * exhausted: int32 [1], only ever grows (one integer atomic add per exhausted row: no result depends on an order).
+ * One launch, one wave per row; no allocation, no host synchronisation.  Refused before any launch: a null struct, a null
+ * ids / mask / img or output pointer (out_ids, out_mask, is_matched, exhausted), B, T or P <= 0, a pool with one of its
+ * three pointers missing, rate outside [0, 1], a NULL draw buffer without rng, an output (out_ids, out_mask, is_matched,
+ * exhausted) overlapping ids, mask, img, matched_in, the pool or another output. */
+#define XGGM_PRETRAIN_SWAP_TRIES 8
+typedef struct xggm_pretrain_swap_args {
+    const int64_t* ids;        /* [B, T] */
+    const int64_t* mask;       /* [B, T] */
+    const int64_t* img;        /* [B] */
+    const int64_t* matched_in; /* [B] or NULL */
+    const int64_t* pool_ids;   /* [P, T] or NULL */
+    const int64_t* pool_mask;  /* [P, T] or NULL */
+    const int64_t* pool_img;   /* [P] or NULL */
+    int64_t* out_ids;          /* [B, T] out */
+    int64_t* out_mask;         /* [B, T] out */
+    int64_t* is_matched;       /* [B] out */
+    int32_t* exhausted;        /* [1] in/out */
+    int B, T;
+    int64_t P;                 /* rows of the pool (ignored when the pool is NULL) */
+    double rate;
+    const float* u_swap;       /* [B] or NULL */
+    const float* u_pick;       /* [B, TRIES] or NULL */
+    const uint64_t* rng;       /* {seed, offset}; needed when a draw buffer is NULL */
+    uint32_t sid_base;
+} xggm_pretrain_swap_args;
+int xggm_pretrain_swap(const xggm_pretrain_swap_args* args, xggm_stream_t stream);
+
 /* ---- preprocessing that feeds the path ----------------------------------------------------
  * adj_true of every sample: data/preprocess/vqa/compute_adjacency.py:38-45 (compute_cosin_sim_v2) + :90.
  *   c[i][j] = cos(cls[i], attr[j]) for j >= i, 0 below the diagonal  (torch.cosine_similarity, eps 1e-6: each

@@ -677,3 +677,241 @@ class CapturedPredictor:
             self.logit, self.label = self._forward()
             self.model.train(was_training)
         return b
+
+
+class CapturedPretrainer:
+    """The LXMERT pre-training step (``LXMERT.train_batch`` / ``valid_batch``, src/pretrain/lxmert_pretrain.py:308-326) as
+    ONE replayed graph per step: one pass kind, one graph, no data parallelism.
+
+        feats = DeviceFeatures.from_args(args, swap=True, vocab_size=..., max_labels=K)
+        tr = CapturedPretrainer(model, optim, batch, feats, train_log=TrainLog(n, dev), answer_log=AnswerLog(n * B, dev, False))
+        for batch in loader: tr.load_batch(batch); tr.step()          # no host synchronisation
+        tr.check(); rec = tr.train_log.read()                         # once per N steps
+
+    ``batch``: dict of DEVICE tensors of the CLEAN batch -- input_ids, input_mask, segment_ids, feats, boxes, obj_labels,
+    obj_confs, attr_labels, attr_confs, is_matched, label_ids, label_scores (``pretrain.lxmert_pretrain.pack_labels``) and,
+    with a swap (``features.match_rate``), img_ids and optionally pool_ids / pool_mask / pool_img; optionally feat_pool (the
+    replacement rows of the object masking).  They become the static input buffers; ``load_batch`` copies into them.
+
+    ``step()`` holds, in order: the swap (when configured) and the masking (``features``: one or two launches),
+    ``LXRTPretraining.forward``, ``Runtime.backward``, ``clip_and_step(model, optim, clip, advance=True)`` (the reference
+    clips at 1.0, :315), the log appends.  ``features`` draws from the model's runtime state ``runtime_of(model).rng``: the
+    ONE advance at the end of the step moves masks, swaps, dropout and noise together, and a restored ``rng``
+    (``vqa.vqacpv2.load_training_state``) reproduces the run.  ``valid_step()`` is the forward-only twin (:320-326),
+    captured under ``model.eval()``: swap, masking, forward, log appends, the rng advance -- no backward, no update.
+
+    The warm-up steps and the capture run on the first batch like everything else here, but what they changed is put back
+    before the constructor returns -- parameters, moments, step counters, ``rng``, the overflow flag and the swap's
+    exhausted counter -- so a captured run, an eager run (``use_graph=False``: the same calls, not captured, no warm-up) and
+    a restored run start from the same state and give the same bits.  ``warmup_iters=0``: the caller has run an eager step
+    already (a capture needs every workspace to exist); nothing is snapshotted.
+
+    ``optim=None``: a validation-only engine (an eval loader with a batch size of its own, an evaluation before any
+    training).  Only the forward-only graph is warmed up and captured, no optimiser step is ever taken on the model -- not
+    even one that is rolled back -- and ``step()`` raises.
+
+    ``train_log`` / ``valid_log`` (``TrainLog``; observe only, None adds no launch): one record of kind
+    ``trainlog.PRETRAIN`` per step -- LOSS, the reference's six terms at the fixed columns 1-6 (a task that is off leaves its
+    column absent), the pre-clip norm in column 7 (absent in ``valid_log``); the record's step is the optimiser counter of the
+    arena group that holds ``cls.predictions``.  ``answer_log`` (``AnswerLog(with_scores=False)``): every step of either
+    kind ends with ``ops.answer_pick`` on the fp32 answer scores (``logit.max(1)`` of :357 / :392 without its ``.cpu()``).
+    A batch of another size than the static one (the ragged last batch of an epoch) goes through ``step(batch)`` /
+    ``valid_step(batch)``: the same calls run eagerly on it."""
+
+    KEYS = ("input_ids", "input_mask", "segment_ids", "feats", "boxes", "obj_labels", "obj_confs", "attr_labels", "attr_confs",
+            "is_matched", "label_ids", "label_scores")
+    POOL = ("pool_ids", "pool_mask", "pool_img")
+
+    def __init__(self, model, optim, batch, features, clip=1.0, use_graph=True, warmup_iters=2, train_log=None,
+                 valid_log=None, answer_log=None):
+        from . import trainlog as T
+        from .lxrt.modeling import VISUAL_CONFIG
+        self.model, self.optim, self.features, self.clip = model, optim, features, clip
+        self.train_log, self.valid_log, self.answer_log = train_log, valid_log, answer_log
+        missing = [k for k in self.KEYS if k not in batch]
+        if features.match_rate is not None and "img_ids" not in batch:
+            missing.append("img_ids")
+        if missing:
+            raise ValueError("CapturedPretrainer: the batch lacks %s" % missing)
+        if 0 < sum(k in batch for k in self.POOL) < 3:
+            raise ValueError("CapturedPretrainer: a sentence pool is pool_ids, pool_mask and pool_img together")
+        if answer_log is not None and (answer_log.with_scores or not model.task_qa):
+            raise ValueError("CapturedPretrainer: answer_log is an AnswerLog(with_scores=False) and needs the QA task")
+        if optim is None and train_log is not None:
+            raise ValueError("CapturedPretrainer: a validation-only engine (optim=None) appends to no train_log")
+        self.static = {k: v.clone() for k, v in batch.items() if torch.is_tensor(v)}
+        self.B = self.static["input_ids"].shape[0]
+        self.rt = runtime_of(model)
+        cols = [T.PT_MASK_LM] if model.task_mask_lm else []
+        cols += [T.PT_MATCHED] if model.task_matched else []
+        if model.task_obj_predict:
+            cols += [dict(obj=T.PT_OBJ, attr=T.PT_ATTR, feat=T.PT_FEAT)[k] for k in VISUAL_CONFIG.visual_losses]
+        cols += [T.PT_QA] if model.task_qa else []
+        self.columns = cols  # column of the i-th entry of the ``losses`` the model returns
+        self.use_graph = use_graph
+        self.graphs, self.outputs = {}, {}
+        self._flags = torch.zeros(1, dtype=torch.int64, device=self.static["input_ids"].device)
+        self._flags_host = torch.zeros(1, dtype=torch.int64).pin_memory()
+        if use_graph:
+            self._capture(warmup_iters)
+
+    # ------------------------------------------------------------------ the two passes
+    def _corrupt(self, s):
+        pool = tuple(s[k] for k in self.POOL) if self.POOL[0] in s else None
+        return self.features(*[s[k] for k in self.KEYS], self.rt.rng, pool=s.get("feat_pool"), img_ids=s.get("img_ids"),
+                             sent_pool=pool)
+
+    def _observe(self, log, loss, losses, norm, ans):
+        from . import trainlog as T
+        if log is not None:
+            if losses.shape[1] != len(self.columns):
+                raise RuntimeError("CapturedPretrainer: the model returned %d loss terms, its tasks name %d"
+                                   % (losses.shape[1], len(self.columns)))
+            cols = [None] * T.COLS
+            cols[T.LOSS] = loss
+            for i, c in enumerate(self.columns):
+                cols[c] = losses[0, i:i + 1]
+            cols[T.PT_GRAD_NORM] = norm
+            arena = self.rt.arena
+            xg = getattr(next(self.model.cls.predictions.parameters()), "_xg", None)
+            gi = arena.group_index[xg[3]] if xg is not None and xg[0] is arena else None
+            ops.train_log_append(log, T.PRETRAIN, cols, step=None if gi is None else arena.steps[gi:gi + 1])
+        if self.answer_log is not None:
+            ops.answer_pick(ans if ans.dtype == torch.float32 else ans.float(), self.answer_log)
+
+    def _train_pass(self, s):
+        self.model.train()
+        total, losses, ans = self.model(*self._corrupt(s))
+        self.rt.backward(total)
+        norm = clip_and_step(self.model, self.optim, self.clip, advance=True)
+        loss = total.detach()
+        self._observe(self.train_log, loss, losses, norm, ans)
+        return loss, losses, ans, norm
+
+    def _valid_pass(self, s):
+        was_training = self.model.training
+        self.model.eval()
+        with torch.no_grad():
+            total, losses, ans = self.model(*self._corrupt(s))
+            loss = total.detach()
+            self._observe(self.valid_log, loss, losses, None, ans)
+            self.rt.advance()
+        self.model.train(was_training)
+        return loss, losses, ans, None
+
+    def _passes(self):
+        train = [("train", self._train_pass)] if self.optim is not None else []
+        return train + [("valid", self._valid_pass)]
+
+    # ------------------------------------------------------------------ capture
+    def _snapshot(self):
+        f = self.features
+        trains = self.optim is not None  # validation passes change no weight and no moment: nothing of them to put back
+        return dict(model={k: v.clone() for k, v in self.model.state_dict().items()} if trains else None,
+                    optim=self.optim.state_dict() if trains else None, rng=self.rt.rng.clone(),
+                    overflow=None if self.model.mlm_overflow is None else self.model.mlm_overflow.clone(),
+                    exhausted=None if f.swap_exhausted is None else f.swap_exhausted.clone())
+
+    def _restore(self, snap):
+        if snap["model"] is not None:
+            self.model.load_state_dict(snap["model"])
+            self.rt = runtime_of(self.model)  # refreshes the bf16 shadows, outside of any capture
+            self.optim.load_state_dict(snap["optim"])
+        self.rt.rng.copy_(snap["rng"])
+        # the two device counters: back to what they held, or to zero when the warm-up created them
+        for t, was in ((self.model.mlm_overflow, snap["overflow"]), (self.features.swap_exhausted, snap["exhausted"])):
+            if t is not None:
+                t.copy_(was if was is not None else torch.zeros_like(t))
+        for log in (self.train_log, self.valid_log, self.answer_log):
+            if log is not None:
+                log.reset()  # what the warm-up steps logged
+
+    def _capture(self, warmup_iters):
+        was_training = self.model.training
+        snap = self._snapshot() if warmup_iters > 0 else None
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            for _ in range(warmup_iters):
+                for _, run in self._passes():
+                    run(self.static)
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+        with _quiet_gc():
+            for kind, run in self._passes():
+                g = torch.cuda.CUDAGraph()  # a memory pool per graph: the outputs of one are not the other's scratch
+                with torch.cuda.graph(g):
+                    out = run(self.static)
+                self.graphs[kind], self.outputs[kind] = g, out
+        torch.cuda.synchronize()
+        if snap is not None:
+            self._restore(snap)
+        self.model.train(was_training)
+        torch.cuda.synchronize()
+
+    # ------------------------------------------------------------------ run
+    def load_batch(self, batch):
+        for k, v in batch.items():
+            if k in self.static:
+                self.static[k].copy_(v, non_blocking=True)
+
+    def _run(self, kind, batch):
+        if kind == "train" and self.optim is None:
+            raise RuntimeError("CapturedPretrainer.step: this engine was built without an optimiser (validation only)")
+        run = self._train_pass if kind == "train" else self._valid_pass
+        if batch is not None and batch["input_ids"].shape[0] != self.B:
+            if self.answer_log is not None:
+                self.answer_log.note(batch["input_ids"].shape[0])
+            return run(batch)  # the ragged last batch: the same calls, eagerly, on the batch as it is
+        if batch is not None:
+            self.load_batch(batch)
+        if self.answer_log is not None:
+            self.answer_log.note(self.B)
+        if not self.use_graph:
+            return run(self.static)
+        runtime_of(self.model)  # weights loaded since the last step (load_state_dict): the bf16 shadows are refreshed here
+        self.graphs[kind].replay()
+        return self.outputs[kind]
+
+    def step(self, batch=None):
+        """one training step -> (loss, losses [1, n], answer scores, pre-clip norm): device tensors, views of static
+        buffers under a graph (consume them before the next step).  ``batch``: loaded first; another batch size than the
+        static one runs eagerly"""
+        return self._run("train", batch)
+
+    def valid_step(self, batch=None):
+        """the forward-only step -> (loss, losses, answer scores, None); it changes no parameter and no optimiser state"""
+        return self._run("valid", batch)
+
+    def check(self):
+        """ONE synchronisation per read-back: the masked-LM overflow flag ``model.mlm_overflow`` (more labelled rows than
+        ``mlm_capacity`` slots: the masked-LM loss of that step was NaN).  Nothing is raised while it is clear -- a NaN of
+        another origin (a batch whose swap left no QA label has a NaN QA loss, as in the reference) is the log's business
+        (``first_bad``), not an error here.  When it is set, the attached logs are read (the failing path alone pays that
+        second transfer) and the RuntimeError names the first retained record whose Mask_LM column is NaN -- its number
+        since the log's reset and the optimiser step it carries -- not merely the first non-finite record; the flag is
+        cleared, so the next read-back reports the next overflow.  Called by the driver once per read-back, never per
+        step."""
+        from . import trainlog as T
+        flag = self.model.mlm_overflow
+        if flag is None:
+            return
+        self._flags[0:1].copy_(flag)
+        self._flags_host.copy_(self._flags, non_blocking=True)
+        torch.cuda.current_stream(self._flags.device).synchronize()
+        if not int(self._flags_host[0]):
+            return
+        flag.zero_()
+        where = []
+        for name, log in (("training", self.train_log), ("validation", self.valid_log)):
+            if log is None:
+                continue
+            rec = log.read()
+            bad = (torch.isnan(rec["values"][:, T.PT_MASK_LM]) & rec["present"][:, T.PT_MASK_LM]).nonzero().reshape(-1)
+            if bad.numel():
+                row, m = int(bad[0]), rec["values"].shape[0]
+                number = int(rec["cursor"]) - m + row
+                where.append("the first %s record with a NaN Mask_LM is number %d since the log's reset (step %d of this "
+                             "window, optimiser step %d)" % (name, number, number + 1, int(rec["steps"][row])))
+        raise RuntimeError("masked-LM overflow: a batch had more labelled tokens than mlm_capacity=%r slots; %s"
+                           % (self.model.mlm_capacity, "; ".join(where) or "no attached log retains the step"))

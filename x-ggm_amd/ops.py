@@ -2290,6 +2290,88 @@ def pretrain_corrupt(input_ids, input_mask, feats, is_matched, label_ids, label_
     return out
 
 
+PRETRAIN_SWAP_TRIES = 8                      # XGGM_PRETRAIN_SWAP_TRIES (include/xggm.h)
+PRETRAIN_SWAP_DRAWS = ("u_swap", "u_pick")   # Philox streams sid_base + 5, sid_base + 6: behind PRETRAIN_DRAWS
+
+
+class PretrainSwapArgs(_ct.Structure):
+    """mirror of ``xggm_pretrain_swap_args`` (include/xggm.h)"""
+    _fields_ = [("ids", _ct.c_void_p), ("mask", _ct.c_void_p), ("img", _ct.c_void_p), ("matched_in", _ct.c_void_p),
+                ("pool_ids", _ct.c_void_p), ("pool_mask", _ct.c_void_p), ("pool_img", _ct.c_void_p), ("out_ids", _ct.c_void_p),
+                ("out_mask", _ct.c_void_p), ("is_matched", _ct.c_void_p), ("exhausted", _ct.c_void_p), ("B", _ct.c_int),
+                ("T", _ct.c_int), ("P", _ct.c_int64), ("rate", _ct.c_double), ("u_swap", _ct.c_void_p), ("u_pick", _ct.c_void_p),
+                ("rng", _ct.c_void_p), ("sid_base", _ct.c_uint32)]
+
+
+def pretrain_swap(ids, mask, img, rate=0.5, matched_in=None, pool=None, rng=None, sid_base=0, draws=None, out=None):
+    """the matched-sentence swap of src/pretrain/lxmert_data.py:173-183 for a clean batch on the device, one launch;
+    contract: xggm_pretrain_swap in xggm.h.  ``ids`` / ``mask`` [B, T] int64, ``img`` [B] int64 (a key per image),
+    ``matched_in`` [B] int64 or None (all 1), ``pool``: None (the batch's own rows) or (pool_ids [P, T], pool_mask [P, T],
+    pool_img [P]).  ``draws``: a dict with any of ``PRETRAIN_SWAP_DRAWS`` (fp32; u_swap [B], u_pick [B, 8]); a missing one is
+    drawn from ``rng`` at stream ``sid_base + 5`` / ``+ 6``.  ``out``: a dict of the four outputs to write into (else they
+    are allocated; a fresh ``exhausted`` starts at 0, a supplied one is added to).
+    -> dict(input_ids, input_mask, is_matched, exhausted)"""
+    _c(ids, torch.int64, "ids"), _c(mask, torch.int64, "mask"), _c(img, torch.int64, "img")
+    if ids.dim() != 2 or tuple(mask.shape) != tuple(ids.shape) or img.numel() != ids.shape[0]:
+        raise ValueError("pretrain_swap: ids / mask [B, T] and img [B] expected, got %s %s %s"
+                         % (tuple(ids.shape), tuple(mask.shape), tuple(img.shape)))
+    B, T = ids.shape
+    if min(B, T) <= 0:
+        raise ValueError("pretrain_swap: empty batch B=%d T=%d" % (B, T))
+    dev = ids.device
+    a = PretrainSwapArgs()
+    if matched_in is not None:
+        _c(matched_in, torch.int64, "matched_in")
+        if matched_in.numel() != B:
+            raise ValueError("pretrain_swap: matched_in has %d entries, %d expected" % (matched_in.numel(), B))
+    pool = tuple(pool) if pool is not None else ()
+    if pool:
+        if len(pool) != 3 or any(t is None for t in pool):
+            raise ValueError("pretrain_swap: pool is (pool_ids, pool_mask, pool_img)")
+        for t, name in zip(pool, ("pool_ids", "pool_mask", "pool_img")):
+            _c(t, torch.int64, name)
+        P = pool[2].numel()
+        if P <= 0 or tuple(pool[0].shape) != (P, T) or tuple(pool[1].shape) != (P, T):
+            raise ValueError("pretrain_swap: pool %s %s %s is no ([P, %d], [P, %d], [P])"
+                             % (tuple(pool[0].shape), tuple(pool[1].shape), tuple(pool[2].shape), T, T))
+        a.pool_ids, a.pool_mask, a.pool_img, a.P = ptr(pool[0]), ptr(pool[1]), ptr(pool[2]), P
+    draws = dict(draws or {})
+    sizes = dict(u_swap=B, u_pick=B * PRETRAIN_SWAP_TRIES)
+    if set(draws) - set(sizes):
+        raise ValueError("pretrain_swap: unknown draws %s" % sorted(set(draws) - set(sizes)))
+    for k, n in sizes.items():
+        d = draws.get(k)
+        if d is not None:
+            _c(d, F32, k)
+            if d.numel() != n:
+                raise ValueError("pretrain_swap: %s has %d draws, %d expected" % (k, d.numel(), n))
+        setattr(a, k, ptr(d))
+    if rng is None:
+        if any(draws.get(k) is None for k in sizes):
+            raise ValueError("pretrain_swap: a missing draw buffer needs rng")
+    else:
+        _c(rng, torch.int64, "rng")
+    if not 0.0 <= float(rate) <= 1.0:
+        raise ValueError("pretrain_swap: rate %r outside [0, 1]" % (rate,))
+    if out is None:
+        out = dict(input_ids=torch.empty_like(ids), input_mask=torch.empty_like(mask),
+                   is_matched=torch.empty(B, device=dev, dtype=torch.int64), exhausted=torch.zeros(1, device=dev, dtype=torch.int32))
+    _c(out["input_ids"], torch.int64, "out input_ids"), _c(out["input_mask"], torch.int64, "out input_mask")
+    _c(out["is_matched"], torch.int64, "out is_matched"), _c(out["exhausted"], torch.int32, "out exhausted")
+    if (out["input_ids"].numel() != B * T or out["input_mask"].numel() != B * T or out["is_matched"].numel() != B
+            or out["exhausted"].numel() != 1):
+        raise ValueError("pretrain_swap: output buffers do not fit B=%d T=%d" % (B, T))
+    for t in (mask, img, matched_in, rng) + pool + tuple(draws.values()) + tuple(out.values()):
+        if t is not None and t.device != dev:
+            raise RuntimeError("pretrain_swap: all operands must live on one device")
+    a.ids, a.mask, a.img, a.matched_in = ptr(ids), ptr(mask), ptr(img), ptr(matched_in)
+    a.out_ids, a.out_mask, a.is_matched, a.exhausted = ptr(out["input_ids"]), ptr(out["input_mask"]), ptr(out["is_matched"]), ptr(out["exhausted"])
+    a.B, a.T, a.rate = B, T, float(rate)
+    a.rng, a.sid_base = ptr(rng), int(sid_base)
+    call("xggm_pretrain_swap", _ct.addressof(a), stream())
+    return out
+
+
 # ----------------------------------------------------------------------------- graph attention
 def gat_att_fwd(s, adj, alpha):
     _c(s, F32, "s"), _c(adj, F32, "adj")

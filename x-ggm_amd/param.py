@@ -34,6 +34,13 @@ def build_parser():
     p.add_argument("--fromScratch", dest="from_scratch", action="store_const", default=False, const=True)
     p.add_argument("--multiGPU", action="store_const", default=False, const=True)
     p.add_argument("--mceLoss", dest="mce_loss", action="store_const", default=False, const=True)  # src/param.py:78
+    # LXMERT pre-training tasks, src/param.py:91-100 (``pretrain.lxmert_pretrain.LXMERT``)
+    p.add_argument("--taskMatched", dest="task_matched", action="store_const", default=False, const=True)
+    p.add_argument("--taskMaskLM", dest="task_mask_lm", action="store_const", default=False, const=True)
+    p.add_argument("--taskObjPredict", dest="task_obj_predict", action="store_const", default=False, const=True)
+    p.add_argument("--taskQA", dest="task_qa", action="store_const", default=False, const=True)
+    p.add_argument("--visualLosses", dest="visual_losses", default="obj,attr,feat", type=str)
+    p.add_argument("--output", type=str, default="snap/test")
     p.add_argument("--wordMaskRate", dest="word_mask_rate", default=0.15, type=float)  # src/param.py:102-105
     p.add_argument("--objMaskRate", dest="obj_mask_rate", default=0.15, type=float)
     p.add_argument("--vocab", dest="vocab_path", type=str, default=None,

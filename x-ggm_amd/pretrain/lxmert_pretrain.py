@@ -16,13 +16,25 @@ Deviations from the reference, both documented in INTEGRATION.md:
   * an example with several answer keys draws by inverse CDF on one uniform instead of ``np.random.multinomial``: the same
     distribution, not the same stream.
 
-Out of scope here: the matched-sentence swap of src/pretrain/lxmert_data.py:175-190 (string work in the data set;
-``is_matched`` arrives with the batch), data-set readers, a pre-training driver loop, and fusing the masking into the
-visual-embedding product's input read."""
+The matched-sentence swap of src/pretrain/lxmert_data.py:173-183 is opt-in (``DeviceFeatures(match_rate=0.5)``): one more
+launch (``ops.pretrain_swap``, contract: xggm_pretrain_swap in include/xggm.h) AHEAD of the corruption, which then reads the
+swapped ids and the new ``is_matched`` -- the reference's order (the data set swaps, ``convert_example_to_features`` masks).
+Its two deviations (a bounded number of candidates, ``randint`` as floor(u n)) are written down in INTEGRATION.md as well.
+
+The driver loop is at the bottom: ``InputExample``, ``collate_examples`` and ``LXMERT``, our own code behind the names and
+signatures of ``class LXMERT`` (src/pretrain/lxmert_pretrain.py:221-409), running on ``engine.CapturedPretrainer``.
+
+Out of scope here: the data-set readers and the evaluator of src/pretrain/lxmert_data.py (``LXMERTDataset``,
+``LXMERTTorchDataset``, ``LXMERTEvaluator``: the data files are absent offline; any ``(dataset, loader, evaluator)`` whose
+loader yields lists of ``InputExample`` serves), data-parallel pre-training, the packed loader ring of the fine-tuning
+side, and fusing the masking into the visual-embedding product's input read."""
+import os
+
 import numpy as np
 import torch
 
 from .. import ops
+from ..trainlog import LOSSES_NAME  # src/pretrain/lxmert_pretrain.py:218
 
 SID_BASE = 0x70726500  # far from the module streams (16 * (i + 1) + k) and the graph streams
 
@@ -54,17 +66,44 @@ class DeviceFeatures:
     ``input_ids, segment_ids, input_mask, lm_labels, masked_feat, pos, obj_labels, matched_labels, ans`` with
     ``obj_labels = {'obj': (obj_labels, obj_confs), 'attr': (attr_labels, attr_confs), 'feat': (feat, feat_mask)}``.
     The five output buffers are allocated once per (shape, dtype, device) and reused -- a call allocates nothing after the
-    first and can be captured; a consumer that keeps a result across calls has to copy it."""
+    first and can be captured; a consumer that keeps a result across calls has to copy it.
 
-    def __init__(self, word_mask_rate=0.15, obj_mask_rate=0.15, vocab_size=30522, mask_id=103, sid_base=SID_BASE, max_labels=4):
+    ``match_rate`` (None: no swap, nothing more is launched): the share of matched examples whose sentence is replaced by one
+    of another image (the reference fixes 0.5, src/pretrain/lxmert_data.py:178).  The swap runs first, from ``img_ids`` [B]
+    (an integer per image) and ``sent_pool`` = (pool_ids, pool_mask, pool_img) or None (the batch's own sentences); the
+    corruption reads the swapped ids, ``input_mask`` and ``matched_labels`` of the result are the swapped ones, and an
+    unmatched row gets ``ans = -1``.  ``swap_exhausted`` (int32 [1] on the device) counts the rows that found no other image
+    among their ``ops.PRETRAIN_SWAP_TRIES`` candidates and stayed matched."""
+
+    def __init__(self, word_mask_rate=0.15, obj_mask_rate=0.15, vocab_size=30522, mask_id=103, sid_base=SID_BASE, max_labels=4,
+                 match_rate=None):
         self.word_mask_rate, self.obj_mask_rate = float(word_mask_rate), float(obj_mask_rate)
         self.vocab_size, self.mask_id, self.sid_base, self.max_labels = int(vocab_size), int(mask_id), int(sid_base), int(max_labels)
-        self._out = {}
+        self.match_rate = None if match_rate is None else float(match_rate)
+        if self.match_rate is not None and not 0.0 <= self.match_rate <= 1.0:
+            raise ValueError("DeviceFeatures: match_rate %r outside [0, 1]" % (match_rate,))
+        self.swap_exhausted = None
+        self._out, self._swap = {}, {}
 
     @classmethod
-    def from_args(cls, args, **kw):
-        """rates from a flag namespace (``--wordMaskRate`` / ``--objMaskRate``, src/param.py:102-105)"""
+    def from_args(cls, args, swap=False, **kw):
+        """rates from a flag namespace (``--wordMaskRate`` / ``--objMaskRate``, src/param.py:102-105); ``swap=True``: the
+        sentence swap follows ``--taskMatched`` (rate 0.5 when the flag is set, as src/pretrain/lxmert_data.py:177-178)"""
+        if swap and "match_rate" not in kw:
+            kw["match_rate"] = 0.5 if getattr(args, "task_matched", False) else None
         return cls(word_mask_rate=args.word_mask_rate, obj_mask_rate=args.obj_mask_rate, **kw)
+
+    def _swap_buffers(self, input_ids):
+        key = (tuple(input_ids.shape), input_ids.device)
+        out = self._swap.get(key)
+        if out is None:
+            dev = input_ids.device
+            if self.swap_exhausted is None or self.swap_exhausted.device != dev:
+                self.swap_exhausted = torch.zeros(1, device=dev, dtype=torch.int32)
+            out = dict(input_ids=torch.empty_like(input_ids), input_mask=torch.empty_like(input_ids),
+                       is_matched=torch.empty(input_ids.shape[0], device=dev, dtype=torch.int64), exhausted=self.swap_exhausted)
+            self._swap[key] = out
+        return out
 
     def _buffers(self, input_ids, feats):
         B, T = input_ids.shape
@@ -81,13 +120,323 @@ class DeviceFeatures:
         return out
 
     def __call__(self, input_ids, input_mask, segment_ids, feats, boxes, obj_labels, obj_confs, attr_labels, attr_confs,
-                 is_matched, label_ids, label_scores, rng, pool=None, draws=None):
+                 is_matched, label_ids, label_scores, rng, pool=None, draws=None, img_ids=None, sent_pool=None):
         if label_ids.dim() != 2 or label_ids.shape[1] != self.max_labels:
             raise ValueError("DeviceFeatures: label_ids %s, [B, %d] expected (pack_labels(labels, %d))"
                              % (tuple(label_ids.shape), self.max_labels, self.max_labels))
+        draws = dict(draws or {})
+        swap_draws = {k: draws.pop(k) for k in ops.PRETRAIN_SWAP_DRAWS if k in draws}
+        if self.match_rate is not None:
+            if img_ids is None:
+                raise ValueError("DeviceFeatures: match_rate needs img_ids [B] (an integer per image)")
+            sw = ops.pretrain_swap(input_ids, input_mask, img_ids, self.match_rate, matched_in=is_matched, pool=sent_pool,
+                                   rng=rng, sid_base=self.sid_base, draws=swap_draws, out=self._swap_buffers(input_ids))
+            input_ids, input_mask, is_matched = sw["input_ids"], sw["input_mask"], sw["is_matched"]
+        elif swap_draws:
+            raise ValueError("DeviceFeatures: swap draws %s without a match_rate" % sorted(swap_draws))
         out = ops.pretrain_corrupt(input_ids, input_mask, feats, is_matched, label_ids, label_scores, self.word_mask_rate,
                                    self.obj_mask_rate, self.vocab_size, self.mask_id, rng=rng, sid_base=self.sid_base,
                                    pool=pool, draws=draws, out=self._buffers(input_ids, feats))
         visn = {'obj': (obj_labels, obj_confs), 'attr': (attr_labels, attr_confs), 'feat': (feats, out["feat_mask"])}
         return (out["input_ids"], segment_ids, input_mask, out["masked_lm_labels"], out["masked_feat"], boxes, visn,
                 is_matched, out["ans"])
+
+
+# ----------------------------------------------------------------------------------------------- the driver loop
+
+
+class InputExample(object):
+    """one example as the data set hands it over (src/pretrain/lxmert_data.py:26-38): ``visual_feats`` = (feats [O, F],
+    boxes [O, 4]), ``obj_labels`` / ``attr_labels`` = (ids [O], confidences [O]), ``label`` = {answer id: score} or None"""
+
+    def __init__(self, uid, sent, visual_feats=None, obj_labels=None, attr_labels=None, is_matched=None, label=None):
+        self.uid, self.sent, self.visual_feats = uid, sent, visual_feats
+        self.obj_labels, self.attr_labels, self.is_matched, self.label = obj_labels, attr_labels, is_matched, label
+
+
+def image_key(example):
+    """a stable non-negative integer per distinct image id: the same in every batch and every process, so that a sentence
+    pool may span batches.  The image id is ``example.img_id`` when the example carries one, else the head of the
+    reference's uid ``"<img_id>_<dset>_<idx>"`` (src/pretrain/lxmert_data.py:80-81, which returns it as a 1-tuple)."""
+    import hashlib
+    img = getattr(example, "img_id", None)
+    if img is None:
+        uid = example.uid[0] if isinstance(example.uid, (tuple, list)) else example.uid
+        parts = str(uid).rsplit("_", 2)
+        img = parts[0] if len(parts) == 3 else str(uid)
+    return int.from_bytes(hashlib.blake2b(str(img).encode("utf-8"), digest_size=8).digest(), "little") >> 1
+
+
+def collate_examples(examples, tokenizer, max_seq_length, max_labels):
+    """a list of ``InputExample`` -> the CLEAN host batch ``engine.CapturedPretrainer`` takes (dict of CPU tensors): each
+    sentence as ``[CLS] tokens[:max_seq_length - 2] [SEP]`` zero-padded with segment ids 0 (the layout of
+    src/pretrain/lxmert_pretrain.py:146-183 without its masking), the stacked visual arrays, ``pack_labels`` and
+    ``img_ids`` (``image_key``).  No masking and no swap: both happen on the device (``DeviceFeatures``)."""
+    B, T = len(examples), int(max_seq_length)
+    if B == 0 or T < 2:
+        raise ValueError("collate_examples: %d examples, max_seq_length %d" % (B, T))
+    ids = np.zeros((B, T), dtype=np.int64)
+    mask = np.zeros((B, T), dtype=np.int64)
+    for b, ex in enumerate(examples):
+        tokens = ["[CLS]"] + tokenizer.tokenize(ex.sent.strip())[:T - 2] + ["[SEP]"]
+        w = tokenizer.convert_tokens_to_ids(tokens)
+        ids[b, :len(w)], mask[b, :len(w)] = w, 1
+    stack = lambda f, dt: torch.from_numpy(np.stack([np.asarray(f(ex)) for ex in examples]).astype(dt, copy=False))
+    label_ids, label_scores = pack_labels([ex.label for ex in examples], max_labels)
+    return dict(input_ids=torch.from_numpy(ids), input_mask=torch.from_numpy(mask), segment_ids=torch.zeros((B, T), dtype=torch.int64),
+                feats=stack(lambda e: e.visual_feats[0], np.float32), boxes=stack(lambda e: e.visual_feats[1], np.float32),
+                obj_labels=stack(lambda e: e.obj_labels[0], np.int64), obj_confs=stack(lambda e: e.obj_labels[1], np.float32),
+                attr_labels=stack(lambda e: e.attr_labels[0], np.int64), attr_confs=stack(lambda e: e.attr_labels[1], np.float32),
+                is_matched=torch.tensor([int(ex.is_matched) for ex in examples], dtype=torch.int64),
+                label_ids=label_ids, label_scores=label_scores,
+                img_ids=torch.tensor([image_key(ex) for ex in examples], dtype=torch.int64))
+
+
+class LXMERT:
+    """``class LXMERT`` of src/pretrain/lxmert_pretrain.py:221-409 -- the names, signatures, return contracts and printed
+    lines are the reference's, the code is ours and runs on ``engine.CapturedPretrainer``: batches are collated CLEAN on the
+    host, swapped and masked on the device, and a step is one graph replay.
+
+    ``model``: an ``LXRTPretraining`` on the GPU (the reference builds it from the downloaded BERT weights; offline the
+    caller builds it); ``tokenizer``: anything with ``tokenize`` / ``convert_tokens_to_ids``; ``args``: the flag namespace
+    (``param.parse_args``: task flags, rates, ``epochs``, ``lr``, ``output``).  ``--taskMatched`` switches the device swap on
+    (rate 0.5): examples arrive with ``is_matched = 1`` and their own sentence.
+
+    ``train_batch`` / ``valid_batch`` keep the reference's return contract ``(loss.item(), losses numpy [1, n],
+    ans_logit)`` at ONE read per call, for callers that keep the reference's outer loop; ``forward`` is one eager pass with
+    the reference's ``(loss, losses on the host, ans_logit)``.  ``train`` /
+    ``evaluate_epoch`` read nothing per step: the losses come from the ``TrainLog`` and the answers from the ``AnswerLog``
+    once per epoch -- with ``log_every=N`` once per N steps (the logs then hold N steps instead of an epoch) -- together
+    with ``CapturedPretrainer.check()``; ``uid2ans`` is built from the answer log and the uids kept on the host in call
+    order.
+
+    Two engines, each captured at the size of the first batch it sees: ``engine`` (training; it also holds a forward-only
+    graph at the training batch size) and, when validation comes with a batch size of its own -- the reference validates at
+    512 or 2048 against ``--bs`` (src/pretrain/lxmert_pretrain.py:50-52) -- or before any training, ``valid_engine``, a
+    validation-only ``CapturedPretrainer(optim=None)`` at THAT size: validation is a replayed graph too and never takes an
+    optimiser step.  Only a ragged last batch (fewer rows than the engine's) runs EAGERLY (the same calls on the batch as it
+    is: padding it would change its mean losses); its answers land in the same log.  An answer log holds ``steps x batch
+    size`` SAMPLES of its own engine and is read back early when the next batch would not fit.
+
+    The printed per-term line names the terms that are on; the reference zips LOSSES_NAME with however many terms there
+    are, which mislabels them as soon as a task is off (:366, :402) -- with all tasks on the lines are the same."""
+
+    def __init__(self, max_seq_length, model, tokenizer, args=None, use_graph=True, log_every=None, max_labels=4,
+                 vocab_size=None, mask_id=None):
+        from .. import param
+        self.max_seq_length, self.model, self.tokenizer = max_seq_length, model, tokenizer
+        self.args = param.args if args is None else args
+        self.use_graph, self.log_every, self.max_labels = use_graph, log_every, int(max_labels)
+        vocab = getattr(tokenizer, "vocab", None)
+        vocab_size = vocab_size if vocab_size is not None else (len(vocab) if vocab is not None else model.config.vocab_size)
+        mask_id = mask_id if mask_id is not None else (vocab["[MASK]"] if vocab is not None else 103)
+        self.features = DeviceFeatures.from_args(self.args, swap=True, vocab_size=vocab_size, mask_id=mask_id, max_labels=max_labels)
+        self.device = next(model.parameters()).device
+        self.engine, self._optim = None, None  # the training engine and the optimiser it was captured with
+        self.valid_engine = None               # validation at another batch size, or before any training
+
+    # ------------------------------------------------------------------ batches and the engines
+    def _device_batch(self, examples):
+        host = collate_examples(examples, self.tokenizer, self.max_seq_length, self.max_labels)
+        return {k: v.to(self.device, non_blocking=True) for k, v in host.items()}
+
+    def _build(self, optim, batch, window):
+        from ..engine import AnswerLog, CapturedPretrainer, TrainLog
+        B = batch["input_ids"].shape[0]
+        e = CapturedPretrainer(self.model, optim, batch, self.features, clip=1.0, use_graph=self.use_graph,
+                               train_log=TrainLog(window, self.device) if optim is not None else None,
+                               valid_log=TrainLog(window, self.device),
+                               answer_log=AnswerLog(window * B, self.device, with_scores=False) if self.model.task_qa else None)
+        e.window = window
+        return e
+
+    def _train_engine(self, optim, batch, window):
+        """the captured step for ``optim``, built at the first training batch (its size is the static one) with logs of
+        ``window`` steps; rebuilt when the caller comes with another optimiser or a longer window"""
+        if self.engine is None or optim is not self._optim or window > self.engine.window:
+            self.engine, self._optim = self._build(optim, batch, window), optim
+        return self.engine
+
+    def _valid_engine(self, batch, window):
+        """the forward-only graph for batches of this size: the training engine's when the size is its own, else a
+        validation-only engine captured at this size (rebuilt for a longer window or a larger batch)"""
+        B = batch["input_ids"].shape[0]
+        e = self.engine
+        if e is not None and e.B == B and window <= e.window:
+            return e
+        e = self.valid_engine
+        if e is None or window > e.window or B > e.B:
+            self.valid_engine = e = self._build(None, batch, window)
+        return e
+
+    @staticmethod
+    def _read(out):
+        flat = torch.cat([out[0].reshape(1), out[1].reshape(-1)]).cpu()  # the ONE read of the call
+        return float(flat[0]), flat[1:].reshape(1, -1).numpy(), out[2]
+
+    def _reset_logs(self, e):
+        for log in (e.train_log, e.valid_log, e.answer_log):
+            if log is not None:
+                log.reset()
+
+    def forward(self, examples):
+        """src/pretrain/lxmert_pretrain.py:258-306 -> (loss, losses [1, n] on the host, ans_logit): ONE eager, uncaptured pass
+        in the model's current mode -- collate, swap and mask on the device, ``model(...)``.  ``loss`` carries its autograd
+        graph in training mode; a caller that goes on by hand ends the pass with ``runtime.backward(loss)`` and
+        ``clip_and_step(model, optim, 1.0, advance=True)`` (the draws of the next pass come with that advance).
+        ``train_batch`` / ``valid_batch`` do not come through here: they are one captured step each."""
+        from ..runtime import runtime_of
+        b = self._device_batch(examples)
+        from ..engine import CapturedPretrainer
+        args = self.features(*[b[k] for k in CapturedPretrainer.KEYS], runtime_of(self.model).rng, img_ids=b["img_ids"])
+        loss, losses, ans_logit = self.model(*args)
+        return loss, losses.detach().cpu(), ans_logit
+
+    def train_batch(self, optim, batch):
+        """src/pretrain/lxmert_pretrain.py:308-318 -> (loss.item(), losses numpy [1, n], ans_logit)"""
+        dev_batch = self._device_batch(batch)
+        e = self._train_engine(optim, dev_batch, 1)
+        self._reset_logs(e)  # a caller of the per-batch interface reads per batch: the logs never hold more than this step
+        return self._read(e.step(dev_batch))
+
+    def valid_batch(self, batch):
+        """src/pretrain/lxmert_pretrain.py:320-326 -> (loss.item(), losses numpy [1, n], ans_logit)"""
+        dev_batch = self._device_batch(batch)
+        e = self._valid_engine(dev_batch, 1)
+        self._reset_logs(e)
+        return self._read(e.valid_step(dev_batch))
+
+    # ------------------------------------------------------------------ epochs
+    def _sweep(self, loader, optim, kind, table, iters=-1):
+        """one pass over ``loader`` with no per-step read -> (sum of losses, {name: sum of term}, steps, uid2ans); the logs
+        are read once at its end, or once per ``log_every`` steps (earlier when the answer log could not take the next batch)"""
+        from .. import trainlog as T
+        n_batches = len(loader)
+        window = max(1, min(self.log_every or n_batches, n_batches))
+        total, terms, steps, uids, uid2ans = 0.0, {}, 0, [], {}
+        e = None
+
+        def read_back():
+            nonlocal total, steps, uids
+            e.check()
+            log = e.train_log if kind == "train" else e.valid_log
+            rec = log.read()
+            mean, named, n = T.pretrain_means(rec)
+            total, steps = total + mean * n, steps + n
+            for name, v in named:
+                terms[name] = terms.get(name, 0.0) + v * n
+            if e.answer_log is not None:
+                labels, _, _, m = e.answer_log.read()
+                assert m == len(uids), (m, len(uids))
+                id2ans = table.id2ans
+                for uid, l in zip(uids, labels.tolist()):
+                    uid2ans[uid] = id2ans(l) if callable(id2ans) else id2ans[l]
+            uids = []
+            self._reset_logs(e)
+
+        pending = 0
+        for i, batch in enumerate(loader):
+            dev_batch = self._device_batch(batch)
+            if e is None:
+                e = self._train_engine(optim, dev_batch, window) if kind == "train" else self._valid_engine(dev_batch, window)
+                self._reset_logs(e)
+            if pending and e.answer_log is not None and e.answer_log.count + len(batch) > e.answer_log.capacity:
+                read_back()
+                pending = 0
+            if kind == "train":
+                e.step(dev_batch)
+            else:
+                e.valid_step(dev_batch)
+            uids.extend(datum.uid for datum in batch)
+            pending += 1
+            if pending == window:
+                read_back()
+                pending = 0
+            if i == iters:
+                break
+        if pending:
+            read_back()
+        return total, terms, steps, uid2ans
+
+    @staticmethod
+    def _losses_line(terms, denom):
+        s = "The losses are "
+        for name in LOSSES_NAME:
+            if name in terms:
+                s += "%s: %0.4f " % (name, terms[name] / denom)
+        return s
+
+    def train(self, train_tuple, eval_tuple):
+        """src/pretrain/lxmert_pretrain.py:328-379; ``*_tuple`` = (dataset, loader, evaluator) or anything with those
+        attributes"""
+        from ..lxrt.optimization import BertAdam
+        args = self.args
+        dataset, train_ld, evaluator = _tuple(train_tuple)
+        batch_per_epoch = len(train_ld)
+        t_total = int(batch_per_epoch * args.epochs)
+        warmup_ratio = 0.05
+        warmup_iters = int(t_total * warmup_ratio)
+        print("Batch per epoch: %d" % batch_per_epoch)
+        print("Total Iters: %d" % t_total)
+        print("Warm up Iters: %d" % warmup_iters)
+        optim = BertAdam(list(self.model.parameters()), lr=args.lr, warmup=warmup_ratio, t_total=t_total)
+        best_eval_loss = 9595.
+        for epoch in range(args.epochs):
+            self.model.train()
+            total_loss, terms, _, uid2ans = self._sweep(train_ld, optim, "train", dataset.answer_table)
+            print("The training loss for Epoch %d is %0.4f" % (epoch, total_loss / batch_per_epoch))
+            print(self._losses_line(terms, batch_per_epoch))
+            if self.model.task_qa:
+                evaluator.evaluate(uid2ans, pprint=True)
+            avg_eval_loss = self.evaluate_epoch(eval_tuple, iters=-1)
+            if avg_eval_loss < best_eval_loss:
+                best_eval_loss = avg_eval_loss
+                self.save("BEST_EVAL_LOSS")
+            self.save("Epoch%02d" % (epoch + 1))
+
+    def evaluate_epoch(self, eval_tuple, iters=-1):
+        """src/pretrain/lxmert_pretrain.py:381-409 (the answers are decoded with the evaluated data set's own table)"""
+        dataset, eval_ld, evaluator = _tuple(eval_tuple)
+        was_training = self.model.training
+        self.model.eval()
+        total_loss, terms, _, uid2ans = self._sweep(eval_ld, None, "valid", dataset.answer_table, iters)
+        self.model.train(was_training)
+        print("The valid loss is %0.4f" % (total_loss / len(eval_ld)))
+        print(self._losses_line(terms, len(eval_ld)))
+        if self.model.task_qa:
+            evaluator.evaluate(uid2ans, pprint=True)
+        return total_loss / len(eval_ld)
+
+    # ------------------------------------------------------------------ snapshots, the reference's file names
+    def save(self, name):
+        os.makedirs(self.args.output, exist_ok=True)
+        torch.save(self.model.state_dict(), os.path.join(self.args.output, "%s_LXRT.pth" % name))
+
+    def load(self, path):
+        print("Load BERT extractor from %s" % path)
+        self.model.load_state_dict(torch.load("%s_LXRT.pth" % path, map_location="cpu", weights_only=True))
+
+    def load_lxmert(self, path):
+        """every weight of the snapshot but the answer head (src/pretrain/lxmert_pretrain.py:420-448); a ``module.``
+        prefix (a snapshot of a DataParallel model) is dropped, names without it are kept"""
+        print("Load LXMERT model from %s" % path)
+        sd = torch.load("%s_LXRT.pth" % path, map_location="cpu", weights_only=True)
+        sd = {(k[len("module."):] if k.startswith("module.") else k): v for k, v in sd.items() if "answer" not in k}
+        load_keys, model_keys = set(sd), set(self.model.state_dict())
+        print()
+        print("Keys in loaded but not in model:")
+        for key in sorted(load_keys.difference(model_keys)):
+            print(key)
+        print()
+        print("Keys in model but not in loaded:")
+        for key in sorted(model_keys.difference(load_keys)):
+            print(key)
+        print()
+        self.model.load_state_dict(sd, strict=False)
+
+
+def _tuple(t):
+    """(dataset, loader, evaluator) of a DataTuple-like object or a plain 3-tuple"""
+    if hasattr(t, "dataset"):
+        return t.dataset, t.loader, t.evaluator
+    return t[0], t[1], t[2]

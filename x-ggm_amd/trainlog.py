@@ -8,6 +8,14 @@ KINDS = 4  # XGGM_TRAINLOG_KINDS
 LOSS, BCE, KL, DSM, GRAD_NORM, LR_SCALE = range(6)  # columns of a pass record; 6 and 7 are spare
 PLAIN, REL, NODE = 0, 1, 2                          # kinds
 KIND_OF = {"plain": PLAIN, "rel": REL, "node": NODE}
+# the spare kind: one record per pre-training step (``engine.CapturedPretrainer``).  Column 0 is LOSS as above; columns 1-6
+# are the reference's six terms in the order of its LOSSES_NAME (src/pretrain/lxmert_pretrain.py:218), each at a FIXED
+# column -- a task that is off leaves its column absent -- and column 7 the pre-clip gradient norm (absent in a validation
+# log, which has no backward)
+PRETRAIN = 3
+LOSSES_NAME = ('Mask_LM', 'Matched', 'Obj', 'Attr', 'Feat', 'QA')
+PT_MASK_LM, PT_MATCHED, PT_OBJ, PT_ATTR, PT_FEAT, PT_QA = range(1, 7)
+PT_GRAD_NORM = 7
 HEADER = 2 + KINDS + KINDS * COLS  # int64 words in front of the ring: cursor, first_bad, counts, sums (fp64 bits)
 
 
@@ -51,3 +59,21 @@ def decode_packed(w, capacity):
                 present=((mask[:, None] >> torch.arange(COLS)) & 1).bool(), cursor=w[0].clone(),
                 sums=w[2 + KINDS:HEADER].view(torch.float64).view(KINDS, COLS).clone(), counts=w[2:2 + KINDS].clone(),
                 first_bad=w[1].clone())
+
+
+def pretrain_means(rec):
+    """what the reference prints per epoch (src/pretrain/lxmert_pretrain.py:363-368, :400-404) from ONE decoded read-back
+    ``rec`` (``decode_packed`` / ``TrainLog.read``): -> (mean loss, [(name, mean term)] for the terms that were logged, in
+    the order of LOSSES_NAME, number of steps).  The means are the log's fp64 running sums of the PRETRAIN records since its
+    reset over their count, so they cover every step even when the ring has wrapped; a term counts as logged when the
+    newest retained PRETRAIN record holds its column (the set of tasks does not change within a run)."""
+    n = int(rec["counts"][PRETRAIN])
+    if n == 0:
+        return 0.0, [], 0
+    rows = (rec["kinds"] == PRETRAIN).nonzero().reshape(-1)
+    if rows.numel() == 0:
+        raise RuntimeError("pretrain_means: %d pre-training steps were logged but the ring retains none of them" % n)
+    present = rec["present"][int(rows[-1])]
+    sums = rec["sums"][PRETRAIN]
+    terms = [(name, float(sums[c]) / n) for name, c in zip(LOSSES_NAME, range(PT_MASK_LM, PT_QA + 1)) if bool(present[c])]
+    return float(sums[LOSS]) / n, terms, n
