@@ -868,6 +868,65 @@ typedef struct xggm_pretrain_swap_args {
 } xggm_pretrain_swap_args;
 int xggm_pretrain_swap(const xggm_pretrain_swap_args* args, xggm_stream_t stream);
 
+/* xggm_batch_gather: a batch assembled from a split that is RESIDENT on the device, in ONE launch.  It replaces what the
+ * reference does on the host every step: collate B items (src/vqa/vqacpv2_data.py:98-127: features, normalised boxes, the
+ * soft-score target row, the adjacency), tokenise B questions and copy four tensors to the device
+ * (src/vqa/vqacpv2.py:164-171).  Output row b (0 <= b < B) is built from sample s = order[start + b]; r = q_row[s] is its
+ * image, stored once however many samples refer to it.
+ * Tables (device, only read):
+ *   feats [n_img, N, F] bf16 bit patterns, or fp32 when feats_f32;  boxes [n_img, N, 4] f32;  adj [n_img, N, N] f32 or NULL;
+ *   q_row [n_q] int32;  q_ids [n_q, T] int32 (zero behind the sentence);  q_len [n_q] int32 (tokens, [CLS] / [SEP] included);
+ *   q_label [n_q, K] int32 (-1: unused slot) and q_score [n_q, K] f32;  q_bias_index [n_q] int64 or NULL.
+ * Selection: order [n] int64 on the device; start and B are host values.
+ * Outputs (device):
+ *   out_feats   row b at out_feats + b * out_feats_stride ELEMENTS, bf16 or fp32 (out_f32) <- feats[r].  Same type: the bits.
+ *               fp32 -> bf16: the bits of torch.Tensor.to(torch.bfloat16) (round to nearest even, the largest finite values
+ *               round up to inf, NaN -> 0x7FC0; nothing is flushed).  bf16 -> fp32: bits << 16.
+ *   out_boxes   [B, N, 4] f32 <- boxes[r];  out_adj [B, N, N] f32 or NULL (not written) <- adj[r];
+ *   input_ids, input_mask, segment_ids  int64 [B, T]: q_ids[s], (t < q_len[s]), 0;
+ *   target      f32 row b at target + b * target_stride elements, or NULL (not written): A zeros, then
+ *               target[q_label[s, k]] = q_score[s, k] for every k with q_label[s, k] >= 0.  The labels of a sample are
+ *               distinct; the zero-fill and the scatter of a row run in one workgroup with a barrier between them;
+ *   bias_index  int64 [B] or NULL <- q_bias_index[s];  sample int64 [B] or NULL <- s.
+ * Feature rows move as 16-byte vectors (F % 8 == 0; table base, output base 16-byte aligned and the output row stride a
+ * multiple of 8 elements), a box is one 16-byte vector.  Rows that are no 16-byte multiples -- target (A = 2274, 29), adj
+ * with odd N -- move element by element inside their own bounds: no vector straddles a row end.  Nothing is written outside
+ * rows 0 .. B - 1 of an output, nor between two rows where a stride exceeds the row.  No atomics: every output element
+ * has one writer.  One launch; nothing is allocated, copied or synchronised, so the call can be captured in a graph (order
+ * is read at run time: a replay follows what order holds then).
+ * The kernel TRUSTS order[i] in [0, n_q), q_row in [0, n_img), q_label in [-1, A) and q_len in [0, T]: the caller validates
+ * them once, when the tables are uploaded.
+ * Refused before any launch: a null struct; a null or misaligned pointer (feats, boxes tables and outputs: 16 bytes; the
+ * other fields: their element size; an optional field may be NULL, but an output whose table is NULL is refused);
+ * B < 1 (or > 65535); start < 0 or start + B > n; T, K, A, N or F < 1; F % 8 != 0; a row stride below its row. */
+typedef struct xggm_batch_gather_args {
+    const void* feats;             /* [n_img, N, F] bf16 bits or fp32 */
+    const float* boxes;            /* [n_img, N, 4] */
+    const float* adj;              /* [n_img, N, N] or NULL */
+    const int32_t* q_row;          /* [n_q] */
+    const int32_t* q_ids;          /* [n_q, T] */
+    const int32_t* q_len;          /* [n_q] */
+    const int32_t* q_label;        /* [n_q, K] or NULL (no target) */
+    const float* q_score;          /* [n_q, K] or NULL (no target) */
+    const int64_t* q_bias_index;   /* [n_q] or NULL */
+    const int64_t* order;          /* [n] */
+    int64_t n, start;
+    void* out_feats;
+    int64_t out_feats_stride;      /* elements between two rows */
+    float* out_boxes;              /* [B, N, 4] */
+    float* out_adj;                /* [B, N, N] or NULL */
+    int64_t* input_ids;            /* [B, T] */
+    int64_t* input_mask;           /* [B, T] */
+    int64_t* segment_ids;          /* [B, T] */
+    float* target;                 /* rows of A or NULL */
+    int64_t target_stride;         /* elements between two rows */
+    int64_t* bias_index;           /* [B] or NULL */
+    int64_t* sample;               /* [B] or NULL */
+    int B, T, K, A, N, F;
+    int feats_f32, out_f32;
+} xggm_batch_gather_args;
+int xggm_batch_gather(const xggm_batch_gather_args* args, xggm_stream_t stream);
+
 /* ---- preprocessing that feeds the path ----------------------------------------------------
  * adj_true of every sample: data/preprocess/vqa/compute_adjacency.py:38-45 (compute_cosin_sim_v2) + :90.
  *   c[i][j] = cos(cls[i], attr[j]) for j >= i, 0 below the diagonal  (torch.cosine_similarity, eps 1e-6: each

@@ -486,6 +486,22 @@ class CapturedTrainer:
         self.static_flat.copy_(it.flat, non_blocking=True)
         it.mark_copied()
 
+    def load_resident(self, store, start):
+        """hand over rows ``start .. start + B`` of the epoch order of ``store`` (tools.resident.ResidentDataset): ONE
+        gather launch out of the device-resident tables into the static inputs, eagerly and in stream order between the
+        replays, where ``load_packed`` queues its copy -- nothing crosses PCIe and no graph is captured again.  An attached
+        debias loss that selects its prior by ``bias_index`` is fed from the store's; one that reads the dense ``bias`` of a
+        batch cannot be (the store holds no [B, A] bias): hand such batches over with ``load_batch``."""
+        s = self.static
+        if getattr(getattr(self.model, "debias_loss", None), "needs_bias", False):
+            if "bias_index" not in s:
+                raise ValueError("CapturedTrainer: a resident store carries no dense bias for the attached debias loss; "
+                                 "build the trainer on a batch with bias_index (loss.set_bias_table) or use load_batch")
+            if "q_bias_index" not in store.tables:
+                raise ValueError("CapturedTrainer: the attached debias loss reads bias_index, the store was built without one")
+        skip = ("sample",) if "q_bias_index" in store.tables else ("sample", "bias_index")
+        store.fill({k: v for k, v in s.items() if k not in skip}, start, s["feats"].shape[0])
+
     def train_score(self):
         """mean soft score of the plain pass's answers since the log's last ``reset()`` (the reference's per-epoch train
         score, src/vqa/vqacpv2.py:285, as a fraction): one read-back"""
@@ -666,6 +682,20 @@ class CapturedPredictor:
             batcher.record_copy()  # the pinned buffer is not rewritten before this copy has read it
         s["feats"][:b].copy_(feats, non_blocking=True)
         s["boxes"][:b].copy_(boxes, non_blocking=True)
+        return self._queue(b)
+
+    def push_resident(self, store, start, b):
+        """``push`` for rows ``start .. start + b`` of the order of ``store`` (tools.resident.ResidentDataset): ONE gather
+        launch out of the device-resident tables into the static buffers (fp32 features: a bf16 table is widened on the
+        way) instead of the host-to-device copies; the row count travels as in ``push``."""
+        if not 1 <= b <= self.B:
+            raise ValueError("batch of %d outside the captured batch size %d" % (b, self.B))
+        s = self.static
+        store.fill(dict(feats=s["feats"], boxes=s["boxes"], input_ids=s["ids"][0], input_mask=s["ids"][1],
+                        segment_ids=s["ids"][2]), start, b)
+        return self._queue(b)
+
+    def _queue(self, b):
         if self.log is not None:
             self.log.note(b)
             self.log.set_rows(b)

@@ -2372,6 +2372,108 @@ def pretrain_swap(ids, mask, img, rate=0.5, matched_in=None, pool=None, rng=None
     return out
 
 
+# ----------------------------------------------------------------------------- resident data set
+class BatchGatherArgs(_ct.Structure):
+    """mirror of ``xggm_batch_gather_args`` (include/xggm.h)"""
+    _fields_ = [("feats", _ct.c_void_p), ("boxes", _ct.c_void_p), ("adj", _ct.c_void_p), ("q_row", _ct.c_void_p),
+                ("q_ids", _ct.c_void_p), ("q_len", _ct.c_void_p), ("q_label", _ct.c_void_p), ("q_score", _ct.c_void_p),
+                ("q_bias_index", _ct.c_void_p), ("order", _ct.c_void_p), ("n", _ct.c_int64), ("start", _ct.c_int64),
+                ("out_feats", _ct.c_void_p), ("out_feats_stride", _ct.c_int64), ("out_boxes", _ct.c_void_p),
+                ("out_adj", _ct.c_void_p), ("input_ids", _ct.c_void_p), ("input_mask", _ct.c_void_p),
+                ("segment_ids", _ct.c_void_p), ("target", _ct.c_void_p), ("target_stride", _ct.c_int64),
+                ("bias_index", _ct.c_void_p), ("sample", _ct.c_void_p), ("B", _ct.c_int), ("T", _ct.c_int), ("K", _ct.c_int),
+                ("A", _ct.c_int), ("N", _ct.c_int), ("F", _ct.c_int), ("feats_f32", _ct.c_int), ("out_f32", _ct.c_int)]
+
+
+def _rows_of(t, B, row, name):
+    """``t``: at least B rows of shape ``row`` whose insides are contiguous (the row stride is free) -> row stride"""
+    if t.dim() != 1 + len(row) or tuple(t.shape[1:]) != tuple(row) or t.shape[0] < B:
+        raise ValueError("batch_gather: %s is %s, at least [%d, %s] expected" % (name, tuple(t.shape), B, ", ".join(map(str, row))))
+    if not t[0].is_contiguous():
+        raise RuntimeError("xggm_amd: the rows of %s must be contiguous" % name)
+    return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t[0].numel())
+
+
+def batch_gather(tables, order, start, B, out):
+    """rows ``order[start : start + B]`` of a device-resident split into the batch buffers ``out``, one launch; contract:
+    xggm_batch_gather in xggm.h.  ``tables``: feats [n_img, N, F] bf16 / fp32, boxes [n_img, N, 4], adj [n_img, N, N] or None,
+    q_row [n_q] int32, q_ids [n_q, T] int32, q_len [n_q] int32, q_label [n_q, K] int32, q_score [n_q, K] fp32, q_bias_index
+    [n_q] int64 or None.  ``order``: [n] int64.  ``out``: feats (bf16 / fp32; the row stride is free), boxes, input_ids,
+    input_mask, segment_ids and any of adj_true, target (row stride free), bias_index, sample; each with at least B rows,
+    rows past B are not touched.  The indices inside the tables are trusted (``tools.resident.ResidentDataset`` validates
+    them once at upload); every shape is checked here."""
+    tb, dev = tables, order.device
+    for k in ("feats", "boxes", "q_row", "q_ids", "q_len", "q_label", "q_score"):
+        _c(tb[k], None, "table " + k)
+    _c(order, torch.int64, "order")
+    feats, boxes, adj, bias = tb["feats"], tb["boxes"], tb.get("adj"), tb.get("q_bias_index")
+    if feats.dtype not in (BF16, F32) or feats.dim() != 3:
+        raise TypeError("batch_gather: feature table %s %s, [n_img, N, F] bfloat16 or float32 expected" % (tuple(feats.shape), feats.dtype))
+    n_img, N, F = feats.shape
+    _c(boxes, F32, "table boxes"), _c(tb["q_row"], torch.int32, "q_row"), _c(tb["q_ids"], torch.int32, "q_ids")
+    _c(tb["q_len"], torch.int32, "q_len"), _c(tb["q_label"], torch.int32, "q_label"), _c(tb["q_score"], F32, "q_score")
+    n_q = tb["q_row"].numel()
+    if tb["q_ids"].dim() != 2 or tb["q_label"].dim() != 2:
+        raise ValueError("batch_gather: q_ids [n_q, T] and q_label [n_q, K] expected")
+    T, K = tb["q_ids"].shape[1], tb["q_label"].shape[1]
+    if (tuple(boxes.shape) != (n_img, N, 4) or tb["q_row"].dim() != 1 or tb["q_ids"].shape[0] != n_q or tuple(tb["q_len"].shape) != (n_q,)
+            or tb["q_label"].shape[0] != n_q or tuple(tb["q_score"].shape) != (n_q, K)):
+        raise ValueError("batch_gather: the tables do not fit n_img=%d N=%d n_q=%d T=%d K=%d" % (n_img, N, n_q, T, K))
+    if adj is not None and (_c(adj, F32, "table adj").shape != (n_img, N, N)):
+        raise ValueError("batch_gather: adjacency table %s, [%d, %d, %d] expected" % (tuple(adj.shape), n_img, N, N))
+    if bias is not None and tuple(_c(bias, torch.int64, "q_bias_index").shape) != (n_q,):
+        raise ValueError("batch_gather: q_bias_index %s, [%d] expected" % (tuple(bias.shape), n_q))
+    if min(n_img, n_q, N, F, T, K) < 1:
+        raise ValueError("batch_gather: empty tables")
+    if F % 8:
+        raise ValueError("batch_gather: F=%d is no multiple of 8 (feature rows move 16 bytes per lane)" % F)
+    start, B, n = int(start), int(B), order.numel()
+    if order.dim() != 1 or B < 1 or start < 0 or start + B > n:
+        raise ValueError("batch_gather: rows %d .. %d of an order of %d" % (start, start + B, n))
+    unknown = set(out) - {"feats", "boxes", "adj_true", "input_ids", "input_mask", "segment_ids", "target", "bias_index", "sample"}
+    if unknown:
+        raise ValueError("batch_gather: unknown outputs %s" % sorted(unknown))
+    a = BatchGatherArgs()
+    of = _chk(out["feats"], None, "out feats")
+    if of.dtype not in (BF16, F32):
+        raise TypeError("batch_gather: out feats %s, bfloat16 or float32 expected" % of.dtype)
+    a.out_feats_stride = _rows_of(of, B, (N, F), "out feats")
+    _rows_of(_c(out["boxes"], F32, "out boxes"), B, (N, 4), "out boxes")
+    for k in ("input_ids", "input_mask", "segment_ids"):
+        _rows_of(_c(out[k], torch.int64, "out " + k), B, (T,), "out " + k)
+    oa, tg, ob, sm = out.get("adj_true"), out.get("target"), out.get("bias_index"), out.get("sample")
+    if oa is not None:
+        if adj is None:
+            raise ValueError("batch_gather: the tables hold no adjacency for out adj_true")
+        _rows_of(_c(oa, F32, "out adj_true"), B, (N, N), "out adj_true")
+    if tg is not None:
+        if _chk(tg, F32, "out target").dim() != 2:
+            raise ValueError("batch_gather: out target %s, [B, A] expected" % (tuple(tg.shape),))
+        a.A = tg.shape[1]
+        a.target_stride = _rows_of(tg, B, (a.A,), "out target")
+    else:
+        a.A, a.target_stride = 1, 1
+    if ob is not None:
+        if bias is None:
+            raise ValueError("batch_gather: the tables hold no q_bias_index for out bias_index")
+        _rows_of(_c(ob, torch.int64, "out bias_index"), B, (), "out bias_index")
+    if sm is not None:
+        _rows_of(_c(sm, torch.int64, "out sample"), B, (), "out sample")
+    for t in list(tb.values()) + list(out.values()):
+        if t is not None and t.device != dev:
+            raise RuntimeError("batch_gather: all operands must live on one device")
+    a.feats, a.boxes, a.adj, a.q_row, a.q_ids, a.q_len = ptr(feats), ptr(boxes), ptr(adj), ptr(tb["q_row"]), ptr(tb["q_ids"]), ptr(tb["q_len"])
+    a.q_label, a.q_score, a.q_bias_index = ptr(tb["q_label"]), ptr(tb["q_score"]), ptr(bias)
+    a.order, a.n, a.start = ptr(order), n, start
+    a.out_feats, a.out_boxes, a.out_adj = ptr(of), ptr(out["boxes"]), ptr(oa)
+    a.input_ids, a.input_mask, a.segment_ids = ptr(out["input_ids"]), ptr(out["input_mask"]), ptr(out["segment_ids"])
+    a.target, a.bias_index, a.sample = ptr(tg), ptr(ob), ptr(sm)
+    a.B, a.T, a.K, a.N, a.F = B, T, K, N, F
+    a.feats_f32, a.out_f32 = int(feats.dtype == F32), int(of.dtype == F32)
+    call("xggm_batch_gather", _ct.addressof(a), stream())
+    return out
+
+
 # ----------------------------------------------------------------------------- graph attention
 def gat_att_fwd(s, adj, alpha):
     _c(s, F32, "s"), _c(adj, F32, "adj")

@@ -1,0 +1,224 @@
+"""Device-resident data set: a whole split uploaded to HBM once, a batch assembled there by ONE launch.
+
+``DataLoaderX`` is as good as a host loader gets (memory-mapped bf16 shards, pinned slots, one stream-ordered copy per
+batch), but every visit of a sample still carries its 147 456 B of features across PCIe -- questions that share an image
+ship the image again -- and a producer thread tokenises and copies rows beside a loop whose step takes milliseconds.
+The features of a split fit in HBM many times over (120 000 images: 17.7 GB of bf16), so ``ResidentDataset`` stores
+
+    feats [n_img, N, F]   the shard's own storage type (bf16, or fp32 for a ``float32`` parity shard)
+    boxes [n_img, N, 4], adj [n_img, N, N]
+    q_row [n_q] int32     the image row of every sample: an image is stored ONCE however many questions refer to it
+    q_ids [n_q, T] int32, q_len [n_q] int32       what ``SentenceBatcher`` would produce for the question
+    q_label, q_score [n_q, K]                     the (label, score) pairs ``fill_target`` would write, -1 = unused slot
+    q_bias_index [n_q] int64                      optional: the prior-table row of a debias loss
+
+and ``fill`` gathers ``order[start : start + B]`` into the trainer's static buffers with ``ops.batch_gather``: no producer
+thread, no pinned ring, no host-to-device copy, no host work per step beyond the launch.  ``host_batch`` restates the
+gather in numpy from the same tables -- the reference the kernel is tested against on the CPU, NOT a fallback: ``fill``
+refuses CPU tensors like every other op.  Pre-training batches are not covered.
+"""
+import numpy as np
+import torch
+
+from .shards import _bf16_bits
+
+FIELDS = ("feats", "boxes", "adj_true", "input_ids", "input_mask", "segment_ids", "target", "bias_index", "sample")
+
+
+class _Slots:
+    """what ``fill_target`` assigns, recorded instead of written: {label: score}, a repeated label keeps its LAST score (as
+    the sequential assignment into a target row does) at its first position"""
+
+    def __init__(self):
+        self.d = {}
+
+    def __setitem__(self, label, score):
+        self.d[int(label)] = np.float32(score)
+
+
+def sample_tables(ts, batcher, A=None):
+    """the per-sample host tables of ``ts`` (VQATorchDataset / GQATorchDataset: ``rows``, ``data``, ``raw_dataset``,
+    ``fill_target``) -> dict of numpy arrays q_row, q_ids, q_len, q_label, q_score.  Everything the kernel will trust is
+    checked here, once: image rows fit int32, token ids fit their row, labels lie in [0, A)."""
+    ds = ts.raw_dataset
+    A = int(A if A is not None else ds.num_answers)
+    n_q, T = len(ts.data), int(batcher.T)
+    rows = np.asarray(ts.rows, dtype=np.int64)
+    if n_q < 1:
+        raise ValueError("ResidentDataset: the data set holds no sample")
+    if rows.shape != (n_q,) or rows.min() < 0 or rows.max() >= len(ts.shard):
+        raise ValueError("ResidentDataset: image rows outside the shard's %d images" % len(ts.shard))
+    q_ids, q_len, pairs = np.zeros((n_q, T), dtype=np.int32), np.zeros(n_q, dtype=np.int32), []
+    for i, d in enumerate(ts.data):
+        ids = batcher.ids_of(d[ds.sent_key])
+        if len(ids) > T:
+            raise ValueError("ResidentDataset: question %r has %d tokens, max_seq_length is %d" % (d["question_id"], len(ids), T))
+        q_ids[i, :len(ids)] = ids
+        q_len[i] = len(ids)
+        s = _Slots()
+        if "label" in d:  # test splits carry none: all slots stay unused, the target row zero
+            ts.fill_target(d, s)
+        for l in s.d:
+            if not 0 <= l < A:
+                raise ValueError("ResidentDataset: question %r has label %d outside the answer table [0, %d)"
+                                 % (d["question_id"], l, A))
+        pairs.append(s.d)
+    K = max(1, max(len(p) for p in pairs))
+    q_label, q_score = np.full((n_q, K), -1, dtype=np.int32), np.zeros((n_q, K), dtype=np.float32)
+    for i, p in enumerate(pairs):
+        if p:
+            q_label[i, :len(p)] = list(p.keys())
+            q_score[i, :len(p)] = list(p.values())
+    return dict(q_row=rows.astype(np.int32), q_ids=q_ids, q_len=q_len, q_label=q_label, q_score=q_score)
+
+
+def gather_host(tables, indices, A, out_f32=False):
+    """``ops.batch_gather`` restated in numpy: the batch of the samples ``indices`` out of host ``tables`` (numpy arrays
+    under the kernel's names; ``feats`` uint16 bf16 bit patterns or float32) -> dict of CPU tensors under the trainer's
+    names plus ``sample``.  Same-type features are copied, fp32 -> bf16 rounds as ``torch.Tensor.to(torch.bfloat16)``,
+    bf16 -> fp32 is ``bits << 16``."""
+    idx = np.asarray(indices, dtype=np.int64).reshape(-1)
+    rows = tables["q_row"][idx].astype(np.int64)
+    f = np.ascontiguousarray(tables["feats"][rows])
+    if f.dtype == np.float32:
+        feats = torch.from_numpy(f.copy()) if out_f32 else torch.from_numpy(_bf16_bits(f).view(np.int16).copy()).view(torch.bfloat16)
+    elif f.dtype == np.uint16:
+        feats = (torch.from_numpy((f.astype(np.uint32) << 16).view(np.float32)) if out_f32
+                 else torch.from_numpy(f.view(np.int16).copy()).view(torch.bfloat16))
+    else:
+        raise TypeError("gather_host: feats are %s, uint16 (bf16 bits) or float32 expected" % f.dtype)
+    B, T = len(idx), tables["q_ids"].shape[1]
+    out = dict(feats=feats, boxes=torch.from_numpy(np.array(tables["boxes"][rows], dtype=np.float32)))
+    if tables.get("adj") is not None:
+        out["adj_true"] = torch.from_numpy(np.array(tables["adj"][rows], dtype=np.float32))
+    out["input_ids"] = torch.from_numpy(tables["q_ids"][idx].astype(np.int64))
+    out["input_mask"] = torch.from_numpy((np.arange(T)[None, :] < tables["q_len"][idx][:, None]).astype(np.int64))
+    out["segment_ids"] = torch.zeros((B, T), dtype=torch.int64)
+    tgt = np.zeros((B, int(A)), dtype=np.float32)
+    for b, s in enumerate(idx):
+        for l, v in zip(tables["q_label"][s], tables["q_score"][s]):
+            if l >= 0:
+                tgt[b, l] = v
+    out["target"] = torch.from_numpy(tgt)
+    if tables.get("q_bias_index") is not None:
+        out["bias_index"] = torch.from_numpy(tables["q_bias_index"][idx].astype(np.int64))
+    out["sample"] = torch.from_numpy(idx.copy())
+    return out
+
+
+class ResidentDataset:
+    def __init__(self, ts, batcher, device, bias_index=None, chunk_bytes=64 << 20, max_bytes=None, batch_size=None):
+        """``ts``: a ``VQATorchDataset`` / ``GQATorchDataset`` (anything with ``.shard``, ``.rows``, ``.data``,
+        ``.raw_dataset`` and ``fill_target``); ``batcher``: the model's ``SentenceBatcher``; ``bias_index``: [n_q] ints, the
+        prior-table row of every sample for a debias loss, or None.  The shard's arrays are uploaded once through ONE
+        pinned staging buffer of ``chunk_bytes``.  ``max_bytes``: refuse (ValueError naming the total) a split whose tables
+        exceed it; default: the device's free memory minus 2 GiB.  ``batch_size``: default of ``order`` for ``world > 1``."""
+        self.ts, self.batcher, self.device = ts, batcher, torch.device(device)
+        self.batch_size = batch_size
+        sh = ts.shard
+        self.N, self.F, self.T, self.A = int(sh.N), int(sh.F), int(batcher.T), int(ts.raw_dataset.num_answers)
+        if self.F % 8:
+            raise ValueError("ResidentDataset: feat_dim %d is no multiple of 8 (feature rows move 16 bytes per lane)" % self.F)
+        host = sample_tables(ts, batcher, self.A)
+        if bias_index is not None:
+            bi = np.asarray(bias_index, dtype=np.int64).reshape(-1)
+            if bi.shape[0] != len(ts.data):
+                raise ValueError("ResidentDataset: bias_index has %d entries for %d samples" % (bi.shape[0], len(ts.data)))
+            host["q_bias_index"] = bi
+        # the shard's own arrays, as mapped: nothing is read before the upload (or host_batch) touches the rows
+        host["feats"] = sh.feats_bits if sh.feats_f is None else sh.feats_f
+        host["boxes"] = sh.boxes
+        host["adj"] = sh.adj
+        self.host = host
+        self.n, self.K = len(ts.data), host["q_label"].shape[1]
+        self.nbytes = sum(int(v.nbytes) for v in host.values() if v is not None)
+        cuda = self.device.type == "cuda"
+        if max_bytes is None and cuda:
+            max_bytes = torch.cuda.mem_get_info(self.device)[0] - (2 << 30)
+        if max_bytes is not None and self.nbytes > max_bytes:
+            raise ValueError("ResidentDataset: the split needs %d bytes on the device, the limit is %d" % (self.nbytes, max_bytes))
+        self._stage = None
+        self.tables = {k: self._upload(k, v, int(chunk_bytes)) for k, v in host.items() if v is not None}
+        self._stage = None  # the pinned staging buffer is only needed for the upload
+        # ONE device buffer for every epoch's order: a captured ``fill`` keeps reading the same address
+        self._order_buf = torch.zeros(self.n, dtype=torch.int64, device=self.device)
+        self._order, self._order_host = None, None
+        self.order(0, shuffle=False, drop_last=False)  # identity until the loop asks for an epoch
+
+    def __len__(self):
+        return self.n
+
+    def _upload(self, name, arr, chunk_bytes):
+        bf16 = name == "feats" and arr.dtype == np.uint16
+        dt = torch.bfloat16 if bf16 else torch.from_numpy(np.empty(0, dtype=arr.dtype)).dtype
+        dst = torch.empty(arr.shape, dtype=dt, device=self.device)
+        flat = dst.view(-1).view(torch.int16) if bf16 else dst.view(-1)
+        src = np.asarray(arr).reshape(-1)
+        if bf16:
+            src = src.view(np.int16)
+        if self.device.type != "cuda":
+            flat.numpy()[:] = src
+            return dst
+        if self._stage is None:
+            self._stage = torch.empty(max(chunk_bytes, 4096), dtype=torch.uint8).pin_memory()
+        per = self._stage.numel() // src.itemsize
+        stage = self._stage[:per * src.itemsize].view(flat.dtype)
+        for o in range(0, src.shape[0], per):
+            m = min(per, src.shape[0] - o)
+            stage.numpy()[:m] = src[o:o + m]
+            flat[o:o + m].copy_(stage[:m], non_blocking=True)
+            torch.cuda.current_stream(self.device).synchronize()  # the ONE staging buffer is rewritten next
+        return dst
+
+    # ------------------------------------------------------------------ epoch order
+    def order(self, epoch, shuffle=True, seed=0, rank=0, world=1, drop_last=True, batch_size=None):
+        """this rank's sample indices of epoch ``epoch`` (host int64 array), uploaded as the order ``fill`` reads.  The
+        permutation is the one ``DataLoaderX._batches`` draws for its epoch ``epoch`` with the same ``seed``; with
+        ``world > 1`` step s covers ``perm[s B world : (s + 1) B world]`` and rank r takes the r-th B of it (``batch_size``
+        here or in the constructor).  ``drop_last``: only whole (global) batches."""
+        n = self.n
+        perm = np.random.default_rng([seed, epoch]).permutation(n) if shuffle else np.arange(n)
+        B = batch_size if batch_size is not None else self.batch_size
+        if world > 1:
+            if B is None:
+                raise ValueError("ResidentDataset.order: world > 1 needs the batch size")
+            if not 0 <= rank < world:
+                raise ValueError("ResidentDataset.order: rank %d of %d" % (rank, world))
+            steps = n // (B * world)  # a ragged global step cannot be split into equal ranks: always dropped
+            perm = perm[:steps * B * world].reshape(steps, world, B)[:, rank].reshape(-1)
+        elif drop_last and B is not None:
+            perm = perm[:n // B * B]
+        perm = np.ascontiguousarray(perm, dtype=np.int64)
+        if len(perm) == 0:
+            raise ValueError("ResidentDataset.order: no whole batch of %s in %d samples" % (B, n))
+        self._order_host = perm
+        self._order = self._order_buf[:len(perm)]
+        self._order.copy_(torch.from_numpy(perm))
+        return perm
+
+    # ------------------------------------------------------------------ batches
+    def fill(self, out, start, B):
+        """rows ``order[start : start + B]`` into the device tensors ``out`` (the trainer's names: feats, boxes, adj_true,
+        input_ids, input_mask, segment_ids, target and optionally bias_index, sample; other keys are left alone), ONE
+        launch on the current stream."""
+        for k, want in (("feats", (self.N, self.F)), ("input_ids", (self.T,)), ("target", (self.A,))):
+            if k in out and tuple(out[k].shape[1:]) != want:
+                raise ValueError("ResidentDataset.fill: out[%r] has rows of %s, the store holds N=%d F=%d T=%d A=%d"
+                                 % (k, tuple(out[k].shape[1:]), self.N, self.F, self.T, self.A))
+        sel = {k: out[k] for k in FIELDS if k in out}
+        if "adj_true" in sel and "adj" not in self.tables:
+            raise ValueError("ResidentDataset.fill: the shard holds no adjacency")
+        if "bias_index" in sel and "q_bias_index" not in self.tables:
+            raise ValueError("ResidentDataset.fill: the store was built without bias_index")
+        from .. import ops
+        ops.batch_gather(self.tables, self._order, start, B, sel)
+        return out
+
+    def host_batch(self, indices, out_f32=False):
+        """``fill`` restated in numpy from the same tables, for the SAMPLE indices given (not positions of the order):
+        CPU tensors under the trainer's names plus ``sample``.  The CPU-testable reference of the kernel; no fallback."""
+        return gather_host(self.host, indices, self.A, out_f32)
+
+    def ques_ids(self, indices):
+        """question ids of the samples ``indices`` (what ``fill`` leaves in ``sample``), for pairing with an ``AnswerLog``"""
+        return [self.ts.data[int(i)]["question_id"] for i in np.asarray(indices).reshape(-1)]

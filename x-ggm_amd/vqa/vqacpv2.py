@@ -460,21 +460,39 @@ def make_optimizer(model, lr, t_total, warmup=0.1, optim='bert', no_decay=None, 
     return BertAdam(groups, lr=lr, warmup=warmup, t_total=t_total)
 
 
-def predict(model, eval_tuple, dump=None, predictor=None):
+def predict(model, eval_tuple, dump=None, predictor=None, resident=None):
     """``VQA.predict`` (src/vqa/vqacpv2.py:315-339; GQA twin src/gqa/gqa_ood.py:379-403): eval mode, encoder ->
     ``logit_fc`` -> arg-max -> ``{question_id: answer}``.  ``eval_tuple`` = (dset, loader, evaluator) as in the
     reference; only the first four fields of a loader item are looked at (never the ground truth).  ``predictor``:
     an ``engine.CapturedPredictor`` to replay one captured forward per batch instead of launching eagerly.  When the
     predictor carries an ``engine.AnswerLog`` the answers stay on the device for the whole sweep: every batch is only
     queued (``push``), the question ids are kept on the host in call order, and the log is read ONCE behind the loop --
-    no host synchronisation between the first and the last batch (the per-batch ``.cpu()`` of :333 is gone)."""
+    no host synchronisation between the first and the last batch (the per-batch ``.cpu()`` of :333 is gone).
+    ``resident``: a ``tools.resident.ResidentDataset`` of the split: the sweep then goes over the store's samples in data
+    set order, ``predictor.push_resident`` gathers every batch on the device (the last one ragged) and the loader is not
+    iterated; needs a ``predictor``.  Same ``{question_id: answer}`` as the loader path."""
     dset, loader, evaluator = eval_tuple
     dev = next(model.parameters()).device
     was_training = model.training
     model.eval()
     quesid2ans = {}
     try:
-        if predictor is not None and getattr(predictor, "log", None) is not None:
+        if resident is not None:
+            if predictor is None:
+                raise ValueError("predict: a resident store is swept through a CapturedPredictor (predictor=...)")
+            from ..answers import to_quesid2ans
+            log, n, B = getattr(predictor, "log", None), len(resident), predictor.B
+            ques_ids = resident.ques_ids(resident.order(0, shuffle=False, drop_last=False))
+            labels = []
+            if log is not None:
+                log.reset()
+            for start in range(0, n, B):
+                b = predictor.push_resident(resident, start, min(B, n - start))
+                if log is None:
+                    labels.append(predictor.label[:b].cpu())  # a view of a static buffer: consumed before the next push
+            labels = log.read()[0] if log is not None else torch.cat(labels)
+            quesid2ans = to_quesid2ans(ques_ids, labels, dset.label2ans)
+        elif predictor is not None and getattr(predictor, "log", None) is not None:
             from ..answers import to_quesid2ans
             log, ques_ids = predictor.log, []
             log.reset()
@@ -503,9 +521,9 @@ def predict(model, eval_tuple, dump=None, predictor=None):
     return quesid2ans
 
 
-def evaluate(model, eval_tuple, dump=None, predictor=None):
+def evaluate(model, eval_tuple, dump=None, predictor=None, resident=None):
     """``VQA.evaluate`` (src/vqa/vqacpv2.py:341-344)"""
-    return eval_tuple[2].evaluate(predict(model, eval_tuple, dump, predictor))
+    return eval_tuple[2].evaluate(predict(model, eval_tuple, dump, predictor, resident))
 
 
 def save_training_state(path, model, optim, **extra):
