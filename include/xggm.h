@@ -937,19 +937,29 @@ int xggm_cosine_adjacency_f32(const float* cls, const float* attr, float* adj, i
                               xggm_stream_t stream);
 
 /* ---- optimiser ---------------------------------------------------------------------------
- * *out += sum g^2 over a flat fp32 range (clip_grad_norm_, src/vqa/vqacpv2.py:175).  The sum is taken in a
- * fixed order (per-workgroup partials in `ws`, added up by a second one-workgroup launch), so data-parallel
- * replicas that hold identical gradients compute bit-identical norms and stay bit-identical.  `ws`: caller-owned
- * scratch of XGGM_SQNORM_WS_FLOATS floats (contents irrelevant before, undefined after). */
+ * The gradient norm (nn.utils.clip_grad_norm_, src/vqa/vqacpv2.py:175).  Five entries, ONE mechanism -- "sum (the
+ * squares of) some ranges in a fixed order, then finish a scalar" -- in two launches (one when there is no range):
+ *  - ranges: [offsets[i], offsets[i] + lengths[i]) of a 16-byte aligned buffer, non-empty, starting on a multiple of 4
+ *    (fp32) or 8 (bf16) elements; offsets / lengths are HOST arrays.  Squared ranges come first, then (fp32 only) ranges
+ *    summed as they are: the gradient-norm slots of the weight-gradient GEMMs (xggm_gemm_problem.sqsum) already hold
+ *    sums of squares.
+ *  - fixed (range, slice) order: every range gets workgroups in proportion to its length (about 4096 in all), every
+ *    workgroup sums one slice of one range and writes its partial to `ws` at its (range, slice) position; a second
+ *    one-workgroup launch adds the partials in that order.  No floating-point atomics: the bits depend on the ranges
+ *    of the call alone, so data-parallel replicas that hold identical gradients compute identical norms and stay
+ *    bit-identical.  How ranges are grouped into calls decides the slices, and so the bits.
+ *  - `ws`: caller-owned scratch of XGGM_SQNORM_WS_FLOATS floats (contents irrelevant before, undefined after).
+ *  - finish: *out = ((accumulate ? *out : 0) + sum) * mul; *norm (or NULL) = sqrt(*out), the total norm clip_grad_norm_
+ *    returns.  accumulate extends a sum that another call (or an all-reduce over the ranks) has left in *out; mul = 1 /
+ *    world^2 turns the norm of SUMMED data-parallel gradients into the norm of their average.  With no range at all the
+ *    call only seeds / finishes.
+ *  - `tail` (xggm_clip_norm_*, or NULL): work of the pass that the finishing workgroup takes along, see xggm_pass_tail.
+ *
+ * xggm_sqnorm_f32: one squared range, the whole of g[0, n); accumulate = 1, mul = 1, no norm. */
 #define XGGM_SQNORM_WS_FLOATS 4100
 int xggm_sqnorm_f32(const float* g, int64_t n, float* out, float* ws, xggm_stream_t stream);
-/* The same sum over up to 16 ranges [offsets[i], offsets[i] + lengths[i]) of ONE fp32 buffer (HOST arrays; offsets
- * multiples of 4) in two launches, partials added in (range, slice) order: *out = (overwrite ? 0 : *out) + sum;
- * *norm (or NULL) = sqrt(*out) -- the total norm nn.utils.clip_grad_norm_ returns.  n == 0 only seeds / finishes.
- * square == 0 sums the VALUES instead of their squares: the gradient-norm slots of the weight-gradient GEMMs
- * (xggm_gemm_problem.sqsum) already hold sums of squares and are added to the running sum by a second call.
- * mul: the new *out is multiplied by it before the root (1; 1 / world^2 turns the norm of SUMMED data-parallel
- * gradients into the norm of their average). */
+/* up to 16 ranges of ONE fp32 buffer, all squared (square != 0) or all summed as they are (square == 0);
+ * accumulate = !overwrite. */
 int xggm_sqnorm_multi_f32(const float* base, const int64_t* offsets, const int64_t* lengths, int n, float* out, float* norm,
                           float* ws, int overwrite, int square, float mul, xggm_stream_t stream);
 /* BertAdam.step (src/lxrt/optimization.py:159-193) fused with the clip scale
@@ -994,7 +1004,7 @@ int xggm_bertadam_ex(const xggm_adam_args* args, xggm_stream_t stream);
  * update) in ONE launch: src/lxrt/optimization.py:159-193 loops over param_groups, each span carries its own group's
  * lr / schedule value / weight decay.  All spans of a call share the gradient type (g_bf16). */
 int xggm_bertadam_multi(const xggm_adam_args* args, int n, xggm_stream_t stream);
-/* *out += sum g^2 of a flat bf16 range (the wire arena), same fixed summation order as xggm_sqnorm_f32 */
+/* xggm_sqnorm_f32 over a bf16 buffer (the data-parallel wire arena) */
 int xggm_sqnorm_bf16(const void* g, int64_t n, float* out, float* ws, xggm_stream_t stream);
 /* *lr_scale = warmup_linear(*step / t_total, warmup); *step += 1 (optimization.py:42-48) */
 int xggm_sched_step(int64_t* step, float* lr_scale, int64_t t_total, float warmup, xggm_stream_t stream);
@@ -1080,13 +1090,12 @@ typedef struct xggm_sched_entry {
 int xggm_sched_step_ex(int64_t* steps, float* lr_scale, float* step_scalars, const xggm_sched_entry* entries, int n,
                        xggm_stream_t stream);
 
-/* The tail of a pass in two launches instead of seven: nn.utils.clip_grad_norm_'s norm (src/vqa/vqacpv2.py:175) over up
- * to 24 ranges in all -- `n` ranges of the gradient buffer `g` (squared) and `n_slots` ranges of the slot table the
- * weight-gradient products filled (xggm_gemm_problem.sqsum: summed as they are) -- with partials added in (range, slice)
- * order (fixed: replicas stay bit-identical); *out = sum * mul, *norm (or NULL) = sqrt(*out).  With `tail` the finishing
- * workgroup also performs xggm_sched_step_multi's schedule step for tail->n counters (BertAdam.step's bookkeeping,
- * src/lxrt/optimization.py:170-180) and, with tail->rng, xggm_rng_advance(rng, rng_by).  offsets / lengths / tail's
- * arrays: HOST arrays; offsets multiples of 4; ws: XGGM_SQNORM_WS_FLOATS floats. */
+/* The tail of a pass in two launches instead of seven: the norm (see "optimiser" above) over up to 24 ranges in all --
+ * `n` ranges of the gradient buffer `g` (squared) and `n_slots` ranges of the slot table the weight-gradient products
+ * filled (summed as they are); accumulate = 0.  With `tail` the finishing workgroup also performs
+ * xggm_sched_step_multi's schedule step for tail->n counters (BertAdam.step's bookkeeping,
+ * src/lxrt/optimization.py:170-180; index, t_total, warmup: HOST arrays) and, with tail->rng, xggm_rng_advance(rng,
+ * rng_by). */
 typedef struct {
     int64_t* steps;
     float* lr_scale;
@@ -1100,9 +1109,8 @@ typedef struct {
 int xggm_clip_norm_f32(const float* g, const int64_t* offsets, const int64_t* lengths, int n, const float* slots,
                        const int64_t* slot_offsets, const int64_t* slot_lengths, int n_slots, float* out, float* norm, float* ws,
                        float mul, const xggm_pass_tail* tail, xggm_stream_t stream);
-/* the same pair of launches over up to 24 ranges of a BF16 buffer (the data-parallel wire arena, offsets multiples of 8):
- * *out = ((accumulate ? *out : 0) + sum g^2) * mul -- accumulate = 1 extends a sum another call (or an all-reduce over the
- * ranks, sharded update) has left in *out; mul = 1 / world^2 turns the norm of SUMMED gradients into that of their mean. */
+/* the same over up to 24 squared ranges of a BF16 buffer (the data-parallel wire arena); accumulate = 1 is the sharded
+ * update's second half */
 int xggm_clip_norm_bf16(const void* g, const int64_t* offsets, const int64_t* lengths, int n, float* out, float* norm, float* ws,
                         int accumulate, float mul, const xggm_pass_tail* tail, xggm_stream_t stream);
 

@@ -1059,6 +1059,183 @@ def test_clip_norm_over_the_bf16_wire(ops):
         ops.clip_norm_bf16(g, [(4, 100)], o2)
 
 
+def _bits(t):
+    """the 32-bit pattern of a one-element fp32 tensor"""
+    return int(t.view(torch.int32).item())
+
+
+def _lay_out(lengths, align):
+    """(start, end) ranges of those lengths one behind the other, every start on a multiple of ``align``, and the room
+    they need"""
+    spans, pos = [], 0
+    for n in lengths:
+        spans.append((pos, pos + n))
+        pos = (pos + n + align - 1) // align * align + align  # a gap of at least one vector that no range reads
+    return spans, pos
+
+
+def test_norm_entries_share_one_range_mechanism(ops):
+    """xggm_sqnorm_f32 / _multi_f32 / _bf16 and xggm_clip_norm_f32 / _bf16 are one first stage (a workgroup per slice of
+    a range), one finish and one planner.  Lengths sit where the range code changes path, with NT = 256 the workgroup
+    size of loss_optim.hip and 32 (fp32) or 64 (bf16) elements per thread of a full workgroup: no whole 16-byte vector,
+    exactly one, the first trip of the four-in-flight loop, exactly one workgroup's share, one element more (a second
+    workgroup and a remainder lane), five workgroups and a remainder; 16 ranges (sqnorm_multi's limit per launch), 24
+    (clip_norm's).  Values lie in [0.25, 1.25): sums of squares and plain sums are both well conditioned, and the
+    tolerance against float64 is the neighbouring tests' 2e-6 relative.
+    1. every entry agrees with float64, honours mul, overwrite / accumulate and norm = sqrt(out), and a call without
+       ranges writes 0 or leaves out * mul;  2. the entries give the same BITS for the same ranges;  3. and the same bits
+       from call to call;  4. sched_step, sched_step_multi and clip_norm's tail take the same schedule step."""
+    from oracle import xggm_oracle as O
+    NT = 256
+    lens = [3, 4, 16 * NT + 4, 32 * NT, 32 * NT + 1, 5 * 32 * NT + 2]
+    short = [5, 12, 1, 33, 8, 3, 64, 7, 19, 4, 2, 100, 9, 6, 31, 17, 11, 13, 4, 25, 1, 40, 3, 10]
+    gen = torch.Generator().manual_seed(11)
+    RTOL = 2e-6
+
+    def zero():
+        return torch.zeros(1, device=DEV)
+
+    def full(v):
+        return torch.full((1,), float(v), device=DEV)
+
+    def close(got, want, scale=None):
+        assert abs(float(got) - want) <= RTOL * (want if scale is None else scale), (float(got), want)
+
+    def same(fn, n=3):
+        """fn() -> a one-element tensor; called n times it gives one bit pattern, which is returned"""
+        seen = {_bits(fn()) for _ in range(n)}
+        assert len(seen) == 1, seen
+        return seen.pop()
+
+    # ------------------------------------------------------------------ fp32: ranges, 16 and 24 short ranges, slot ranges
+    spans, room = _lay_out(lens, 4)
+    shorts, room_s = _lay_out(short, 4)
+    shorts = [(a + room, b + room) for a, b in shorts]
+    g = (torch.rand(room + room_s, generator=gen) + 0.25).to(DEV)
+    slots = (torch.rand(room + room_s, generator=gen) + 0.25).to(DEV)
+    g64, s64 = g.double().cpu(), slots.double().cpu()
+
+    def sq(rs):
+        return sum(float((g64[a:b] ** 2).sum()) for a, b in rs)
+
+    def plain(rs):
+        return sum(float(s64[a:b].sum()) for a, b in rs)
+
+    def multi(buf, rs, **kw):
+        o = zero()
+        ops.sqnorm_multi(buf, rs, o, **kw)
+        return o
+
+    def clip(rs, ss, **kw):
+        o = full(-7.0)  # clip_norm never accumulates
+        ops.clip_norm(g, rs, slots if ss else None, ss, o, **kw)
+        return o
+
+    def single(a, b):
+        o = zero()
+        ops.sqnorm(g[a:b], o)
+        return o
+
+    for a, b in spans:  # every length alone: the grid of a single range is what its length asks for
+        want = sq([(a, b)])
+        one = same(lambda: single(a, b))
+        close(single(a, b), want)
+        assert one == same(lambda: multi(g, [(a, b)])) == same(lambda: clip([(a, b)], []))
+        o = full(1.5)  # sqnorm extends the sum it finds
+        ops.sqnorm(g[a:b], o)
+        close(o, 1.5 + want)
+    for rs in (spans, shorts[:16], spans + shorts[:10]):  # side by side: workgroups shared out in proportion
+        want = sq(rs)
+        both = same(lambda: multi(g, rs))
+        close(multi(g, rs), want)
+        assert both == same(lambda: clip(rs, []))
+        o, nrm = full(2.0), zero()  # overwrite / accumulate, mul, norm
+        ops.sqnorm_multi(g, rs, o, nrm, overwrite=False, mul=0.25)
+        close(o, 0.25 * (2.0 + want))
+        close(nrm, (0.25 * (2.0 + want)) ** 0.5)
+        ops.sqnorm_multi(g, rs, o, nrm, overwrite=True)
+        close(o, want)
+        close(nrm, want ** 0.5)
+    close(multi(g, shorts), sq(shorts))  # 24 ranges through sqnorm_multi: two launch pairs, 16 + 8
+    same(lambda: multi(g, shorts))
+    for ss in (spans, shorts[:16]):  # summed as they are: sqnorm_multi(square=False) and clip_norm's slot ranges
+        want = plain(ss)
+        b0 = same(lambda: multi(slots, ss, square=False))
+        close(multi(slots, ss, square=False), want)
+        assert b0 == same(lambda: clip([], ss))
+    for rs, ss in ((spans, spans[2:4]), (shorts[:16], shorts[16:]), (shorts[:3], shorts[3:])):  # up to 24 in all
+        want = sq(rs) + plain(ss)
+        same(lambda: clip(rs, ss))
+        nrm = zero()
+        o = clip(rs, ss, norm=nrm, mul=0.25)
+        close(o, 0.25 * want)
+        close(nrm, (0.25 * want) ** 0.5)
+    # no ranges: the finish alone
+    assert float(multi(g, [])) == 0.0 and float(clip([], [])) == 0.0
+    o = full(3.0)
+    ops.sqnorm_multi(g, [], o, overwrite=True)
+    assert float(o) == 0.0
+    o = full(3.0)
+    ops.sqnorm_multi(g, [], o, overwrite=False, mul=0.5)
+    assert float(o) == 1.5
+
+    # ------------------------------------------------------------------ bf16: the same lengths, bf16's own, 7 elements
+    lens16 = lens + [7, 32 * NT + 8, 64 * NT, 64 * NT + 1, 3 * 64 * NT + 9]
+    spans16, room16 = _lay_out(lens16, 8)
+    shorts16, room16_s = _lay_out(short, 8)
+    shorts16 = [(a + room16, b + room16) for a, b in shorts16]
+    w = (torch.rand(room16 + room16_s, generator=gen) + 0.25).to(torch.bfloat16).to(DEV)
+    w64 = w.double().cpu()
+
+    def sq16(rs):
+        return sum(float((w64[a:b] ** 2).sum()) for a, b in rs)
+
+    def clip16(rs, seed=None, **kw):
+        o = full(-7.0 if seed is None else seed)
+        ops.clip_norm_bf16(w, rs, o, accumulate=seed is not None, **kw)
+        return o
+
+    def single16(a, b):
+        o = zero()
+        ops.sqnorm_bf16(w[a:b], o)
+        return o
+
+    for a, b in spans16:
+        want = sq16([(a, b)])
+        one = same(lambda: single16(a, b))
+        close(single16(a, b), want)
+        assert one == same(lambda: clip16([(a, b)]))
+        o = full(1.5)
+        ops.sqnorm_bf16(w[a:b], o)
+        close(o, 1.5 + want)
+    for rs in (spans16, shorts16, spans16 + shorts16[:13]):
+        want = sq16(rs)
+        same(lambda: clip16(rs))
+        close(clip16(rs), want)
+        nrm = zero()
+        o = clip16(rs, seed=2.0, norm=nrm, mul=0.25)
+        close(o, 0.25 * (2.0 + want))
+        close(nrm, (0.25 * (2.0 + want)) ** 0.5)
+    assert float(clip16([])) == 0.0 and float(clip16([], seed=3.0, mul=0.5)) == 1.5
+
+    # ------------------------------------------------------------------ the schedule step: three carriers, one function
+    for s0, tt, wu in ((0, 100, 0.1), (1, 100, 0.1), (5, 100, 0.1), (50, 100, 0.1), (150, 100, 0.1), (7, -1, 0.1)):
+        got = []
+        for how in ("single", "multi", "tail"):
+            steps, scale = torch.tensor([s0], dtype=torch.int64, device=DEV), full(-1.0)
+            if how == "single":
+                ops.sched_step(steps, scale, tt, wu)
+            elif how == "multi":
+                ops.sched_step_multi(steps, scale, [(0, tt, wu)])
+            else:
+                ops.clip_norm(g, spans[:1], None, [], zero(), sched=(steps, scale, [(0, tt, wu)]))
+            assert steps.tolist() == [s0 + 1]
+            got.append(_bits(scale))
+            want = O.warmup_linear(s0 / tt, wu) if tt > 0 else 1.0
+            assert np.allclose(float(scale), want, rtol=1e-6, atol=1e-7), (how, s0, tt, float(scale), want)
+        assert len(set(got)) == 1, (s0, tt, got)
+
+
 # ------------------------------------------------------------------------------------------------ fp8 forward (C5)
 def _e4m3(x, q):
     """reference quantisation: torch's float8_e4m3fn cast of clamp(x * q, +-448), as uint8 bits"""

@@ -2,7 +2,7 @@
 //   xggm_dsm_loss_fwd/bwd   denoising score matching  (src/vqa/vqacpv2.py:48-51)
 //   xggm_symkl_fwd/bwd      symmetric KL of row softmaxes (src/vqa/vqacpv2.py:54-61)
 //   xggm_bce_fwd/bwd        BCEWithLogits(mean) * A   (src/vqa/vqacpv2.py:131,173)
-//   xggm_sqnorm_f32         sum of squares of a flat fp32 gradient range (clip_grad_norm_, vqacpv2.py:175)
+//   xggm_sqnorm_* / xggm_clip_norm_*  sum of squares of gradient ranges in a fixed order (clip_grad_norm_, vqacpv2.py:175)
 //   xggm_bertadam_f32       clip-scale + BertAdam update + bf16 shadow weight, ONE pass over
 //                           p/g/m/v (src/lxrt/optimization.py:159-193): 16 B read + 12(+2) B
 //                           written per parameter, the HBM floor of the update.
@@ -168,52 +168,13 @@ __global__ __launch_bounds__(NT) void bce_bwd_kernel(const float* __restrict__ l
 }
 
 // ------------------------------------------------------------------------------- optimiser
-__global__ __launch_bounds__(NT) void sqnorm_kernel(const float* __restrict__ g, int64_t n, float* out, float* ws) {
-    float acc = 0.f;
-    const int64_t n4 = n >> 2;
-    typedef float __attribute__((ext_vector_type(4))) f4;
-    const f4* g4 = reinterpret_cast<const f4*>(g);
-    const int64_t stride = (int64_t)gridDim.x * NT;
-    int64_t i = (int64_t)blockIdx.x * NT + threadIdx.x;
-    // four independent 16-byte loads in flight per thread
-    for (; i + 3 * stride < n4; i += 4 * stride) {
-        const f4 a = __builtin_nontemporal_load(g4 + i), b = __builtin_nontemporal_load(g4 + i + stride),
-                 c = __builtin_nontemporal_load(g4 + i + 2 * stride), d = __builtin_nontemporal_load(g4 + i + 3 * stride);
-        acc += (a.x * a.x + a.y * a.y + a.z * a.z + a.w * a.w) + (b.x * b.x + b.y * b.y + b.z * b.z + b.w * b.w) +
-               (c.x * c.x + c.y * c.y + c.z * c.z + c.w * c.w) + (d.x * d.x + d.y * d.y + d.z * d.z + d.w * d.w);
-    }
-    for (; i < n4; i += stride) {
-        const f4 v = g4[i];
-        acc += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
-    }
-    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
-        const float v = g[(n4 << 2) + threadIdx.x];
-        acc += v * v;
-    }
-    acc = block_sum(acc);
-    if (threadIdx.x == 0) ws[blockIdx.x] = acc;  // per-workgroup partial; summed in index order by sqnorm_finish_kernel
-}
-
-// second stage: one workgroup adds the partials in a fixed order (no floating-point atomics: replicas that hold
-// the same gradients get the same bits).  A separate launch instead of a last-arriver finish in the first
-// kernel: the device-scope fence that needs costs an L2 write-back per workgroup (3.5 -> 1.6 TB/s measured).
-__global__ __launch_bounds__(NT) void sqnorm_finish_kernel(const float* __restrict__ ws, int nblk, float* out) {
-    float t = 0.f;
-    for (int b = threadIdx.x; b < nblk; b += NT) t += ws[b];
-    t = block_sum(t);
-    if (threadIdx.x == 0) *out += t;
-}
-
-// clip_grad_norm_ over SEVERAL ranges of one fp32 buffer in two launches: every workgroup owns one slice of one
-// range (ranges get workgroups in proportion to their length), partials land in ws in (range, slice) order and one
-// workgroup adds them in that order -- the same bits whatever the scheduling.  The finish also seeds / extends the
-// running sum and writes the norm, so the host issues no fill, add or sqrt kernels around it.
-constexpr int MAX_SPANS = 16;
-struct Spans {
-    int64_t off[MAX_SPANS], len[MAX_SPANS];
-    int blk0[MAX_SPANS + 1];  // first workgroup of each range
-    int n;
-};
+// The gradient norm (clip_grad_norm_, vqacpv2.py:175): "sum (the squares of) some ranges in a fixed order, then finish a
+// scalar", in two launches.  norm_partials_kernel: every workgroup owns one slice of one range and writes its partial to
+// ws in (range, slice) order.  norm_finish_kernel: one workgroup adds the partials in that order -- no floating-point
+// atomics, the same bits whatever the scheduling, so replicas that hold the same gradients keep the same norm.  A
+// separate launch instead of a last-arriver finish in the first kernel: the device-scope fence that needs costs an L2
+// write-back per workgroup (3.5 -> 1.6 TB/s measured).  norm_of_ranges (below) shares out the workgroups.
+//
 // one workgroup's share of one range: slice b of nb, four 16-byte loads in flight per thread
 template <bool SQ>
 __device__ __forceinline__ float span_partial(const float* __restrict__ g, int64_t n, int b, int nb) {
@@ -244,37 +205,7 @@ __device__ __forceinline__ float span_partial(const float* __restrict__ g, int64
     return block_sum(acc);
 }
 
-template <bool SQ>
-__global__ __launch_bounds__(NT) void sqnorm_multi_kernel(const float* __restrict__ base, Spans sp, float* ws) {
-    int k = 0;
-#pragma unroll
-    for (int j = 1; j < MAX_SPANS; ++j)
-        if (j < sp.n && (int)blockIdx.x >= sp.blk0[j]) k = j;
-    const float acc = span_partial<SQ>(base + sp.off[k], sp.len[k], blockIdx.x - sp.blk0[k], sp.blk0[k + 1] - sp.blk0[k]);
-    if (threadIdx.x == 0) ws[blockIdx.x] = acc;
-}
-
-// The norm of a whole pass in ONE pair of launches (xggm_clip_norm_f32): ranges of the gradient buffer (squared) and
-// ranges of the slot table the weight-gradient products filled (already sums of squares: added as they are) side by
-// side in one grid, partials in (range, slice) order; the finishing workgroup also takes the schedule step and the
-// RNG advance of the pass along (three one-workgroup launches of their own before).
-constexpr int MAX_NORM_SPANS = 24;
-struct NormSpans {
-    const float* ptr[MAX_NORM_SPANS];
-    int64_t len[MAX_NORM_SPANS];
-    int blk0[MAX_NORM_SPANS + 1];
-    int n, n_sq;  // ranges [0, n_sq) are squared, [n_sq, n) summed as they are
-};
-__global__ __launch_bounds__(NT) void clip_norm_kernel(NormSpans sp, float* ws) {
-    int k = 0;
-#pragma unroll
-    for (int j = 1; j < MAX_NORM_SPANS; ++j)
-        if (j < sp.n && (int)blockIdx.x >= sp.blk0[j]) k = j;
-    const int b = blockIdx.x - sp.blk0[k], nb = sp.blk0[k + 1] - sp.blk0[k];
-    const float acc = k < sp.n_sq ? span_partial<true>(sp.ptr[k], sp.len[k], b, nb) : span_partial<false>(sp.ptr[k], sp.len[k], b, nb);
-    if (threadIdx.x == 0) ws[blockIdx.x] = acc;
-}
-// the same grid over ranges of a bf16 buffer (the data-parallel wire arena): 8 elements per 16-byte load, four in flight
+// the same slice of a range of a bf16 buffer (the data-parallel wire arena): 8 elements per 16-byte load, four in flight
 __device__ __forceinline__ float span_partial_bf16(const bf16* __restrict__ g, int64_t n, int b, int nb) {
     typedef short __attribute__((ext_vector_type(8))) s8;
     const s8* g8 = reinterpret_cast<const s8*>(g);
@@ -302,53 +233,29 @@ __device__ __forceinline__ float span_partial_bf16(const bf16* __restrict__ g, i
     }
     return block_sum(acc);
 }
-struct NormSpans16 {
-    const bf16* ptr[MAX_NORM_SPANS];
+
+// ranges [0, n_sq) are squared, [n_sq, n) summed as they are (fp32 only: a bf16 launch has n_sq == n)
+constexpr int MAX_NORM_SPANS = 24;
+template <typename T>
+struct NormSpans {
+    const T* ptr[MAX_NORM_SPANS];
     int64_t len[MAX_NORM_SPANS];
-    int blk0[MAX_NORM_SPANS + 1];
-    int n;
+    int blk0[MAX_NORM_SPANS + 1];  // first workgroup of each range
+    int n, n_sq;
 };
-__global__ __launch_bounds__(NT) void clip_norm_bf16_kernel(NormSpans16 sp, float* ws) {
+// first stage: workgroup blockIdx.x finds its range k and its slice of it, and leaves that slice's sum in ws[blockIdx.x]
+template <typename T>
+__global__ __launch_bounds__(NT) void norm_partials_kernel(NormSpans<T> sp, float* ws) {
     int k = 0;
 #pragma unroll
     for (int j = 1; j < MAX_NORM_SPANS; ++j)
         if (j < sp.n && (int)blockIdx.x >= sp.blk0[j]) k = j;
-    const float acc = span_partial_bf16(sp.ptr[k], sp.len[k], blockIdx.x - sp.blk0[k], sp.blk0[k + 1] - sp.blk0[k]);
-    if (threadIdx.x == 0) ws[blockIdx.x] = acc;
-}
-
-__global__ __launch_bounds__(NT) void sqnorm_multi_finish_kernel(const float* __restrict__ ws, int nblk, float* out, float* norm,
-                                                                 int overwrite, float mul) {
-    float t = 0.f;
-    for (int b = threadIdx.x; b < nblk; b += NT) t += ws[b];
-    t = block_sum(t);
-    if (threadIdx.x == 0) {
-        const float s = ((overwrite ? 0.f : *out) + t) * mul;
-        *out = s;
-        if (norm) *norm = sqrtf(s);
-    }
-}
-
-// the same sum over a bf16 buffer (data-parallel wire arena): 8 elements per 16-byte load
-__global__ __launch_bounds__(NT) void sqnorm_bf16_kernel(const bf16* __restrict__ g, int64_t n, float* ws) {
-    float acc = 0.f;
-    const int64_t n8 = n >> 3;
-    typedef short __attribute__((ext_vector_type(8))) s8;
-    const s8* g8 = reinterpret_cast<const s8*>(g);
-    const int64_t stride = (int64_t)gridDim.x * NT;
-    for (int64_t i = (int64_t)blockIdx.x * NT + threadIdx.x; i < n8; i += stride) {
-        const s8 v = __builtin_nontemporal_load(g8 + i);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const float f = __bfloat162float(__builtin_bit_cast(bf16, (short)v[e]));
-            acc += f * f;
-        }
-    }
-    if (blockIdx.x == 0 && threadIdx.x < (n & 7)) {
-        const float f = __bfloat162float(g[(n8 << 3) + threadIdx.x]);
-        acc += f * f;
-    }
-    acc = block_sum(acc);
+    const int b = blockIdx.x - sp.blk0[k], nb = sp.blk0[k + 1] - sp.blk0[k];
+    float acc;
+    if constexpr (std::is_same<T, float>::value)
+        acc = k < sp.n_sq ? span_partial<true>(sp.ptr[k], sp.len[k], b, nb) : span_partial<false>(sp.ptr[k], sp.len[k], b, nb);
+    else
+        acc = span_partial_bf16(sp.ptr[k], sp.len[k], b, nb);
     if (threadIdx.x == 0) ws[blockIdx.x] = acc;
 }
 
@@ -750,9 +657,9 @@ __global__ __launch_bounds__(1024) void fp8_scale_update_kernel(float* amax, flo
     if (bump && threadIdx.x == 0) *pos += 1;
 }
 
-// lr_scale = warmup_linear(step / t_total, warmup); step += 1   (t_total <= 0: scale = 1)
-__global__ void sched_kernel(int64_t* step, float* lr_scale, int64_t t_total, float warmup) {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+// the float schedule step of one counter: *lr_scale = warmup_linear(*step / t_total, warmup); *step += 1
+// (optimization.py:42-48; t_total <= 0: scale = 1)
+__device__ __forceinline__ void sched_step_f32(int64_t* step, float* lr_scale, int64_t t_total, float warmup) {
     const int64_t s = *step;
     float sc = 1.f;
     if (t_total > 0) {
@@ -763,7 +670,7 @@ __global__ void sched_kernel(int64_t* step, float* lr_scale, int64_t t_total, fl
     *step = s + 1;
 }
 
-// the same for several counters of one table in ONE launch (all parameter groups of an optimiser step)
+// that step for several counters of one table in ONE launch (all parameter groups of an optimiser step)
 constexpr int MAX_SCHED = 16;
 struct SchedArgs {
     int index[MAX_SCHED];
@@ -774,15 +681,26 @@ struct SchedArgs {
 __global__ void sched_multi_kernel(int64_t* steps, float* lr_scale, SchedArgs a) {
     const int i = threadIdx.x;
     if (blockIdx.x != 0 || i >= a.n) return;
-    const int k = a.index[i];
-    const int64_t s = steps[k];
-    float sc = 1.f;
-    if (a.t_total[i] > 0) {
-        const float x = (float)((double)s / (double)a.t_total[i]);
-        sc = x < a.warmup[i] ? x / a.warmup[i] : fmaxf((x - 1.f) / (a.warmup[i] - 1.f), 0.f);
+    sched_step_f32(steps + a.index[i], lr_scale + a.index[i], a.t_total[i], a.warmup[i]);
+}
+
+// second stage of the norm: one workgroup adds the partials in index order, seeds / extends the running sum, scales it,
+// writes the norm, and takes the tail of the pass along (schedule step of sa.n counters, RNG advance): the host issues
+// no fill, add, sqrt, schedule or RNG kernels around it.
+__global__ __launch_bounds__(NT) void norm_finish_kernel(const float* __restrict__ ws, int nblk, float* out, float* norm, float mul,
+                                                         int64_t* steps, float* lr_scale, SchedArgs sa, uint64_t* rng,
+                                                         uint64_t rng_by, int accumulate) {
+    float t = 0.f;
+    for (int b = threadIdx.x; b < nblk; b += NT) t += ws[b];
+    t = block_sum(t);
+    if (threadIdx.x == 0) {
+        const float s = ((accumulate ? *out : 0.f) + t) * mul;
+        *out = s;
+        if (norm) *norm = sqrtf(s);
+        if (rng) rng[1] += rng_by;
     }
-    lr_scale[k] = sc;
-    steps[k] = s + 1;
+    const int i = threadIdx.x;
+    if (i < sa.n) sched_step_f32(steps + sa.index[i], lr_scale + sa.index[i], sa.t_total[i], sa.warmup[i]);
 }
 
 // sched_multi_kernel with a schedule kind per entry (src/lxrt/optimization.py:27-48), evaluated in double, and the
@@ -863,6 +781,80 @@ int symkl(const void* x, const void* y, float* loss, const float* gout, void* dx
     return xggm_check_launch("xggm_symkl");
 }
 
+// ------------------------------------------------------------------------------- norm of ranges: host side
+struct TailArgs {
+    SchedArgs sa;
+    int64_t* steps = nullptr;
+    float* lr_scale = nullptr;
+    uint64_t* rng = nullptr;
+    uint64_t rng_by = 0;
+};
+int tail_args_of(const xggm_pass_tail* tail, TailArgs& ta) {
+    ta.sa.n = 0;
+    if (!tail) return XGGM_OK;
+    XGGM_REQUIRE(tail->n >= 0 && tail->n <= MAX_SCHED && (tail->n == 0 || (tail->steps && tail->lr_scale && tail->index &&
+                                                                         tail->t_total && tail->warmup)),
+                 "xggm_clip_norm: bad schedule entries (n = %d, at most %d)", tail->n, MAX_SCHED);
+    ta.sa.n = tail->n;
+    for (int i = 0; i < tail->n; ++i) {
+        XGGM_REQUIRE(tail->index[i] >= 0, "xggm_clip_norm: negative schedule index");
+        for (int j = 0; j < i; ++j)
+            XGGM_REQUIRE(tail->index[j] != tail->index[i], "xggm_clip_norm: counter %d listed twice", tail->index[i]);
+        ta.sa.index[i] = tail->index[i];
+        ta.sa.t_total[i] = tail->t_total[i];
+        ta.sa.warmup[i] = tail->warmup[i];
+    }
+    ta.steps = tail->steps;
+    ta.lr_scale = tail->lr_scale;
+    ta.rng = tail->rng;
+    ta.rng_by = tail->rng_by;
+    return XGGM_OK;
+}
+
+// The one planner behind the five xggm_sqnorm_* / xggm_clip_norm_* entries: validates the n <= MAX_NORM_SPANS ranges
+// (squared ones first), hands every range workgroups in proportion to its length -- 4096 in all plus at most one per
+// range (the partials fit XGGM_SQNORM_WS_FLOATS), no more than leave a thread eight 16-byte loads, at least one --
+// and issues the first stage (if there is any range) and the finish.  `who`: the entry's name, for the error texts.
+template <typename T>
+struct NormRange {
+    const T* base;
+    int64_t off, len;
+    bool sq;
+};
+template <typename T>
+int norm_of_ranges(const char* who, const NormRange<T>* r, int n, float* out, float* norm, float* ws, int accumulate, float mul,
+                   const xggm_pass_tail* tail, hipStream_t st) {
+    constexpr int VEC = 16 / sizeof(T), PER = 8 * VEC;  // elements per 16-byte load; per thread of a full workgroup
+    XGGM_REQUIRE(out && ws && n >= 0 && n <= MAX_NORM_SPANS, "%s: bad arguments (null out or ws, or %d ranges)", who, n);
+    NormSpans<T> sp;
+    sp.n = n;
+    sp.n_sq = 0;
+    int64_t total = 0;
+    for (int i = 0; i < n; ++i) {
+        XGGM_REQUIRE(reinterpret_cast<uintptr_t>(r[i].base) % 16 == 0, "%s: buffers must be 16-byte aligned", who);
+        XGGM_REQUIRE(r[i].off >= 0 && r[i].len > 0 && r[i].off % VEC == 0, "%s: range %d (offset %lld, length %lld) must be "
+                     "non-empty and start on a multiple of %d", who, i, (long long)r[i].off, (long long)r[i].len, VEC);
+        XGGM_REQUIRE(r[i].sq ? sp.n_sq == i : sizeof(T) == 4, "%s: internal: range %d out of place", who, i);
+        sp.n_sq += r[i].sq;
+        sp.ptr[i] = r[i].base + r[i].off;
+        sp.len[i] = r[i].len;
+        total += r[i].len;
+    }
+    int nblk = 0;
+    for (int i = 0; i < n; ++i) {
+        sp.blk0[i] = nblk;
+        nblk += (int)std::max<int64_t>(1, std::min<int64_t>(ceil_div64(sp.len[i], (int64_t)NT * PER), (4096 - n) * sp.len[i] / total + 1));
+    }
+    sp.blk0[n] = nblk;
+    XGGM_REQUIRE(nblk <= 4100, "%s: internal: %d partials", who, nblk);
+    TailArgs ta;
+    if (int e = tail_args_of(tail, ta)) return e;
+    if (nblk > 0) hipLaunchKernelGGL(norm_partials_kernel<T>, dim3(nblk), dim3(NT), 0, st, sp, ws);
+    hipLaunchKernelGGL(norm_finish_kernel, dim3(1), dim3(NT), 0, st, ws, nblk, out, norm, mul, ta.steps, ta.lr_scale, ta.sa, ta.rng,
+                       ta.rng_by, accumulate);
+    return xggm_check_launch(who);
+}
+
 }  // namespace
 
 #define LOSS_API(SUF, T)                                                                                                   \
@@ -899,13 +891,9 @@ extern "C" int xggm_bce_fwd(const float* l, const float* t, float* loss, int64_t
 }
 
 extern "C" int xggm_sqnorm_f32(const float* g, int64_t n, float* out, float* ws, hipStream_t st) {
-    XGGM_REQUIRE(g && out && ws && n > 0, "xggm_sqnorm_f32: bad arguments");
-    XGGM_REQUIRE(reinterpret_cast<uintptr_t>(g) % 16 == 0, "xggm_sqnorm_f32: pointer must be 16-byte aligned");
-    // at least 8 float4 per thread: the per-workgroup atomics all hit ONE address and serialise
-    const int nblk = grid1d(n / 32 + 1, 4096);
-    hipLaunchKernelGGL(sqnorm_kernel, dim3(nblk), dim3(NT), 0, st, g, n, out, ws);
-    hipLaunchKernelGGL(sqnorm_finish_kernel, dim3(1), dim3(NT), 0, st, ws, nblk, out);
-    return xggm_check_launch("xggm_sqnorm_f32");
+    XGGM_REQUIRE(g && n > 0, "xggm_sqnorm_f32: bad arguments");
+    const NormRange<float> r{g, 0, n, true};
+    return norm_of_ranges("xggm_sqnorm_f32", &r, 1, out, nullptr, ws, 1, 1.f, nullptr, st);
 }
 
 namespace {
@@ -934,34 +922,12 @@ extern "C" int xggm_bertadam_f32(float* p, const float* g, float* m, float* v, v
 
 extern "C" int xggm_sqnorm_multi_f32(const float* base, const int64_t* offsets, const int64_t* lengths, int n, float* out,
                                      float* norm, float* ws, int overwrite, int square, float mul, hipStream_t st) {
-    XGGM_REQUIRE(base && offsets && lengths && out && ws && n >= 0 && n <= MAX_SPANS,
-                 "xggm_sqnorm_multi_f32: bad arguments (n = %d, at most %d ranges)", n, MAX_SPANS);
-    XGGM_REQUIRE(reinterpret_cast<uintptr_t>(base) % 16 == 0, "xggm_sqnorm_multi_f32: base must be 16-byte aligned");
-    Spans sp;
-    sp.n = n;
-    int64_t total = 0;
-    for (int i = 0; i < n; ++i) {
-        XGGM_REQUIRE(offsets[i] >= 0 && lengths[i] > 0 && offsets[i] % 4 == 0, "xggm_sqnorm_multi_f32: range %d (offset %lld, "
-                     "length %lld) must be non-empty and start on a multiple of 4", i, (long long)offsets[i], (long long)lengths[i]);
-        sp.off[i] = offsets[i];
-        sp.len[i] = lengths[i];
-        total += lengths[i];
-    }
-    // 4096 workgroups in all (the partials fit XGGM_SQNORM_WS_FLOATS), at least 8 float4 per thread, at least one each
-    int nblk = 0;
-    for (int i = 0; i < n; ++i) {
-        sp.blk0[i] = nblk;
-        const int64_t want = std::max<int64_t>(1, std::min<int64_t>(ceil_div64(lengths[i], (int64_t)NT * 32), (4096 - n) * lengths[i] / total + 1));
-        nblk += (int)want;
-    }
-    sp.blk0[n] = nblk;
-    XGGM_REQUIRE(nblk <= 4100, "xggm_sqnorm_multi_f32: internal: %d partials", nblk);
-    if (nblk > 0) {
-        if (square) hipLaunchKernelGGL(sqnorm_multi_kernel<true>, dim3(nblk), dim3(NT), 0, st, base, sp, ws);
-        else hipLaunchKernelGGL(sqnorm_multi_kernel<false>, dim3(nblk), dim3(NT), 0, st, base, sp, ws);
-    }
-    hipLaunchKernelGGL(sqnorm_multi_finish_kernel, dim3(1), dim3(NT), 0, st, ws, nblk, out, norm, overwrite, mul);
-    return xggm_check_launch("xggm_sqnorm_multi_f32");
+    // 16 and not MAX_NORM_SPANS: how callers chunk their ranges decides the workgroups each gets, and so the bits
+    XGGM_REQUIRE(base && offsets && lengths && n >= 0 && n <= 16,
+                 "xggm_sqnorm_multi_f32: bad arguments (n = %d, at most 16 ranges)", n);
+    NormRange<float> r[16];
+    for (int i = 0; i < n; ++i) r[i] = {base, offsets[i], lengths[i], square != 0};
+    return norm_of_ranges("xggm_sqnorm_multi_f32", r, n, out, norm, ws, !overwrite, mul, nullptr, st);
 }
 
 extern "C" int xggm_bertadam_ex(const xggm_adam_args* x, hipStream_t st) {
@@ -1161,12 +1127,9 @@ int optim_multi(const xggm_optim_args* args, int n, const xggm_hyper_map* map, h
 }  // namespace
 
 extern "C" int xggm_sqnorm_bf16(const void* g, int64_t n, float* out, float* ws, hipStream_t st) {
-    XGGM_REQUIRE(g && out && ws && n > 0, "xggm_sqnorm_bf16: bad arguments");
-    XGGM_REQUIRE(reinterpret_cast<uintptr_t>(g) % 16 == 0, "xggm_sqnorm_bf16: pointer must be 16-byte aligned");
-    const int nblk = grid1d(n / 64 + 1, 4096);
-    hipLaunchKernelGGL(sqnorm_bf16_kernel, dim3(nblk), dim3(NT), 0, st, (const bf16*)g, n, ws);
-    hipLaunchKernelGGL(sqnorm_finish_kernel, dim3(1), dim3(NT), 0, st, ws, nblk, out);
-    return xggm_check_launch("xggm_sqnorm_bf16");
+    XGGM_REQUIRE(g && n > 0, "xggm_sqnorm_bf16: bad arguments");
+    const NormRange<bf16> r{(const bf16*)g, 0, n, true};
+    return norm_of_ranges("xggm_sqnorm_bf16", &r, 1, out, nullptr, ws, 1, 1.f, nullptr, st);
 }
 
 extern "C" int xggm_fp8_scale_update(float* amax, float* hist, float* qscale, float* dscale, int64_t* pos, int n,
@@ -1183,7 +1146,12 @@ extern "C" int xggm_fp8_scale_update(float* amax, float* hist, float* qscale, fl
 
 extern "C" int xggm_sched_step(int64_t* step, float* lr_scale, int64_t t_total, float warmup, hipStream_t st) {
     XGGM_REQUIRE(step && lr_scale, "xggm_sched_step: null pointer");
-    hipLaunchKernelGGL(sched_kernel, dim3(1), dim3(64), 0, st, step, lr_scale, t_total, warmup);
+    SchedArgs a;
+    a.n = 1;
+    a.index[0] = 0;
+    a.t_total[0] = t_total;
+    a.warmup[0] = warmup;
+    hipLaunchKernelGGL(sched_multi_kernel, dim3(1), dim3(64), 0, st, step, lr_scale, a);
     return xggm_check_launch("xggm_sched_step");
 }
 
@@ -1227,127 +1195,25 @@ extern "C" int xggm_sched_step_ex(int64_t* steps, float* lr_scale, float* step_s
     return xggm_check_launch("xggm_sched_step_ex");
 }
 
-namespace {
-__global__ __launch_bounds__(NT) void clip_norm_finish_kernel(const float* __restrict__ ws, int nblk, float* out, float* norm, float mul,
-                                                              int64_t* steps, float* lr_scale, SchedArgs sa, uint64_t* rng,
-                                                              uint64_t rng_by, int accumulate) {
-    float t = 0.f;
-    for (int b = threadIdx.x; b < nblk; b += NT) t += ws[b];
-    t = block_sum(t);
-    if (threadIdx.x == 0) {
-        const float s = ((accumulate ? *out : 0.f) + t) * mul;
-        *out = s;
-        if (norm) *norm = sqrtf(s);
-        if (rng) rng[1] += rng_by;
-    }
-    const int i = threadIdx.x;
-    if (i < sa.n) {  // sched_multi_kernel's step
-        const int k = sa.index[i];
-        const int64_t s = steps[k];
-        float sc = 1.f;
-        if (sa.t_total[i] > 0) {
-            const float x = (float)((double)s / (double)sa.t_total[i]);
-            sc = x < sa.warmup[i] ? x / sa.warmup[i] : fmaxf((x - 1.f) / (sa.warmup[i] - 1.f), 0.f);
-        }
-        lr_scale[k] = sc;
-        steps[k] = s + 1;
-    }
-}
-}  // namespace
-
-namespace {
-struct TailArgs {
-    SchedArgs sa;
-    int64_t* steps = nullptr;
-    float* lr_scale = nullptr;
-    uint64_t* rng = nullptr;
-    uint64_t rng_by = 0;
-};
-int tail_args_of(const xggm_pass_tail* tail, TailArgs& ta) {
-    ta.sa.n = 0;
-    if (!tail) return XGGM_OK;
-    XGGM_REQUIRE(tail->n >= 0 && tail->n <= MAX_SCHED && (tail->n == 0 || (tail->steps && tail->lr_scale && tail->index &&
-                                                                         tail->t_total && tail->warmup)),
-                 "xggm_clip_norm: bad schedule entries (n = %d, at most %d)", tail->n, MAX_SCHED);
-    ta.sa.n = tail->n;
-    for (int i = 0; i < tail->n; ++i) {
-        XGGM_REQUIRE(tail->index[i] >= 0, "xggm_clip_norm: negative schedule index");
-        for (int j = 0; j < i; ++j)
-            XGGM_REQUIRE(tail->index[j] != tail->index[i], "xggm_clip_norm: counter %d listed twice", tail->index[i]);
-        ta.sa.index[i] = tail->index[i];
-        ta.sa.t_total[i] = tail->t_total[i];
-        ta.sa.warmup[i] = tail->warmup[i];
-    }
-    ta.steps = tail->steps;
-    ta.lr_scale = tail->lr_scale;
-    ta.rng = tail->rng;
-    ta.rng_by = tail->rng_by;
-    return XGGM_OK;
-}
-}  // namespace
-
 extern "C" int xggm_clip_norm_f32(const float* g, const int64_t* offsets, const int64_t* lengths, int n, const float* slots,
                                   const int64_t* slot_offsets, const int64_t* slot_lengths, int n_slots, float* out, float* norm,
                                   float* ws, float mul, const xggm_pass_tail* tail, hipStream_t st) {
-    XGGM_REQUIRE(out && ws && n >= 0 && n_slots >= 0 && n + n_slots <= MAX_NORM_SPANS && (n == 0 || (g && offsets && lengths)) &&
+    XGGM_REQUIRE(n >= 0 && n_slots >= 0 && n + n_slots <= MAX_NORM_SPANS && (n == 0 || (g && offsets && lengths)) &&
                      (n_slots == 0 || (slots && slot_offsets && slot_lengths)),
                  "xggm_clip_norm_f32: bad arguments (%d + %d ranges, at most %d in all)", n, n_slots, MAX_NORM_SPANS);
-    XGGM_REQUIRE((reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(slots)) % 16 == 0,
-                 "xggm_clip_norm_f32: buffers must be 16-byte aligned");
-    NormSpans sp;
-    sp.n = n + n_slots;
-    sp.n_sq = n;
-    int64_t total = 0;
-    for (int i = 0; i < sp.n; ++i) {
-        const int64_t o = i < n ? offsets[i] : slot_offsets[i - n], l = i < n ? lengths[i] : slot_lengths[i - n];
-        XGGM_REQUIRE(o >= 0 && l > 0 && o % 4 == 0, "xggm_clip_norm_f32: range %d (offset %lld, length %lld) must be non-empty and "
-                     "start on a multiple of 4", i, (long long)o, (long long)l);
-        sp.ptr[i] = (i < n ? g : slots) + o;
-        sp.len[i] = l;
-        total += l;
-    }
-    int nblk = 0;  // as xggm_sqnorm_multi_f32: <= 4096 + n partials, at least 8 float4 per thread where a range is long enough
-    for (int i = 0; i < sp.n; ++i) {
-        sp.blk0[i] = nblk;
-        nblk += (int)std::max<int64_t>(1, std::min<int64_t>(ceil_div64(sp.len[i], (int64_t)NT * 32), (4096 - sp.n) * sp.len[i] / total + 1));
-    }
-    sp.blk0[sp.n] = nblk;
-    XGGM_REQUIRE(nblk <= 4100, "xggm_clip_norm_f32: internal: %d partials", nblk);
-    TailArgs ta;
-    if (int e = tail_args_of(tail, ta)) return e;
-    if (nblk > 0) hipLaunchKernelGGL(clip_norm_kernel, dim3(nblk), dim3(NT), 0, st, sp, ws);
-    hipLaunchKernelGGL(clip_norm_finish_kernel, dim3(1), dim3(NT), 0, st, ws, nblk, out, norm, mul, ta.steps, ta.lr_scale, ta.sa, ta.rng, ta.rng_by, 0);
-    return xggm_check_launch("xggm_clip_norm_f32");
+    NormRange<float> r[MAX_NORM_SPANS];
+    for (int i = 0; i < n; ++i) r[i] = {g, offsets[i], lengths[i], true};
+    for (int i = 0; i < n_slots; ++i) r[n + i] = {slots, slot_offsets[i], slot_lengths[i], false};
+    return norm_of_ranges("xggm_clip_norm_f32", r, n + n_slots, out, norm, ws, 0, mul, tail, st);
 }
 
 extern "C" int xggm_clip_norm_bf16(const void* g, const int64_t* offsets, const int64_t* lengths, int n, float* out, float* norm,
                                    float* ws, int accumulate, float mul, const xggm_pass_tail* tail, hipStream_t st) {
-    XGGM_REQUIRE(out && ws && n >= 0 && n <= MAX_NORM_SPANS && (n == 0 || (g && offsets && lengths)),
+    XGGM_REQUIRE(n >= 0 && n <= MAX_NORM_SPANS && (n == 0 || (g && offsets && lengths)),
                  "xggm_clip_norm_bf16: bad arguments (%d ranges, at most %d)", n, MAX_NORM_SPANS);
-    XGGM_REQUIRE(reinterpret_cast<uintptr_t>(g) % 16 == 0, "xggm_clip_norm_bf16: the buffer must be 16-byte aligned");
-    NormSpans16 sp;
-    sp.n = n;
-    int64_t total = 0;
-    for (int i = 0; i < n; ++i) {
-        XGGM_REQUIRE(offsets[i] >= 0 && lengths[i] > 0 && offsets[i] % 8 == 0, "xggm_clip_norm_bf16: range %d (offset %lld, length "
-                     "%lld) must be non-empty and start on a multiple of 8", i, (long long)offsets[i], (long long)lengths[i]);
-        sp.ptr[i] = reinterpret_cast<const bf16*>(g) + offsets[i];
-        sp.len[i] = lengths[i];
-        total += lengths[i];
-    }
-    int nblk = 0;
-    for (int i = 0; i < n; ++i) {
-        sp.blk0[i] = nblk;
-        nblk += (int)std::max<int64_t>(1, std::min<int64_t>(ceil_div64(sp.len[i], (int64_t)NT * 64), (4096 - n) * sp.len[i] / total + 1));
-    }
-    sp.blk0[n] = nblk;
-    XGGM_REQUIRE(nblk <= 4100, "xggm_clip_norm_bf16: internal: %d partials", nblk);
-    TailArgs ta;
-    if (int e = tail_args_of(tail, ta)) return e;
-    if (nblk > 0) hipLaunchKernelGGL(clip_norm_bf16_kernel, dim3(nblk), dim3(NT), 0, st, sp, ws);
-    hipLaunchKernelGGL(clip_norm_finish_kernel, dim3(1), dim3(NT), 0, st, ws, nblk, out, norm, mul, ta.steps, ta.lr_scale, ta.sa, ta.rng, ta.rng_by,
-                       accumulate);
-    return xggm_check_launch("xggm_clip_norm_bf16");
+    NormRange<bf16> r[MAX_NORM_SPANS];
+    for (int i = 0; i < n; ++i) r[i] = {(const bf16*)g, offsets[i], lengths[i], true};
+    return norm_of_ranges("xggm_clip_norm_bf16", r, n, out, norm, ws, accumulate, mul, tail, st);
 }
 
 extern "C" int xggm_rng_advance(uint64_t* rng, uint64_t by, hipStream_t st) {

@@ -1632,13 +1632,25 @@ def zero_ranges(buf, ranges, rows=None):
 _SQNORM_WS = {}
 
 
+def _norm_ws(device):
+    """the device's XGGM_SQNORM_WS_FLOATS floats of scratch for the norm entries' partial sums (xggm.h)"""
+    ws = _SQNORM_WS.get(device)
+    if ws is None:
+        ws = _SQNORM_WS[device] = torch.zeros(4100, device=device, dtype=F32)
+    return ptr(ws)
+
+
+def _span_arrays(spans):
+    """(offsets, lengths) of [(start, end)] as host int64 arrays, as pointers (never empty arrays)"""
+    n = max(len(spans), 1)
+    return (_ct.cast((_ct.c_int64 * n)(*[s for s, _ in spans]), _ct.c_void_p),
+            _ct.cast((_ct.c_int64 * n)(*[e - s for s, e in spans]), _ct.c_void_p))
+
+
 def sqnorm(g, out):
     """out += sum g^2 (fixed summation order: see xggm.h)."""
     _c(g, F32), _c(out, F32)
-    ws = _SQNORM_WS.get(g.device)
-    if ws is None:  # zeroed once; the kernel leaves its arrival counter at zero
-        ws = _SQNORM_WS[g.device] = torch.zeros(4100, device=g.device, dtype=F32)
-    call("xggm_sqnorm_f32", ptr(g), g.numel(), ptr(out), ptr(ws), stream())
+    call("xggm_sqnorm_f32", ptr(g), g.numel(), ptr(out), _norm_ws(g.device), stream())
 
 
 def sqnorm_multi(buf, spans, out, norm=None, overwrite=True, square=True, mul=1.0):
@@ -1648,17 +1660,13 @@ def sqnorm_multi(buf, spans, out, norm=None, overwrite=True, square=True, mul=1.
     _c(buf, F32), _c(out, F32)
     if norm is not None:
         _c(norm, F32)
-    ws = _SQNORM_WS.get(buf.device)
-    if ws is None:
-        ws = _SQNORM_WS[buf.device] = torch.zeros(4100, device=buf.device, dtype=F32)
     rs = [(s, e) for s, e in spans if e > s]
     chunks = [rs[i:i + 16] for i in range(0, len(rs), 16)] or [[]]
     for ci, ch in enumerate(chunks):
-        offs = (_ct.c_int64 * max(len(ch), 1))(*[s for s, _ in ch])
-        lens = (_ct.c_int64 * max(len(ch), 1))(*[e - s for s, e in ch])
+        offs, lens = _span_arrays(ch)
         last = ci == len(chunks) - 1
-        call("xggm_sqnorm_multi_f32", ptr(buf), _ct.cast(offs, _ct.c_void_p), _ct.cast(lens, _ct.c_void_p), len(ch), ptr(out),
-             ptr(norm) if last else None, ptr(ws), int(overwrite and ci == 0), int(square), float(mul) if last else 1.0, stream())
+        call("xggm_sqnorm_multi_f32", ptr(buf), offs, lens, len(ch), ptr(out), ptr(norm) if last else None,
+             _norm_ws(buf.device), int(overwrite and ci == 0), int(square), float(mul) if last else 1.0, stream())
 
 
 class FpSpan(_ct.Structure):
@@ -1847,15 +1855,10 @@ def clip_norm_bf16(g, spans, out, norm=None, accumulate=False, mul=1.0, sched=No
     _c(g, BF16), _c(out, F32)
     rs = [(s, e) for s, e in spans if e > s]
     assert len(rs) <= CLIP_NORM_MAX_SPANS
-    ws = _SQNORM_WS.get(g.device)
-    if ws is None:
-        ws = _SQNORM_WS[g.device] = torch.zeros(4100, device=g.device, dtype=F32)
-    offs = (_ct.c_int64 * max(len(rs), 1))(*[s for s, _ in rs])
-    lens = (_ct.c_int64 * max(len(rs), 1))(*[e - s for s, e in rs])
+    offs, lens = _span_arrays(rs)
     tail, keep = _pass_tail(sched, rng)
-    call("xggm_clip_norm_bf16", ptr(g), _ct.cast(offs, _ct.c_void_p), _ct.cast(lens, _ct.c_void_p), len(rs), ptr(out),
-         ptr(norm) if norm is not None else None, ptr(ws), int(accumulate), float(mul),
-         _ct.byref(tail) if tail is not None else None, stream())
+    call("xggm_clip_norm_bf16", ptr(g), offs, lens, len(rs), ptr(out), ptr(norm) if norm is not None else None,
+         _norm_ws(g.device), int(accumulate), float(mul), _ct.byref(tail) if tail is not None else None, stream())
 
 
 def clip_norm(g, spans, slots, slot_spans, out, norm=None, mul=1.0, sched=None, rng=None):
@@ -1869,19 +1872,12 @@ def clip_norm(g, spans, slots, slot_spans, out, norm=None, mul=1.0, sched=None, 
     assert len(rs) + len(ss) <= CLIP_NORM_MAX_SPANS
     if ss:
         _c(slots, F32)
-    ws = _SQNORM_WS.get(g.device)
-    if ws is None:
-        ws = _SQNORM_WS[g.device] = torch.zeros(4100, device=g.device, dtype=F32)
-
-    def arrs(r):
-        return ((_ct.c_int64 * max(len(r), 1))(*[s for s, _ in r]), (_ct.c_int64 * max(len(r), 1))(*[e - s for s, e in r]))
-
-    o1, l1 = arrs(rs)
-    o2, l2 = arrs(ss)
+    o1, l1 = _span_arrays(rs)
+    o2, l2 = _span_arrays(ss)
     tail, keep = _pass_tail(sched, rng)
-    call("xggm_clip_norm_f32", ptr(g), _ct.cast(o1, _ct.c_void_p), _ct.cast(l1, _ct.c_void_p), len(rs),
-         ptr(slots) if ss else None, _ct.cast(o2, _ct.c_void_p), _ct.cast(l2, _ct.c_void_p), len(ss), ptr(out),
-         ptr(norm) if norm is not None else None, ptr(ws), float(mul), _ct.byref(tail) if tail is not None else None, stream())
+    call("xggm_clip_norm_f32", ptr(g), o1, l1, len(rs), ptr(slots) if ss else None, o2, l2, len(ss), ptr(out),
+         ptr(norm) if norm is not None else None, _norm_ws(g.device), float(mul),
+         _ct.byref(tail) if tail is not None else None, stream())
 
 
 def additive_mask(mask):
@@ -2094,11 +2090,9 @@ def _adam_args(p, g, m, v, shadow, sqn, max_norm, lr, lr_scale, b1, b2, eps, wd,
 
 
 def sqnorm_bf16(g, out):
+    """out += sum g^2 of a bf16 tensor, as ``sqnorm``"""
     _c(g, BF16), _c(out, F32)
-    ws = _SQNORM_WS.get(g.device)
-    if ws is None:
-        ws = _SQNORM_WS[g.device] = torch.zeros(4100, device=g.device, dtype=F32)
-    call("xggm_sqnorm_bf16", ptr(g), g.numel(), ptr(out), ptr(ws), stream())
+    call("xggm_sqnorm_bf16", ptr(g), g.numel(), ptr(out), _norm_ws(g.device), stream())
 
 
 def fp8_scale_update(amax, hist, qscale, dscale, pos, i0, n, hist_len, margin, shrink, bump, slots=1):
