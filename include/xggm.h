@@ -927,6 +927,93 @@ typedef struct xggm_batch_gather_args {
 } xggm_batch_gather_args;
 int xggm_batch_gather(const xggm_batch_gather_args* args, xggm_stream_t stream);
 
+/* xggm_pretrain_gather: a CLEAN pre-training batch assembled from a corpus that is RESIDENT on the device, with the
+ * matched-sentence swap fused in, in ONE launch.  It replaces what LXMERTTorchDataset.__getitem__ does per example on the
+ * host (src/pretrain/lxmert_data.py:148-199: look the image up, copy its features, boxes, object / attribute labels and
+ * confidences, swap the sentence with probability 0.5, build the answer dict) plus the collation and the copies of the
+ * batch.  Output row b (0 <= b < B) is built from sample s = order[start + b]; r = q_row[s] is its image, stored once
+ * however many sentences refer to it.
+ * Tables (device, only read):
+ *   per image   feats [n_img, O, F] bf16 bit patterns, or fp32 when feats_f32;  boxes [n_img, O, 4] f32 (already
+ *               normalised);  obj_labels, attr_labels [n_img, O] int32;  obj_confs, attr_confs [n_img, O] f32;
+ *   per sample  q_row [n_q] int32;  q_ids [n_q, T] int32 ([CLS] tokens [SEP], zero behind the sentence);  q_len [n_q] int32
+ *               (tokens, [CLS] / [SEP] included);  q_label [n_q, K] int32 (the keys of example.label in insertion order, -1
+ *               padded: the order matters to the answer draw of xggm_pretrain_corrupt_*);  q_score [n_q, K] f32.
+ * Selection: order [n] int64 on the device, read at run time; start and B are host values.
+ * Outputs (device) -- the clean batch xggm_pretrain_corrupt_* takes, plus img_ids:
+ *   out_feats   row b at out_feats + b * out_feats_stride ELEMENTS, bf16 or fp32 (out_f32) <- feats[r], the four type pairs
+ *               exactly as in xggm_batch_gather (same type: the bits; fp32 -> bf16: torch's rounding; bf16 -> fp32: << 16);
+ *   out_boxes [B, O, 4] f32 <- boxes[r];  out_obj_labels, out_attr_labels int64 [B, O] (widened);  out_obj_confs,
+ *   out_attr_confs f32 [B, O];
+ *   input_ids, input_mask, segment_ids  int64 [B, T]: q_ids[j], (t < q_len[j]), 0 with j = s unless the row swapped (below);
+ *   label_ids int64 [B, K] <- q_label[s] (widened, -1 kept);  label_scores f32 [B, K] <- q_score[s];
+ *   is_matched int64 [B];  img_ids int64 [B] <- r;  sample int64 [B] or NULL <- s;
+ *   swapped_from int64 [B] or NULL: the sample whose sentence row b carries, -1 when it is its own.
+ *   Labels, features and img_ids always belong to s: only the sentence can come from elsewhere (:178-183).
+ * The fused swap is the rule and the draw streams of xggm_pretrain_swap, unchanged; its pool is EVERY sample of the store
+ * (the reference: "a random datum of the data set", :180) and its image key is q_row:
+ *   swap == 0: no draw is read, is_matched[b] = 1, rng may be NULL;
+ *   else (double)u_swap[b] < rate false: the row keeps its sentence, is_matched[b] = 1;
+ *   else for r = 0 .. XGGM_PRETRAIN_SWAP_TRIES - 1: j = min(floor((double)u_pick[b, r] * n_q), n_q - 1) (a pick below 0 is
+ *        held at 0); the FIRST j with q_row[j] != q_row[s] supplies q_ids[j] and q_len[j], is_matched[b] = 0;
+ *   no candidate qualifies: the row stays matched and *exhausted += 1 (one vector integer atomic add per such row).
+ *   A NULL draw buffer means philox_uniform(seed, offset, sid_base + 5, b) resp. (..., sid_base + 6, b * TRIES + r) with
+ *   {seed, offset} = rng[0..1]; rng is only read.  The decision of a row is taken by one workgroup from wave-uniform values.
+ * Grid (roles, B) as xggm_batch_gather: role 0 of a row takes the decision and writes every small field, roles 1 .. move
+ * the feature row as 16-byte vectors (F % 8 == 0, 16-byte aligned bases, a row stride that is a multiple of 8 elements); a
+ * box is one 16-byte vector.  Rows of T, O or K elements need not be multiples of 16 bytes: they move element by element
+ * inside their own bounds, no vector straddles a row end.  Every output element has one writer; nothing is written outside
+ * rows 0 .. B - 1 of an output, nor between two rows where the stride exceeds the row.  One launch; nothing is allocated,
+ * copied or synchronised, so the call can be captured in a graph (order, rng and the draws are read at run time).
+ * The kernel TRUSTS order[i] in [0, n_q), q_row in [0, n_img) and q_len in [0, T]: the caller validates them once, when
+ * the tables are uploaded.
+ * Refused before any launch: a null struct; a null or misaligned required pointer (feats, boxes tables and outputs: 16
+ * bytes; the other fields: their element size; only sample and swapped_from may be NULL -- an output whose table is NULL is
+ * refused); B < 1 (or > 65535); start < 0 or start + B > n; T, K, O, F, n_img or n_q < 1; F % 8 != 0; a feature row stride
+ * below the row or no multiple of 8; swap with rate outside [0, 1], with NULL exhausted, or with a NULL draw buffer and
+ * NULL rng; an output overlapping a table, order, rng, a draw buffer or another output. */
+typedef struct xggm_pretrain_gather_args {
+    const void* feats;             /* [n_img, O, F] bf16 bits or fp32 */
+    const float* boxes;            /* [n_img, O, 4] */
+    const int32_t* obj_labels;     /* [n_img, O] */
+    const int32_t* attr_labels;    /* [n_img, O] */
+    const float* obj_confs;        /* [n_img, O] */
+    const float* attr_confs;       /* [n_img, O] */
+    const int32_t* q_row;          /* [n_q] */
+    const int32_t* q_ids;          /* [n_q, T] */
+    const int32_t* q_len;          /* [n_q] */
+    const int32_t* q_label;        /* [n_q, K] */
+    const float* q_score;          /* [n_q, K] */
+    const int64_t* order;          /* [n] */
+    int64_t n_img, n_q, n, start;
+    void* out_feats;
+    int64_t out_feats_stride;      /* elements between two rows */
+    float* out_boxes;              /* [B, O, 4] */
+    int64_t* out_obj_labels;       /* [B, O] */
+    int64_t* out_attr_labels;      /* [B, O] */
+    float* out_obj_confs;          /* [B, O] */
+    float* out_attr_confs;         /* [B, O] */
+    int64_t* input_ids;            /* [B, T] */
+    int64_t* input_mask;           /* [B, T] */
+    int64_t* segment_ids;          /* [B, T] */
+    int64_t* label_ids;            /* [B, K] */
+    float* label_scores;           /* [B, K] */
+    int64_t* is_matched;           /* [B] */
+    int64_t* img_ids;              /* [B] */
+    int64_t* sample;               /* [B] or NULL */
+    int64_t* swapped_from;         /* [B] or NULL */
+    int B, T, K, O, F;
+    int feats_f32, out_f32;
+    int swap;                      /* 0: no swap, no draw is read */
+    double rate;
+    const float* u_swap;           /* [B] or NULL */
+    const float* u_pick;           /* [B, TRIES] or NULL */
+    const uint64_t* rng;           /* {seed, offset}; needed when swap and a draw buffer is NULL */
+    uint32_t sid_base;
+    int32_t* exhausted;            /* [1] in/out; needed when swap */
+} xggm_pretrain_gather_args;
+int xggm_pretrain_gather(const xggm_pretrain_gather_args* args, xggm_stream_t stream);
+
 /* ---- preprocessing that feeds the path ----------------------------------------------------
  * adj_true of every sample: data/preprocess/vqa/compute_adjacency.py:38-45 (compute_cosin_sim_v2) + :90.
  *   c[i][j] = cos(cls[i], attr[j]) for j >= i, 0 below the diagonal  (torch.cosine_similarity, eps 1e-6: each

@@ -7,65 +7,13 @@
 // load or store on the bf16 side and two on the fp32 side.  Every output element has one writer (the target row: one
 // workgroup, ordered by its barrier); nothing is accumulated, so there are no atomics.
 #include "common.h"
+#include "feat_move.h"
 #include "xggm.h"
 
 namespace {
-constexpr int NT = 256;
-constexpr int RUNS = 4;  // 8-element runs per lane: four independent 16-byte loads in flight
-typedef unsigned int u4 __attribute__((ext_vector_type(4)));
-
-// the bits of torch's fp32 -> bf16 conversion (c10::detail::round_to_nearest_even): ties to even, a carry out of the
-// mantissa moves into the exponent (the largest finite values become inf), NaN becomes the quiet NaN 0x7FC0
-__device__ __forceinline__ unsigned bf16_bits(unsigned u) {
-    if ((u & 0x7fffffffu) > 0x7f800000u) return 0x7fc0u;
-    return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
-}
-__device__ __forceinline__ unsigned pack2(unsigned lo, unsigned hi) { return bf16_bits(lo) | (bf16_bits(hi) << 16); }
-
-template <bool IN32, bool OUT32>
-__device__ __forceinline__ void move_feats(const xggm_batch_gather_args& a, int64_t row, int64_t b, int chunk) {
-    const int64_t runs = (int64_t)a.N * a.F / 8;  // F % 8 == 0: a row is a whole number of runs
-    const int64_t r0 = (int64_t)chunk * (NT * RUNS) + threadIdx.x;
-    const u4* src = reinterpret_cast<const u4*>(a.feats) + row * runs * (IN32 ? 2 : 1);
-    u4* dst = reinterpret_cast<u4*>(reinterpret_cast<char*>(a.out_feats) + b * a.out_feats_stride * (OUT32 ? 4 : 2));
-    u4 lo[RUNS], hi[RUNS];
-#pragma unroll
-    for (int u = 0; u < RUNS; ++u) {
-        const int64_t r = r0 + u * NT;
-        if (r < runs) {
-            if (IN32) {
-                lo[u] = src[2 * r];
-                hi[u] = src[2 * r + 1];
-            } else {
-                lo[u] = src[r];
-            }
-        }
-    }
-#pragma unroll
-    for (int u = 0; u < RUNS; ++u) {
-        const int64_t r = r0 + u * NT;
-        if (r >= runs) continue;
-        if (IN32 == OUT32) {
-            if (IN32) {
-                dst[2 * r] = lo[u];
-                dst[2 * r + 1] = hi[u];
-            } else {
-                dst[r] = lo[u];
-            }
-        } else if (IN32) {  // eight fp32 -> eight bf16
-            u4 o;
-            o.x = pack2(lo[u].x, lo[u].y);
-            o.y = pack2(lo[u].z, lo[u].w);
-            o.z = pack2(hi[u].x, hi[u].y);
-            o.w = pack2(hi[u].z, hi[u].w);
-            dst[r] = o;
-        } else {  // eight bf16 -> eight fp32: bits << 16
-            const u4 v = lo[u];
-            dst[2 * r] = (u4){v.x << 16, v.x & 0xffff0000u, v.y << 16, v.y & 0xffff0000u};
-            dst[2 * r + 1] = (u4){v.z << 16, v.z & 0xffff0000u, v.w << 16, v.w & 0xffff0000u};
-        }
-    }
-}
+using feat_move::NT;
+using feat_move::RUNS;
+using feat_move::u4;
 
 __global__ __launch_bounds__(NT) void batch_gather_kernel(const xggm_batch_gather_args a, const int adj_vec) {
     const int64_t b = blockIdx.y;
@@ -73,13 +21,10 @@ __global__ __launch_bounds__(NT) void batch_gather_kernel(const xggm_batch_gathe
     const int role = blockIdx.x, tid = threadIdx.x;
     if (role >= 2) {
         const int64_t row = a.q_row[s];
-        if (a.feats_f32) {
-            if (a.out_f32) move_feats<true, true>(a, row, b, role - 2);
-            else move_feats<true, false>(a, row, b, role - 2);
-        } else {
-            if (a.out_f32) move_feats<false, true>(a, row, b, role - 2);
-            else move_feats<false, false>(a, row, b, role - 2);
-        }
+        const int64_t runs = (int64_t)a.N * a.F / 8;  // F % 8 == 0: a row is a whole number of runs
+        feat_move::move_row_any(a.feats_f32, a.out_f32,
+                                reinterpret_cast<const char*>(a.feats) + row * runs * (a.feats_f32 ? 32 : 16),
+                                reinterpret_cast<char*>(a.out_feats) + b * a.out_feats_stride * (a.out_f32 ? 4 : 2), runs, role - 2);
         return;
     }
     if (role == 1) {

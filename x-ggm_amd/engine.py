@@ -722,6 +722,9 @@ class CapturedPretrainer:
     obj_confs, attr_labels, attr_confs, is_matched, label_ids, label_scores (``pretrain.lxmert_pretrain.pack_labels``) and,
     with a swap (``features.match_rate``), img_ids and optionally pool_ids / pool_mask / pool_img; optionally feat_pool (the
     replacement rows of the object masking).  They become the static input buffers; ``load_batch`` copies into them.
+    ``resident=store`` (``pretrain.resident.ResidentPretrainSet``): ``static["feat_pool"]`` is the store's whole feature table
+    by reference (not cloned; refused when its dtype is not that of ``feats``), and ``load_resident(store, start)`` fills the
+    static inputs with one gather launch instead of ``load_batch``.
 
     ``step()`` holds, in order: the swap (when configured) and the masking (``features``: one or two launches),
     ``LXRTPretraining.forward``, ``Runtime.backward``, ``clip_and_step(model, optim, clip, advance=True)`` (the reference
@@ -753,7 +756,7 @@ class CapturedPretrainer:
     POOL = ("pool_ids", "pool_mask", "pool_img")
 
     def __init__(self, model, optim, batch, features, clip=1.0, use_graph=True, warmup_iters=2, train_log=None,
-                 valid_log=None, answer_log=None):
+                 valid_log=None, answer_log=None, resident=None):
         from . import trainlog as T
         from .lxrt.modeling import VISUAL_CONFIG
         self.model, self.optim, self.features, self.clip = model, optim, features, clip
@@ -771,6 +774,14 @@ class CapturedPretrainer:
             raise ValueError("CapturedPretrainer: a validation-only engine (optim=None) appends to no train_log")
         self.static = {k: v.clone() for k, v in batch.items() if torch.is_tensor(v)}
         self.B = self.static["input_ids"].shape[0]
+        if resident is not None:
+            # every object of every image of the store, by reference: the pool torchdset.random_feat() draws from
+            pool = resident.feat_pool()
+            if pool.dtype != self.static["feats"].dtype:
+                raise ValueError("CapturedPretrainer: resident= hands the store's %s feature table to the object masking as its "
+                                 "pool, the batch's feats are %s; build the batch in the store's type (store.buffers(B))"
+                                 % (pool.dtype, self.static["feats"].dtype))
+            self.static["feat_pool"] = pool
         self.rt = runtime_of(model)
         cols = [T.PT_MASK_LM] if model.task_mask_lm else []
         cols += [T.PT_MATCHED] if model.task_matched else []
@@ -884,6 +895,22 @@ class CapturedPretrainer:
         for k, v in batch.items():
             if k in self.static:
                 self.static[k].copy_(v, non_blocking=True)
+
+    def load_resident(self, store, start):
+        """hand over rows ``start .. start + B`` of the epoch order of ``store`` (pretrain.resident.ResidentPretrainSet): ONE
+        gather launch out of the device-resident tables into the static inputs (and img_ids / sample where the static batch
+        has them), eagerly and in stream order between the replays, where ``load_batch`` would copy -- nothing crosses PCIe
+        and no graph is captured again.  A store with a ``match_rate`` swaps in that launch, drawing from the model's
+        runtime state ``rng`` at ``features.sid_base`` -- the state the step that follows masks with, so the swap moves with
+        the ONE advance per step, and a captured, an eager and a restored run give the same bits.  ``features`` must then
+        not swap itself."""
+        if getattr(store, "match_rate", None) is not None and self.features.match_rate is not None:
+            raise ValueError("CapturedPretrainer.load_resident: the store swaps (match_rate %g) and so does features (match_rate "
+                             "%g): the batch would be swapped twice; build DeviceFeatures without a match_rate"
+                             % (store.match_rate, self.features.match_rate))
+        if "img_ids" not in self.static:  # the launch writes it; a batch without a swap of its own came without one
+            self.static["img_ids"] = torch.zeros(self.B, dtype=torch.int64, device=self.static["input_ids"].device)
+        store.fill(self.static, start, self.B, rng=runtime_of(self.model).rng, sid_base=self.features.sid_base)
 
     def _run(self, kind, batch):
         if kind == "train" and self.optim is None:

@@ -2379,10 +2379,10 @@ class BatchGatherArgs(_ct.Structure):
                 ("A", _ct.c_int), ("N", _ct.c_int), ("F", _ct.c_int), ("feats_f32", _ct.c_int), ("out_f32", _ct.c_int)]
 
 
-def _rows_of(t, B, row, name):
+def _rows_of(t, B, row, name, who="batch_gather"):
     """``t``: at least B rows of shape ``row`` whose insides are contiguous (the row stride is free) -> row stride"""
     if t.dim() != 1 + len(row) or tuple(t.shape[1:]) != tuple(row) or t.shape[0] < B:
-        raise ValueError("batch_gather: %s is %s, at least [%d, %s] expected" % (name, tuple(t.shape), B, ", ".join(map(str, row))))
+        raise ValueError("%s: %s is %s, at least [%d, %s] expected" % (who, name, tuple(t.shape), B, ", ".join(map(str, row))))
     if not t[0].is_contiguous():
         raise RuntimeError("xggm_amd: the rows of %s must be contiguous" % name)
     return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t[0].numel())
@@ -2465,6 +2465,123 @@ def batch_gather(tables, order, start, B, out):
     a.B, a.T, a.K, a.N, a.F = B, T, K, N, F
     a.feats_f32, a.out_f32 = int(feats.dtype == F32), int(of.dtype == F32)
     call("xggm_batch_gather", _ct.addressof(a), stream())
+    return out
+
+
+class PretrainGatherArgs(_ct.Structure):
+    """mirror of ``xggm_pretrain_gather_args`` (include/xggm.h)"""
+    _fields_ = ([(k, _ct.c_void_p) for k in ("feats", "boxes", "obj_labels", "attr_labels", "obj_confs", "attr_confs", "q_row",
+                                             "q_ids", "q_len", "q_label", "q_score", "order")]
+                + [(k, _ct.c_int64) for k in ("n_img", "n_q", "n", "start")]
+                + [("out_feats", _ct.c_void_p), ("out_feats_stride", _ct.c_int64)]
+                + [(k, _ct.c_void_p) for k in ("out_boxes", "out_obj_labels", "out_attr_labels", "out_obj_confs", "out_attr_confs",
+                                               "input_ids", "input_mask", "segment_ids", "label_ids", "label_scores", "is_matched",
+                                               "img_ids", "sample", "swapped_from")]
+                + [(k, _ct.c_int) for k in ("B", "T", "K", "O", "F", "feats_f32", "out_f32", "swap")]
+                + [("rate", _ct.c_double), ("u_swap", _ct.c_void_p), ("u_pick", _ct.c_void_p), ("rng", _ct.c_void_p),
+                   ("sid_base", _ct.c_uint32), ("exhausted", _ct.c_void_p)])
+
+
+PRETRAIN_GATHER_TABLES = ("feats", "boxes", "obj_labels", "attr_labels", "obj_confs", "attr_confs", "q_row", "q_ids", "q_len",
+                          "q_label", "q_score")
+# the clean batch of ``engine.CapturedPretrainer.KEYS`` plus img_ids; sample and swapped_from are optional
+PRETRAIN_GATHER_OUT = ("input_ids", "input_mask", "segment_ids", "feats", "boxes", "obj_labels", "obj_confs", "attr_labels",
+                       "attr_confs", "is_matched", "label_ids", "label_scores", "img_ids")
+
+
+def pretrain_gather(tables, order, start, B, out, match_rate=None, rng=None, sid_base=0, draws=None, exhausted=None):
+    """rows ``order[start : start + B]`` of a device-resident pre-training corpus into the clean batch buffers ``out``, the
+    matched-sentence swap fused in, one launch; contract: xggm_pretrain_gather in xggm.h.  ``tables``
+    (``PRETRAIN_GATHER_TABLES``): feats [n_img, O, F] bf16 / fp32, boxes [n_img, O, 4], obj_labels / attr_labels [n_img, O]
+    int32, obj_confs / attr_confs [n_img, O] fp32, q_row [n_q] int32, q_ids [n_q, T] int32, q_len [n_q] int32, q_label
+    [n_q, K] int32, q_score [n_q, K] fp32.  ``order``: [n] int64.  ``out``: every name of ``PRETRAIN_GATHER_OUT`` (feats bf16 /
+    fp32 with a free row stride) and optionally sample, swapped_from; each with at least B rows, rows past B are not touched.
+    ``match_rate`` (None: no swap, no draw is read): a row swaps iff its u_swap < match_rate and then takes the sentence of
+    the first of ``PRETRAIN_SWAP_TRIES`` candidates of another image out of ALL samples of the tables.  ``draws``: a dict with
+    any of ``PRETRAIN_SWAP_DRAWS`` (fp32; u_swap [B], u_pick [B, 8]); a missing one is drawn from ``rng`` at stream
+    ``sid_base + 5`` / ``+ 6``.  ``exhausted``: int32 [1], added to (needed with a swap).  The indices inside the tables are
+    trusted (``pretrain.resident.pretrain_tables`` validates them once); every shape is checked here."""
+    who = "pretrain_gather"
+    tb, dev = tables, order.device
+    missing = [k for k in PRETRAIN_GATHER_TABLES if tb.get(k) is None]
+    if missing:
+        raise ValueError("%s: the tables lack %s" % (who, missing))
+    _c(order, torch.int64, "order")
+    feats = _c(tb["feats"], None, "table feats")
+    if feats.dtype not in (BF16, F32) or feats.dim() != 3:
+        raise TypeError("%s: feature table %s %s, [n_img, O, F] bfloat16 or float32 expected" % (who, tuple(feats.shape), feats.dtype))
+    n_img, O, F = feats.shape
+    for k, dt in (("boxes", F32), ("obj_labels", torch.int32), ("attr_labels", torch.int32), ("obj_confs", F32), ("attr_confs", F32),
+                  ("q_row", torch.int32), ("q_ids", torch.int32), ("q_len", torch.int32), ("q_label", torch.int32), ("q_score", F32)):
+        _c(tb[k], dt, "table " + k)
+    n_q = tb["q_row"].numel()
+    if tb["q_ids"].dim() != 2 or tb["q_label"].dim() != 2:
+        raise ValueError("%s: q_ids [n_q, T] and q_label [n_q, K] expected" % who)
+    T, K = tb["q_ids"].shape[1], tb["q_label"].shape[1]
+    if (tuple(tb["boxes"].shape) != (n_img, O, 4) or any(tuple(tb[k].shape) != (n_img, O) for k in ("obj_labels", "attr_labels", "obj_confs", "attr_confs"))
+            or tb["q_row"].dim() != 1 or tb["q_ids"].shape[0] != n_q or tuple(tb["q_len"].shape) != (n_q,)
+            or tb["q_label"].shape[0] != n_q or tuple(tb["q_score"].shape) != (n_q, K)):
+        raise ValueError("%s: the tables do not fit n_img=%d O=%d n_q=%d T=%d K=%d" % (who, n_img, O, n_q, T, K))
+    if min(n_img, n_q, O, F, T, K) < 1:
+        raise ValueError("%s: empty tables" % who)
+    if F % 8:
+        raise ValueError("%s: F=%d is no multiple of 8 (feature rows move 16 bytes per lane)" % (who, F))
+    start, B, n = int(start), int(B), order.numel()
+    if order.dim() != 1 or B < 1 or start < 0 or start + B > n:
+        raise ValueError("%s: rows %d .. %d of an order of %d" % (who, start, start + B, n))
+    unknown = set(out) - set(PRETRAIN_GATHER_OUT) - {"sample", "swapped_from"}
+    lacking = [k for k in PRETRAIN_GATHER_OUT if out.get(k) is None]
+    if unknown or lacking:
+        raise ValueError("%s: unknown outputs %s, missing outputs %s" % (who, sorted(unknown), lacking))
+    a = PretrainGatherArgs()
+    of = _chk(out["feats"], None, "out feats")
+    if of.dtype not in (BF16, F32):
+        raise TypeError("%s: out feats %s, bfloat16 or float32 expected" % (who, of.dtype))
+    a.out_feats_stride = _rows_of(of, B, (O, F), "out feats", who)
+    for k, dt, row in (("boxes", F32, (O, 4)), ("obj_labels", torch.int64, (O,)), ("attr_labels", torch.int64, (O,)),
+                       ("obj_confs", F32, (O,)), ("attr_confs", F32, (O,)), ("input_ids", torch.int64, (T,)),
+                       ("input_mask", torch.int64, (T,)), ("segment_ids", torch.int64, (T,)), ("label_ids", torch.int64, (K,)),
+                       ("label_scores", F32, (K,)), ("is_matched", torch.int64, ()), ("img_ids", torch.int64, ()),
+                       ("sample", torch.int64, ()), ("swapped_from", torch.int64, ())):
+        if out.get(k) is not None:
+            _rows_of(_c(out[k], dt, "out " + k), B, row, "out " + k, who)
+    draws = dict(draws or {})
+    sizes = dict(u_swap=B, u_pick=B * PRETRAIN_SWAP_TRIES)
+    if set(draws) - set(sizes):
+        raise ValueError("%s: unknown draws %s" % (who, sorted(set(draws) - set(sizes))))
+    if match_rate is None:
+        if draws:
+            raise ValueError("%s: swap draws %s without a match_rate" % (who, sorted(draws)))
+    else:
+        if not 0.0 <= float(match_rate) <= 1.0:
+            raise ValueError("%s: match_rate %r outside [0, 1]" % (who, match_rate))
+        for k, m in sizes.items():
+            d = draws.get(k)
+            if d is not None and _c(d, F32, k).numel() != m:
+                raise ValueError("%s: %s has %d draws, %d expected" % (who, k, d.numel(), m))
+            setattr(a, k, ptr(d))
+        if rng is None:
+            if any(draws.get(k) is None for k in sizes):
+                raise ValueError("%s: a missing draw buffer needs rng" % who)
+        else:
+            _c(rng, torch.int64, "rng")
+        if exhausted is None or _c(exhausted, torch.int32, "exhausted").numel() != 1:
+            raise ValueError("%s: a swap needs exhausted, int32 [1]" % who)
+        a.swap, a.rate, a.rng, a.exhausted = 1, float(match_rate), ptr(rng), ptr(exhausted)
+    for t in [tb[k] for k in PRETRAIN_GATHER_TABLES] + list(out.values()) + list(draws.values()) + [rng, exhausted]:
+        if t is not None and t.device != dev:
+            raise RuntimeError("%s: all operands must live on one device" % who)
+    for k in PRETRAIN_GATHER_TABLES + ("order",):
+        setattr(a, k, ptr(order if k == "order" else tb[k]))
+    a.n_img, a.n_q, a.n, a.start = n_img, n_q, n, start
+    a.out_feats, a.out_boxes = ptr(of), ptr(out["boxes"])
+    a.out_obj_labels, a.out_attr_labels = ptr(out["obj_labels"]), ptr(out["attr_labels"])
+    a.out_obj_confs, a.out_attr_confs = ptr(out["obj_confs"]), ptr(out["attr_confs"])
+    for k in ("input_ids", "input_mask", "segment_ids", "label_ids", "label_scores", "is_matched", "img_ids", "sample", "swapped_from"):
+        setattr(a, k, ptr(out.get(k)))
+    a.B, a.T, a.K, a.O, a.F = B, T, K, O, F
+    a.feats_f32, a.out_f32, a.sid_base = int(feats.dtype == F32), int(of.dtype == F32), int(sid_base)
+    call("xggm_pretrain_gather", _ct.addressof(a), stream())
     return out
 
 

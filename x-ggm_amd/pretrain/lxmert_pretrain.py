@@ -12,7 +12,8 @@ them by explicit buffers (tests pin the kernel to the reference's functions that
 
 Deviations from the reference, both documented in INTEGRATION.md:
   * the random replacement row comes from ``pool`` [P, F] (default: the batch's own clean features as [B O, F]) instead of
-    ``torchdset.random_feat()``, a random object of a random datum of the whole data set; a loader can pass a larger pool;
+    ``torchdset.random_feat()``, a random object of a random datum of the whole data set; a loader can pass a larger pool,
+    and a resident corpus (``pretrain.resident.ResidentPretrainSet``) passes every object of every image;
   * an example with several answer keys draws by inverse CDF on one uniform instead of ``np.random.multinomial``: the same
     distribution, not the same stream.
 
@@ -24,10 +25,14 @@ Its two deviations (a bounded number of candidates, ``randint`` as floor(u n)) a
 The driver loop is at the bottom: ``InputExample``, ``collate_examples`` and ``LXMERT``, our own code behind the names and
 signatures of ``class LXMERT`` (src/pretrain/lxmert_pretrain.py:221-409), running on ``engine.CapturedPretrainer``.
 
+The batch itself can come from the device: ``pretrain.resident.ResidentPretrainSet`` keeps a corpus of ``InputExample``s in
+HBM and one launch gathers a clean batch with the swap fused in -- drawn from EVERY sample, as the reference draws -- in
+place of ``collate_examples`` and thirteen copies; ``LXMERT(resident=True)`` takes such a store as the loader of a tuple.
+
 Out of scope here: the data-set readers and the evaluator of src/pretrain/lxmert_data.py (``LXMERTDataset``,
 ``LXMERTTorchDataset``, ``LXMERTEvaluator``: the data files are absent offline; any ``(dataset, loader, evaluator)`` whose
-loader yields lists of ``InputExample`` serves), data-parallel pre-training, the packed loader ring of the fine-tuning
-side, and fusing the masking into the visual-embedding product's input read."""
+loader yields lists of ``InputExample`` or is a ``ResidentPretrainSet`` serves), data-parallel pre-training, the packed
+loader ring of the fine-tuning side, and fusing the masking into the visual-embedding product's input read."""
 import os
 
 import numpy as np
@@ -218,11 +223,18 @@ class LXMERT:
     is: padding it would change its mean losses); its answers land in the same log.  An answer log holds ``steps x batch
     size`` SAMPLES of its own engine and is read back early when the next batch would not fit.
 
+    A tuple's loader may be a ``pretrain.resident.ResidentPretrainSet`` (build ``LXMERT(resident=True)``: the store's gather
+    launch swaps, ``features`` does not): the per-epoch order comes from the store (training shuffles with ``args.seed`` and
+    drops the ragged tail, as the reference's train loader does), a step is ``load_resident`` + ``step()``, validation runs a
+    short last batch eagerly through buffers of its own size, and ``uid2ans`` pairs the answer log with ``store.uids(order)``.
+    ``train_batch(optim, (store, start[, rows]))`` / ``valid_batch((store, start[, rows]))`` take rows of the order the store
+    currently holds.
+
     The printed per-term line names the terms that are on; the reference zips LOSSES_NAME with however many terms there
     are, which mislabels them as soon as a task is off (:366, :402) -- with all tasks on the lines are the same."""
 
     def __init__(self, max_seq_length, model, tokenizer, args=None, use_graph=True, log_every=None, max_labels=4,
-                 vocab_size=None, mask_id=None):
+                 vocab_size=None, mask_id=None, resident=False):
         from .. import param
         self.max_seq_length, self.model, self.tokenizer = max_seq_length, model, tokenizer
         self.args = param.args if args is None else args
@@ -230,7 +242,8 @@ class LXMERT:
         vocab = getattr(tokenizer, "vocab", None)
         vocab_size = vocab_size if vocab_size is not None else (len(vocab) if vocab is not None else model.config.vocab_size)
         mask_id = mask_id if mask_id is not None else (vocab["[MASK]"] if vocab is not None else 103)
-        self.features = DeviceFeatures.from_args(self.args, swap=True, vocab_size=vocab_size, mask_id=mask_id, max_labels=max_labels)
+        # with a resident store the swap is fused into its gather launch: ``features`` must not swap a second time
+        self.features = DeviceFeatures.from_args(self.args, swap=not resident, vocab_size=vocab_size, mask_id=mask_id, max_labels=max_labels)
         self.device = next(model.parameters()).device
         self.engine, self._optim = None, None  # the training engine and the optimiser it was captured with
         self.valid_engine = None               # validation at another batch size, or before any training
@@ -240,24 +253,56 @@ class LXMERT:
         host = collate_examples(examples, self.tokenizer, self.max_seq_length, self.max_labels)
         return {k: v.to(self.device, non_blocking=True) for k, v in host.items()}
 
-    def _build(self, optim, batch, window):
+    @staticmethod
+    def _is_store(loader):
+        from .resident import ResidentPretrainSet
+        return isinstance(loader, ResidentPretrainSet)
+
+    def resident_order(self, store, kind, epoch=0):
+        """the order of one sweep over a store: training shuffles with ``args.seed`` and drops the ragged tail (the reference's
+        train loader: shuffle, drop_last), validation walks every sample in the store's own order"""
+        train = kind == "train"
+        if store.batch_size is None:
+            raise ValueError("LXMERT: a ResidentPretrainSet loader needs its batch_size")
+        return store.order(epoch, shuffle=train, seed=int(getattr(self.args, "seed", 0) or 0), drop_last=train,
+                           batch_size=store.batch_size)
+
+    def _n_batches(self, loader, kind):
+        if not self._is_store(loader):
+            return len(loader)
+        B = loader.batch_size
+        return len(loader) // B if kind == "train" else -(-len(loader) // B)
+
+    def _resident_batch(self, store, start, rows, like=None):
+        """buffers of ``rows`` rows filled from the store, swap included: the first batch an engine is built on (``like`` None:
+        a clean gather, nothing is drawn) or a ragged last batch that runs eagerly through buffers of its own size"""
+        from ..runtime import runtime_of
+        bufs = store.buffers(rows)
+        if like is None:
+            return store.fill(bufs, start, rows, swap=False)
+        store.fill(bufs, start, rows, rng=runtime_of(self.model).rng, sid_base=self.features.sid_base)
+        if "feat_pool" in like.static:
+            bufs["feat_pool"] = like.static["feat_pool"]
+        return bufs
+
+    def _build(self, optim, batch, window, resident=None):
         from ..engine import AnswerLog, CapturedPretrainer, TrainLog
         B = batch["input_ids"].shape[0]
-        e = CapturedPretrainer(self.model, optim, batch, self.features, clip=1.0, use_graph=self.use_graph,
+        e = CapturedPretrainer(self.model, optim, batch, self.features, clip=1.0, use_graph=self.use_graph, resident=resident,
                                train_log=TrainLog(window, self.device) if optim is not None else None,
                                valid_log=TrainLog(window, self.device),
                                answer_log=AnswerLog(window * B, self.device, with_scores=False) if self.model.task_qa else None)
         e.window = window
         return e
 
-    def _train_engine(self, optim, batch, window):
+    def _train_engine(self, optim, batch, window, resident=None):
         """the captured step for ``optim``, built at the first training batch (its size is the static one) with logs of
         ``window`` steps; rebuilt when the caller comes with another optimiser or a longer window"""
         if self.engine is None or optim is not self._optim or window > self.engine.window:
-            self.engine, self._optim = self._build(optim, batch, window), optim
+            self.engine, self._optim = self._build(optim, batch, window, resident), optim
         return self.engine
 
-    def _valid_engine(self, batch, window):
+    def _valid_engine(self, batch, window, resident=None):
         """the forward-only graph for batches of this size: the training engine's when the size is its own, else a
         validation-only engine captured at this size (rebuilt for a longer window or a larger batch)"""
         B = batch["input_ids"].shape[0]
@@ -266,7 +311,7 @@ class LXMERT:
             return e
         e = self.valid_engine
         if e is None or window > e.window or B > e.B:
-            self.valid_engine = e = self._build(None, batch, window)
+            self.valid_engine = e = self._build(None, batch, window, resident)
         return e
 
     @staticmethod
@@ -294,6 +339,8 @@ class LXMERT:
 
     def train_batch(self, optim, batch):
         """src/pretrain/lxmert_pretrain.py:308-318 -> (loss.item(), losses numpy [1, n], ans_logit)"""
+        if self._is_store(batch[0]):
+            return self._resident_call("train", optim, *batch)
         dev_batch = self._device_batch(batch)
         e = self._train_engine(optim, dev_batch, 1)
         self._reset_logs(e)  # a caller of the per-batch interface reads per batch: the logs never hold more than this step
@@ -301,17 +348,52 @@ class LXMERT:
 
     def valid_batch(self, batch):
         """src/pretrain/lxmert_pretrain.py:320-326 -> (loss.item(), losses numpy [1, n], ans_logit)"""
+        if self._is_store(batch[0]):
+            return self._resident_call("valid", None, *batch)
         dev_batch = self._device_batch(batch)
         e = self._valid_engine(dev_batch, 1)
         self._reset_logs(e)
         return self._read(e.valid_step(dev_batch))
 
+    def _resident_step(self, e, kind, store, start, rows):
+        """rows ``start .. start + rows`` of the store's current order through engine ``e``: ``load_resident`` + the replayed
+        step, or -- a ragged last batch -- the same calls eagerly on buffers of its own size"""
+        run = e.step if kind == "train" else e.valid_step
+        if rows == e.B:
+            e.load_resident(store, start)
+            return run()
+        if store.match_rate is not None and self.features.match_rate is not None:
+            raise ValueError("LXMERT: the store swaps and so does features; build LXMERT(resident=True)")
+        return run(self._resident_batch(store, start, rows, like=e))
+
+    def _resident_call(self, kind, optim, store, start, rows=None):
+        """``train_batch(optim, (store, start[, rows]))`` / ``valid_batch((store, start[, rows]))``: the batch is rows
+        ``start .. start + rows`` (default: the store's batch size) of the order the store currently holds"""
+        rows = int(rows if rows is not None else store.batch_size)
+        first = lambda: self._resident_batch(store, start, rows)
+        e = self.engine if self.engine is not None and (kind == "valid" or optim is self._optim) and self.engine.B == rows else None
+        if e is None:
+            e = self._train_engine(optim, first(), 1, store) if kind == "train" else self._valid_engine(first(), 1, store)
+        self._reset_logs(e)
+        return self._read(self._resident_step(e, kind, store, start, rows))
+
     # ------------------------------------------------------------------ epochs
-    def _sweep(self, loader, optim, kind, table, iters=-1):
+    def _steps(self, loader, kind, epoch):
+        """one sweep as (feed, rows, uids) per step; feed: the device batch of a list loader, or (store, start) of a store"""
+        if not self._is_store(loader):
+            for batch in loader:
+                yield self._device_batch(batch), len(batch), [datum.uid for datum in batch]
+            return
+        order, B = self.resident_order(loader, kind, epoch), loader.batch_size
+        for start in range(0, len(order), B):
+            rows = min(B, len(order) - start)
+            yield (loader, start), rows, loader.uids(order[start:start + rows])
+
+    def _sweep(self, loader, optim, kind, table, iters=-1, epoch=0):
         """one pass over ``loader`` with no per-step read -> (sum of losses, {name: sum of term}, steps, uid2ans); the logs
         are read once at its end, or once per ``log_every`` steps (earlier when the answer log could not take the next batch)"""
         from .. import trainlog as T
-        n_batches = len(loader)
+        n_batches = self._n_batches(loader, kind)
         window = max(1, min(self.log_every or n_batches, n_batches))
         total, terms, steps, uids, uid2ans = 0.0, {}, 0, [], {}
         e = None
@@ -335,19 +417,24 @@ class LXMERT:
             self._reset_logs(e)
 
         pending = 0
-        for i, batch in enumerate(loader):
-            dev_batch = self._device_batch(batch)
+        store = loader if self._is_store(loader) else None
+        for i, (feed, rows, step_uids) in enumerate(self._steps(loader, kind, epoch)):
             if e is None:
-                e = self._train_engine(optim, dev_batch, window) if kind == "train" else self._valid_engine(dev_batch, window)
+                # a store's engine is built on a clean gather of the sweep's first rows, with the store's table as its pool
+                first = feed if store is None else self._resident_batch(store, feed[1], rows)
+                e = (self._train_engine(optim, first, window, store) if kind == "train"
+                     else self._valid_engine(first, window, store))
                 self._reset_logs(e)
-            if pending and e.answer_log is not None and e.answer_log.count + len(batch) > e.answer_log.capacity:
+            if pending and e.answer_log is not None and e.answer_log.count + rows > e.answer_log.capacity:
                 read_back()
                 pending = 0
-            if kind == "train":
-                e.step(dev_batch)
+            if store is not None:
+                self._resident_step(e, kind, store, feed[1], rows)
+            elif kind == "train":
+                e.step(feed)
             else:
-                e.valid_step(dev_batch)
-            uids.extend(datum.uid for datum in batch)
+                e.valid_step(feed)
+            uids.extend(step_uids)
             pending += 1
             if pending == window:
                 read_back()
@@ -372,7 +459,7 @@ class LXMERT:
         from ..lxrt.optimization import BertAdam
         args = self.args
         dataset, train_ld, evaluator = _tuple(train_tuple)
-        batch_per_epoch = len(train_ld)
+        batch_per_epoch = self._n_batches(train_ld, "train")
         t_total = int(batch_per_epoch * args.epochs)
         warmup_ratio = 0.05
         warmup_iters = int(t_total * warmup_ratio)
@@ -383,7 +470,7 @@ class LXMERT:
         best_eval_loss = 9595.
         for epoch in range(args.epochs):
             self.model.train()
-            total_loss, terms, _, uid2ans = self._sweep(train_ld, optim, "train", dataset.answer_table)
+            total_loss, terms, _, uid2ans = self._sweep(train_ld, optim, "train", dataset.answer_table, epoch=epoch)
             print("The training loss for Epoch %d is %0.4f" % (epoch, total_loss / batch_per_epoch))
             print(self._losses_line(terms, batch_per_epoch))
             if self.model.task_qa:
@@ -401,11 +488,12 @@ class LXMERT:
         self.model.eval()
         total_loss, terms, _, uid2ans = self._sweep(eval_ld, None, "valid", dataset.answer_table, iters)
         self.model.train(was_training)
-        print("The valid loss is %0.4f" % (total_loss / len(eval_ld)))
-        print(self._losses_line(terms, len(eval_ld)))
+        n_eval = self._n_batches(eval_ld, "valid")
+        print("The valid loss is %0.4f" % (total_loss / n_eval))
+        print(self._losses_line(terms, n_eval))
         if self.model.task_qa:
             evaluator.evaluate(uid2ans, pprint=True)
-        return total_loss / len(eval_ld)
+        return total_loss / n_eval
 
     # ------------------------------------------------------------------ snapshots, the reference's file names
     def save(self, name):

@@ -15,7 +15,7 @@ The features of a split fit in HBM many times over (120 000 images: 17.7 GB of b
 and ``fill`` gathers ``order[start : start + B]`` into the trainer's static buffers with ``ops.batch_gather``: no producer
 thread, no pinned ring, no host-to-device copy, no host work per step beyond the launch.  ``host_batch`` restates the
 gather in numpy from the same tables -- the reference the kernel is tested against on the CPU, NOT a fallback: ``fill``
-refuses CPU tensors like every other op.  Pre-training batches are not covered.
+refuses CPU tensors like every other op.  Pre-training batches have a store of their own: ``pretrain.resident.ResidentPretrainSet``.
 """
 import numpy as np
 import torch
@@ -72,6 +72,18 @@ def sample_tables(ts, batcher, A=None):
     return dict(q_row=rows.astype(np.int32), q_ids=q_ids, q_len=q_len, q_label=q_label, q_score=q_score)
 
 
+def host_feats(f, out_f32=False):
+    """feature rows of a host table (uint16 bf16 bit patterns or float32) as the batch tensor the gather kernels write: same
+    type copied, fp32 -> bf16 rounded as ``torch.Tensor.to(torch.bfloat16)``, bf16 -> fp32 as ``bits << 16``"""
+    f = np.ascontiguousarray(f)
+    if f.dtype == np.float32:
+        return torch.from_numpy(f.copy()) if out_f32 else torch.from_numpy(_bf16_bits(f).view(np.int16).copy()).view(torch.bfloat16)
+    if f.dtype == np.uint16:
+        return (torch.from_numpy((f.astype(np.uint32) << 16).view(np.float32)) if out_f32
+                else torch.from_numpy(f.view(np.int16).copy()).view(torch.bfloat16))
+    raise TypeError("gather_host: feats are %s, uint16 (bf16 bits) or float32 expected" % f.dtype)
+
+
 def gather_host(tables, indices, A, out_f32=False):
     """``ops.batch_gather`` restated in numpy: the batch of the samples ``indices`` out of host ``tables`` (numpy arrays
     under the kernel's names; ``feats`` uint16 bf16 bit patterns or float32) -> dict of CPU tensors under the trainer's
@@ -79,14 +91,7 @@ def gather_host(tables, indices, A, out_f32=False):
     bf16 -> fp32 is ``bits << 16``."""
     idx = np.asarray(indices, dtype=np.int64).reshape(-1)
     rows = tables["q_row"][idx].astype(np.int64)
-    f = np.ascontiguousarray(tables["feats"][rows])
-    if f.dtype == np.float32:
-        feats = torch.from_numpy(f.copy()) if out_f32 else torch.from_numpy(_bf16_bits(f).view(np.int16).copy()).view(torch.bfloat16)
-    elif f.dtype == np.uint16:
-        feats = (torch.from_numpy((f.astype(np.uint32) << 16).view(np.float32)) if out_f32
-                 else torch.from_numpy(f.view(np.int16).copy()).view(torch.bfloat16))
-    else:
-        raise TypeError("gather_host: feats are %s, uint16 (bf16 bits) or float32 expected" % f.dtype)
+    feats = host_feats(tables["feats"][rows], out_f32)
     B, T = len(idx), tables["q_ids"].shape[1]
     out = dict(feats=feats, boxes=torch.from_numpy(np.array(tables["boxes"][rows], dtype=np.float32)))
     if tables.get("adj") is not None:
