@@ -1312,6 +1312,50 @@ typedef struct xggm_answer_log {
 int xggm_answer_pick_f32(const float* logits, int64_t row_stride, const float* target, int64_t target_stride, int B, int A,
                          const int* rows, xggm_answer_log* log, float* ws, xggm_stream_t stream);
 
+/* ---- sweep score --------------------------------------------------------------------------
+ * The reference scores a sweep on the host: `evaluator.evaluate(quesid2ans)` walks a {question_id: answer string} dict
+ * through id2datum / ans2label (src/vqa/vqacpv2_data.py:134-142, src/gqa/gqa_ood_data.py:160-167), four times per epoch
+ * for the validation split (src/vqa/vqacpv2.py:271-272, :293-294) and once for the training answers (:285).  The ground
+ * truth of every sample already lies on the device, in the q_label / q_score tables of xggm_batch_gather; ONE launch scores
+ * the `labels` of an answer log against them.  Position i in [0, n):
+ *     s        = order ? order[i] : i                       (order: int64 [n]; the sample the i-th logged answer belongs to)
+ *     a        = labels[i]                                  (int64 [n])
+ *     w        = keep ? (keep[i] != 0) : 1                  (keep: uint8 [n]; 0 drops the position -- a question id that
+ *                                                            occurs again later in the sweep, as a dict assignment would)
+ *     g        = q_group ? q_group[s] : none                (q_group: int32 [n_q], values in [0, G))
+ *     score    = q_score[s][k] for the FIRST k < K with q_label[s][k] == a and q_label[s][k] >= 0, else 0
+ *                                                           (q_label int32 [n_q, K], -1 = unused slot; q_score fp32 [n_q, K])
+ *     v[i]     = w ? (double)score : +0.0;   v_g[i] = (w and g == group) ? (double)score : +0.0
+ * A position with s outside [0, n_q) or g outside [0, G) contributes nothing to any word, none of its table rows is read
+ * (q_group[s] is, when only g offends) and flag bit 1 is raised -- whatever its w.
+ * out (DEVICE int64, 3 + 2 G words, every one written):
+ *     [flags, count_all, count_g[0 .. G), sum_all, sum_g[0 .. G)]      counts: the positions with w = 1; sums: fp64 bit patterns
+ *     flags bit 0: `cursor` (DEVICE int64, may be NULL) was given and *cursor != n;  bit 1: an index was out of range.
+ * ORDER OF THE SUMS (of sum_all over v, of sum_g over v_g; it depends on n alone, not on the grid, the timing or the device):
+ * v is cut into chunks of XGGM_SCORE_CHUNK = 1024 positions, the last one padded with +0.0.  Within a chunk, with x = its
+ * 1024 values:
+ *     a[t]  = (((+0.0 + x[t]) + x[t + 256]) + x[t + 512]) + x[t + 768]          for t in [0, 256)
+ *     then for h = 128, 64, 32, 16, 8, 4, 2, 1:   a[t] = a[t] + a[t + h]          for t in [0, h)
+ *     partial = a[0]
+ * and the sum is (((+0.0 + partial[0]) + partial[1]) + ...) in chunk order.  All additions are fp64; there is no
+ * floating-point atomic.  numpy: x.reshape(4, 256), three row additions, eight times a = a[:h] + a[h:], then a running sum
+ * (xggm_amd.answers.score_host).
+ * One workgroup per chunk leaves its 3 + 2 G words in `ws` with write-through stores and takes a ticket (the publication
+ * pattern of common.h::ordered_grid_sum); the workgroup that draws the last ticket combines the chunks in index order.
+ * `ws`: caller-owned DEVICE scratch of xggm_answer_score_workspace_bytes(n, G) bytes, 8-byte aligned; its first 8 bytes are
+ * 0 at the first launch and the kernel leaves them 0; the rest needs no initialisation.  labels, order, keep and the tables
+ * are only read; nothing outside out[0 .. 3 + 2 G) and the declared workspace is written.  Rows of q_label / q_score are read
+ * with 4-byte loads: K is free.  One launch, no allocation, no host synchronisation: legal inside a stream capture.
+ * Refused before any launch: null labels / q_label / q_score / out / ws; n < 1 (or > 2^31 - 1); n_q < 1; K < 1; G outside
+ * [0, XGGM_SCORE_MAX_GROUPS]; q_group without G or G without q_group; labels, order, cursor, out, ws not 8-byte or a table
+ * not 4-byte aligned; ws_bytes below the declared size. */
+#define XGGM_SCORE_MAX_GROUPS 16
+#define XGGM_SCORE_CHUNK 1024
+size_t xggm_answer_score_workspace_bytes(int64_t n, int G);
+int xggm_answer_score(const int64_t* labels, const int64_t* order, const uint8_t* keep, const int32_t* q_label,
+                      const float* q_score, const int32_t* q_group, int64_t n, int64_t n_q, int K, int G, const int64_t* cursor,
+                      int64_t* out, void* ws, size_t ws_bytes, xggm_stream_t stream);
+
 /* ---- training log -------------------------------------------------------------------------
  * The reference loop reads its scalars from the GPU in every iteration: the running loss, `total_loss += loss.detach()
  * / logit.size(0)` (src/vqa/vqacpv2.py:179), and the tensorboard scalars Train/batch_loss, Train/average_loss and lr

@@ -82,6 +82,7 @@ class AnswerLog:
         self._rows_sent = None   # value the device word holds (after the copies queued so far)
         self._rows_copied = None  # event behind the last copy out of the pinned slot
         self.count = 0  # host mirror of the cursor: samples handed to the log since reset()
+        self._score = None  # buffers of ``score_store``, made on its first call
 
     def set_rows(self, n):
         """queue ``rows = n`` in stream order (nothing is queued while the value does not change: full batches).  The
@@ -126,6 +127,38 @@ class AnswerLog:
             raise RuntimeError("AnswerLog.score: the log was built without scores")
         _, _, total, n = self.read()
         return total / n if n else 0.0
+
+    def score_store(self, store, order=None, keep=None, by_group=False):
+        """what ``evaluator.evaluate`` makes of the log's first ``count`` answers, computed where they lie: ONE launch
+        (``ops.answer_score``) scores them against the ground truth of ``store`` (a ``tools.resident.ResidentDataset``: its
+        q_label / q_score tables) and ONE read-back of a few words follows -- no labels cross the host link, no dict is built.
+        ``order``: the sample of every logged answer, a device int64 tensor or a host array of at least ``count`` entries
+        (None: answer i belongs to sample i, a sweep in data set order); ``keep``: 0 / 1 per answer, device uint8 tensor or
+        host array (None: all count) -- ``answers.last_occurrence_mask`` of the question ids gives the reference's dict
+        semantics, where a question that occurs twice counts once.  ``by_group``: also per group of the store (``ResidentDataset(groups=)``).
+        -> the dict of ``answers.decode_score``; RuntimeError when the cursor is not ``count`` or an index was out of range."""
+        from .answers import decode_score
+        n, dev = self.count, self.buf.device
+        if n < 1:
+            raise RuntimeError("AnswerLog.score_store: the log is empty")
+        G = 0
+        if by_group:
+            if "q_group" not in store.tables:
+                raise ValueError("AnswerLog.score_store: the store was built without groups")
+            G = store.G
+        if self._score is None:  # out words, their pinned mirror and the workspace: sized once, for every later call
+            self._score = (torch.zeros(3 + 2 * ops.SCORE_MAX_GROUPS, dtype=torch.int64, device=dev),
+                           torch.zeros(3 + 2 * ops.SCORE_MAX_GROUPS, dtype=torch.int64).pin_memory(),
+                           ops.answer_score_workspace(self.capacity, ops.SCORE_MAX_GROUPS, dev))
+        out, host, ws = self._score
+        order = order if order is None or torch.is_tensor(order) else torch.as_tensor(order, dtype=torch.int64).to(dev)
+        keep = keep if keep is None or torch.is_tensor(keep) else torch.as_tensor(keep, dtype=torch.uint8).to(dev)
+        W = 3 + 2 * G
+        ops.answer_score(self.labels, store.tables["q_label"], store.tables["q_score"], n, order=order, keep=keep,
+                         q_group=store.tables["q_group"] if G else None, G=G, cursor=self.cursor, out=out, ws=ws)
+        host[:W].copy_(out[:W], non_blocking=True)
+        torch.cuda.current_stream(dev).synchronize()
+        return decode_score(host[:W], G, store.group_names if G else None)
 
 
 class TrainLog:

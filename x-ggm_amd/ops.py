@@ -1761,6 +1761,66 @@ def answer_pick(logits, log, target=None, rows=None):
          ptr(sum_ws(logits.device)), stream())
 
 
+SCORE_MAX_GROUPS = 16  # XGGM_SCORE_MAX_GROUPS (include/xggm.h)
+
+
+def answer_score_workspace(n, G, device):
+    """zeroed workspace of ``answer_score`` for sweeps of up to ``n`` positions and ``G`` groups (int64 words; the kernel
+    leaves it ready for the next launch)"""
+    nbytes = _lib.lib.xggm_answer_score_workspace_bytes(int(n), int(G))
+    if nbytes == 0:
+        raise ValueError("answer_score_workspace: n=%d, G=%d (n >= 1, 0 <= G <= %d)" % (n, G, SCORE_MAX_GROUPS))
+    return torch.zeros(nbytes // 8, dtype=torch.int64, device=device)
+
+
+def answer_score(labels, q_label, q_score, n=None, order=None, keep=None, q_group=None, G=0, n_q=None, cursor=None, out=None,
+                 ws=None):
+    """score the first ``n`` (default: all) ``labels`` (int64, an ``AnswerLog``'s) against the tables ``q_label`` int32
+    [n_q, K] / ``q_score`` fp32 [n_q, K] of a device-resident split in ONE launch; contract: xggm_answer_score in xggm.h.
+    ``order``: int64 [>= n], the sample of every position (None: position i is sample i); ``keep``: uint8 [>= n] (None: all
+    count); ``q_group``: int32 [n_q] with ids in [0, G) for per-group counts and sums; ``n_q``: how many rows of the tables
+    the launch is told of (default: all); ``cursor``: int64 [1] device word compared with n.  ``out``: int64 [>= 3 + 2 G]
+    and ``ws`` (``answer_score_workspace``) are made when not given.  -> ``out[:3 + 2 G]`` on the device:
+    [flags, count_all, count_g.., sum_all, sum_g..]; ``answers.decode_score`` reads its host copy."""
+    _c(labels, torch.int64, "labels"), _c(q_label, torch.int32, "q_label"), _c(q_score, F32, "q_score")
+    dev = labels.device
+    n = labels.numel() if n is None else int(n)
+    G = int(G)
+    if labels.dim() != 1 or not 1 <= n <= labels.numel():
+        raise ValueError("answer_score: n=%d of %s labels" % (n, tuple(labels.shape)))
+    if q_label.dim() != 2 or tuple(q_score.shape) != tuple(q_label.shape) or q_label.shape[0] < 1 or q_label.shape[1] < 1:
+        raise ValueError("answer_score: q_label %s and q_score %s, two [n_q, K] tables expected" % (tuple(q_label.shape), tuple(q_score.shape)))
+    rows, K = q_label.shape
+    n_q = rows if n_q is None else int(n_q)
+    if not 1 <= n_q <= rows:
+        raise ValueError("answer_score: n_q=%d, the tables hold %d samples" % (n_q, rows))
+    if not 0 <= G <= SCORE_MAX_GROUPS or (q_group is None) != (G == 0):
+        raise ValueError("answer_score: G=%d %s q_group (0 <= G <= %d; groups and their number come together)"
+                         % (G, "without" if q_group is None else "with", SCORE_MAX_GROUPS))
+    if order is not None and (_c(order, torch.int64, "order").dim() != 1 or order.numel() < n):
+        raise ValueError("answer_score: order %s for n=%d" % (tuple(order.shape), n))
+    if keep is not None and (_c(keep, torch.uint8, "keep").dim() != 1 or keep.numel() < n):
+        raise ValueError("answer_score: keep %s for n=%d" % (tuple(keep.shape), n))
+    if q_group is not None and tuple(_c(q_group, torch.int32, "q_group").shape) != (rows,):
+        raise ValueError("answer_score: q_group %s, [%d] expected" % (tuple(q_group.shape), rows))
+    if cursor is not None and _c(cursor, torch.int64, "cursor").numel() < 1:
+        raise ValueError("answer_score: cursor must hold ONE int64 word")
+    W = 3 + 2 * G
+    if out is None:
+        out = torch.empty(W, dtype=torch.int64, device=dev)
+    if ws is None:
+        ws = answer_score_workspace(n, G, dev)
+    _c(out, torch.int64, "out"), _c(ws, torch.int64, "ws")
+    if out.numel() < W:
+        raise ValueError("answer_score: out holds %d words, %d are written" % (out.numel(), W))
+    for t in (q_label, q_score, order, keep, q_group, cursor, out, ws):
+        if t is not None and t.device != dev:
+            raise RuntimeError("answer_score: all operands must live on one device")
+    call("xggm_answer_score", ptr(labels), ptr(order), ptr(keep), ptr(q_label), ptr(q_score), ptr(q_group), n, n_q, K, G,
+         ptr(cursor), ptr(out), ptr(ws), ws.numel() * 8, stream())
+    return out[:W]
+
+
 TRAINLOG_COLS = 8   # XGGM_TRAINLOG_COLS (include/xggm.h)
 TRAINLOG_KINDS = 4  # XGGM_TRAINLOG_KINDS
 

@@ -111,15 +111,35 @@ def gather_host(tables, indices, A, out_f32=False):
     return out
 
 
+MAX_GROUPS = 16  # XGGM_SCORE_MAX_GROUPS (include/xggm.h)
+
+
+def group_ids(data, key):
+    """group ids for the per-group scores of a sweep (``AnswerLog.score_store(by_group=True)``): ``data`` is the list of
+    datums in SAMPLE order (``ts.data``), ``key`` a field name (``"answer_type"`` on VQA-CP v2) or a callable datum -> name
+    (head / tail / neither from the id lists of GQA-OOD).  -> (ids int32 [n], names): the distinct names sorted (by their
+    string form, so that the ids do not depend on the order of the data), ``ids[i]`` the index of datum i's name."""
+    name_of = key if callable(key) else (lambda d: d[key])
+    values = [name_of(d) for d in data]
+    names = sorted(set(values), key=str)
+    index = {v: k for k, v in enumerate(names)}
+    return np.asarray([index[v] for v in values], dtype=np.int32), names
+
+
 class ResidentDataset:
-    def __init__(self, ts, batcher, device, bias_index=None, chunk_bytes=64 << 20, max_bytes=None, batch_size=None):
+    def __init__(self, ts, batcher, device, bias_index=None, chunk_bytes=64 << 20, max_bytes=None, batch_size=None, groups=None,
+                 group_names=None):
         """``ts``: a ``VQATorchDataset`` / ``GQATorchDataset`` (anything with ``.shard``, ``.rows``, ``.data``,
         ``.raw_dataset`` and ``fill_target``); ``batcher``: the model's ``SentenceBatcher``; ``bias_index``: [n_q] ints, the
         prior-table row of every sample for a debias loss, or None.  The shard's arrays are uploaded once through ONE
         pinned staging buffer of ``chunk_bytes``.  ``max_bytes``: refuse (ValueError naming the total) a split whose tables
-        exceed it; default: the device's free memory minus 2 GiB.  ``batch_size``: default of ``order`` for ``world > 1``."""
+        exceed it; default: the device's free memory minus 2 GiB.  ``batch_size``: default of ``order`` for ``world > 1``.
+        ``groups``: [n_q] ints in [0, G), G <= 16 -- the answer type, head / tail ... of every sample, uploaded as the table
+        ``q_group`` for ``AnswerLog.score_store(by_group=True)`` -- or the ``(ids, names)`` pair of ``group_ids``;
+        ``group_names``: G names (default: the pair's, else the ids themselves)."""
         self.ts, self.batcher, self.device = ts, batcher, torch.device(device)
         self.batch_size = batch_size
+        self.G, self.group_names, self._qid_index, self._keep = 0, None, None, None
         sh = ts.shard
         self.N, self.F, self.T, self.A = int(sh.N), int(sh.F), int(batcher.T), int(ts.raw_dataset.num_answers)
         if self.F % 8:
@@ -130,6 +150,19 @@ class ResidentDataset:
             if bi.shape[0] != len(ts.data):
                 raise ValueError("ResidentDataset: bias_index has %d entries for %d samples" % (bi.shape[0], len(ts.data)))
             host["q_bias_index"] = bi
+        if groups is not None:
+            if isinstance(groups, tuple):
+                groups, names = groups
+                group_names = names if group_names is None else group_names
+            gi = np.asarray(groups, dtype=np.int64).reshape(-1)
+            G = len(group_names) if group_names is not None else int(gi.max()) + 1 if gi.size else 0
+            if gi.shape[0] != len(ts.data):
+                raise ValueError("ResidentDataset: groups has %d entries for %d samples" % (gi.shape[0], len(ts.data)))
+            if not 1 <= G <= MAX_GROUPS or gi.min() < 0 or gi.max() >= G:
+                raise ValueError("ResidentDataset: group ids must lie in [0, G) with 1 <= G <= %d (G = %d, ids %d .. %d)"
+                                 % (MAX_GROUPS, G, gi.min(), gi.max()))
+            host["q_group"] = gi.astype(np.int32)
+            self.G, self.group_names = G, list(group_names) if group_names is not None else list(range(G))
         # the shard's own arrays, as mapped: nothing is read before the upload (or host_batch) touches the rows
         host["feats"] = sh.feats_bits if sh.feats_f is None else sh.feats_f
         host["boxes"] = sh.boxes
@@ -227,3 +260,23 @@ class ResidentDataset:
     def ques_ids(self, indices):
         """question ids of the samples ``indices`` (what ``fill`` leaves in ``sample``), for pairing with an ``AnswerLog``"""
         return [self.ts.data[int(i)]["question_id"] for i in np.asarray(indices).reshape(-1)]
+
+    @property
+    def qid_index(self):
+        """[n_q] int64: the question id of every sample as a small int -- equal ids (strings included; a GQA datum is kept
+        once per label) get equal ints.  Made on first use."""
+        if self._qid_index is None:
+            ids = [d["question_id"] for d in self.ts.data]
+            self._qid_index = np.unique(np.asarray(ids), return_inverse=True)[1].astype(np.int64).reshape(-1)
+        return self._qid_index
+
+    def keep_mask(self, order=None):
+        """device uint8 [len(order)] for ``AnswerLog.score_store(keep=)``: 1 where a sweep over the samples ``order`` (host
+        indices; None: every sample in data set order, computed ONCE and kept) meets a question id for the last time -- the
+        answers a ``quesid2ans`` dict filled in that order would hold"""
+        from ..answers import last_occurrence_mask
+        if order is None:
+            if self._keep is None:
+                self._keep = torch.from_numpy(last_occurrence_mask(self.qid_index)).to(self.device)
+            return self._keep
+        return torch.from_numpy(last_occurrence_mask(self.qid_index[np.asarray(order, dtype=np.int64)])).to(self.device)

@@ -526,6 +526,320 @@ def evaluate(model, eval_tuple, dump=None, predictor=None, resident=None):
     return eval_tuple[2].evaluate(predict(model, eval_tuple, dump, predictor, resident))
 
 
+def val_schedule(n_batches):
+    """the iterations after which the reference validates inside an epoch of ``n_batches`` iterations
+    (``val_in_epoch``, src/vqa/vqacpv2.py:157; the last bin edge is the epoch's own validation)"""
+    import numpy as np
+    return np.linspace(0, n_batches, 5, dtype=int)[1:-1]
+
+
+def _tuple(t):
+    """(dataset, loader, evaluator) of a DataTuple-like object or a plain 3-tuple"""
+    if hasattr(t, "dataset"):
+        return t.dataset, t.loader, t.evaluator
+    return t[0], t[1], t[2]
+
+
+def _is_store(loader):
+    from ..tools.resident import ResidentDataset
+    return isinstance(loader, ResidentDataset)
+
+
+class FineTuner:
+    """What ``class VQA`` (src/vqa/vqacpv2.py:70-368) and ``class GQA`` (src/gqa/gqa_ood.py:70-431) share -- the names,
+    signatures, printed lines and ``log.log`` lines are the reference's, the code is ours and runs on the pieces of this
+    module and of ``engine``: an iteration is ``CapturedTrainer.load_resident`` + ``iteration(pick_branch(...))``, a
+    validation sweep one ``CapturedPredictor`` with an ``AnswerLog``, and every score one ``AnswerLog.score_store`` launch
+    with a read-back of a few words.  Nothing is read from the device per iteration: the losses come from a ``TrainLog``
+    once per epoch (``log_every=N``: once per N iterations) and ahead of every validation sweep, so that a ``writer`` sees
+    the reference's sequence of scalars.
+
+    ``model``: a ``VQAModel`` / ``GQAModel`` on the GPU, snapshots loaded (the reference builds it inside the class; here
+    the caller does, as for ``pretrain.lxmert_pretrain.LXMERT``); a model prepared with ``enable_data_parallel`` is refused.
+    ``train_tuple`` / ``valid_tuple``: ``(dataset, loader, evaluator)``.  A loader is a ``tools.resident.ResidentDataset``
+    -- the device path: per-epoch order from ``store.order(epoch, shuffle=True, seed=args.seed, drop_last=True)``, batches
+    gathered in HBM, scores computed against the store's own tables with the keep mask that gives a ``quesid2ans`` dict's
+    semantics (a question that occurs twice counts once, with its last answer) -- or a ``DataLoaderX`` (the host path:
+    ``load_batch``, the module's ``predict`` and the evaluator's dict walk).  ``args``: the flag namespace
+    (``param.parse_args``: ``batch_size``, ``epochs``, ``lr``, ``optim``, ``delta``, ``sigma``, ``seed``, ``output``).
+    ``valid_batch_size``: rows of the captured validation forward (default ``valid_factor * args.batch_size``).
+    ``writer``: anything with ``add_scalar(tag, value, step)`` (the reference's ``--tf_writer``); None: nothing is written.
+
+    The training engine is captured on the first batch of the first epoch; ``CapturedTrainer`` warms up with eager passes
+    on that batch (optimiser steps at the head of the warm-up schedule), as it does for every caller."""
+
+    order = "vqa"        # pass order and KL weight of ``CapturedTrainer``
+    valid_factor = 1     # validation batch size over the training one (src/gqa/gqa_ood.py:82: 2)
+    extra_tags = ()      # writer tags beyond the common ones, written with the value the reference leaves in them
+
+    def __init__(self, model, train_tuple, valid_tuple=None, args=None, use_graph=True, valid_batch_size=None, log_every=None,
+                 writer=None):
+        import os
+        from .. import param
+        if getattr(model, "_grad_sync", None) is not None:
+            raise NotImplementedError("%s: a model prepared with enable_data_parallel is not supported by this driver (every "
+                                      "rank would need its own epoch order and the ranks' scores would need combining); "
+                                      "drive CapturedTrainer directly" % type(self).__name__)
+        self.model, self.args = model, (param.args if args is None else args)
+        self.train_tuple, self.valid_tuple = train_tuple, valid_tuple
+        self.use_graph, self.log_every, self.writer = use_graph, log_every, writer
+        self.device = next(model.parameters()).device
+        self.B = int(self.args.batch_size)
+        self.valid_B = int(valid_batch_size) if valid_batch_size else self.valid_factor * self.B
+        self.bce_loss = BCEWithLogitsLoss()
+        batch_per_epoch = self._n_batches(_tuple(train_tuple)[1])
+        t_total = int(batch_per_epoch * self.args.epochs)
+        if 'bert' in self.args.optim:
+            print(self._total_iters_line(t_total))
+        self.optim = make_optimizer(model, self.args.lr, 2 * t_total, optim=self.args.optim)
+        self.output = self.args.output
+        os.makedirs(self.output, exist_ok=True)
+        self.trainer, self.predictor = None, None
+        self.sweeps = 0          # validation sweeps made so far (``predict`` calls)
+        self.total_loss = 0.0    # the reference's running ``total_loss`` (never reset between epochs)
+        self.history = []        # per epoch of ``train``: the unrounded numbers behind the lines of log.log
+        self.valid_scores = []   # every validation score of ``train``, in the order the sweeps ran
+
+    # ------------------------------------------------------------------ what the two classes differ in
+    def _total_iters_line(self, t_total):
+        return f"BertAdam Total Iters: {t_total}\n{'*' * 80}"
+
+    def _loss_divisor(self, trainer):
+        """``total_loss += loss / logit.size(0)`` (src/vqa/vqacpv2.py:179)"""
+        return trainer.static["target"].shape[0]
+
+    def _epoch_lines(self, epoch, train_score, valid_score, best_valid):
+        s = f"\nEpoch {epoch}: Train {train_score:.2f}\n"
+        if valid_score is not None:
+            s += f"\nEpoch {epoch}: Valid {valid_score * 100.:.2f}\n" + f"Epoch {epoch}: Best {best_valid * 100.:.2f}\n"
+        return s
+
+    def _print_lr(self):
+        print(f"lr: {self.optim.state_dict()['param_groups'][0]['lr']}")  # src/vqa/vqacpv2.py:289
+
+    # ------------------------------------------------------------------ engines
+    def _n_batches(self, loader):
+        return len(loader) // self.B if _is_store(loader) else len(loader)
+
+    def _engine(self, make_batch, B, n_batches):
+        """the captured iteration at ``B`` rows with an answer log for a whole epoch and a training log for ``log_every``
+        iterations (default: an epoch); built on ``make_batch()`` when there is none that fits"""
+        from ..engine import AnswerLog, CapturedTrainer, TrainLog
+        window = self.window = min(int(self.log_every), n_batches) if self.log_every else n_batches
+        tr = self.trainer
+        if tr is None or tr.static["target"].shape[0] != B or tr.answer_log.capacity < n_batches * B or tr.window < window:
+            tr = CapturedTrainer(self.model, self.optim, make_batch(), sigma=self.args.sigma, order=self.order,
+                                 use_graph=self.use_graph, answer_log=AnswerLog(n_batches * B, self.device),
+                                 train_log=TrainLog(2 * window, self.device))
+            tr.window = window
+            self.trainer = tr
+        return tr
+
+    def _store_batch(self, store, samples):
+        """the samples ``samples`` of a resident store as device tensors under the trainer's names, features in the store's
+        own type: the batch the engine is captured on"""
+        host = store.host_batch(samples, out_f32=store.tables["feats"].dtype == torch.float32)
+        with_bias = getattr(self.model, "debias_loss", None) is not None
+        return {k: v.to(self.device) for k, v in host.items() if k != "sample" and (k != "bias_index" or with_bias)}
+
+    def _predictor(self, loader):
+        """ONE captured validation forward with an answer log for the whole sweep, reused across sweeps"""
+        from ..engine import AnswerLog, CapturedPredictor
+        n = len(loader) if _is_store(loader) else len(loader.ds)
+        N = loader.N if _is_store(loader) else loader.ds.shard.N
+        B = self.valid_B if _is_store(loader) else max(self.valid_B, loader.B)
+        p = self.predictor
+        if p is None or p.log.capacity < n or p.B < B or p.static["feats"].shape[1] != N:
+            p = self.predictor = CapturedPredictor(self.model, B, n_objects=N, use_graph=self.use_graph,
+                                                   log=AnswerLog(n, self.device, with_scores=False))
+        return p
+
+    def _device_batch(self, item):
+        """a loader item (ques_id, feats, boxes, sent, target, adj) as the trainer's static fields"""
+        _, feats, boxes, sent, target, adj = item[:6]
+        if not torch.is_tensor(sent) and not (len(sent) == 3 and torch.is_tensor(sent[0])):
+            sent = self.model.lxrt_encoder.batcher.host_batch(list(sent)).clone()  # strings: tokenised here
+        to = lambda t: (torch.from_numpy(t) if not torch.is_tensor(t) else t).to(self.device)  # noqa: E731
+        return dict(feats=to(feats), boxes=to(boxes), input_ids=to(sent[0]), input_mask=to(sent[1]), segment_ids=to(sent[2]),
+                    target=to(target), adj_true=to(adj))
+
+    # ------------------------------------------------------------------ the reference's methods
+    def _flush_losses(self, state):
+        """ONE read of the training log: the scalars of the iterations since the last flush, to ``total_loss`` and the writer"""
+        tr = self.trainer
+        if tr is None or state["pending"] == 0:
+            return
+        from ..engine import TrainLog
+        rec = tr.train_log.read()
+        tr.train_log.reset()
+        m = 2 * state["pending"]
+        values, kinds = rec["values"][-m:], rec["kinds"][-m:]
+        if int(rec["cursor"]) != m or values.shape[0] != m:
+            raise RuntimeError("%s: the training log holds %d records, %d were expected" % (type(self).__name__, int(rec["cursor"]), m))
+        div = float(self._loss_divisor(tr))
+        lr = self.optim.state_dict()['param_groups'][0]['lr']
+        for k in range(state["pending"]):
+            pair = range(2 * k, 2 * k + 2)
+            plain = [j for j in pair if int(kinds[j]) == TrainLog.PLAIN]
+            if len(plain) != 1:
+                raise RuntimeError("%s: iteration without exactly one plain pass in the training log" % type(self).__name__)
+            self.total_loss += float(values[plain[0], TrainLog.LOSS]) / div
+            if self.writer is not None:
+                it = state["train_iter"]
+                # ``loss`` as the iteration leaves it: the SECOND pass's (VQA: the GGM pass, GQA: the plain pass)
+                self.writer.add_scalar('Train/batch_loss', float(values[2 * k + 1, TrainLog.LOSS]), it)
+                self.writer.add_scalar('Train/average_loss', self.total_loss / (it + 1), it)
+                self.writer.add_scalar('lr', lr, it)
+                for tag in self.extra_tags:
+                    self.writer.add_scalar(tag, 0., it)
+                state["train_iter"] += 1
+        state["pending"] = 0
+
+    def train(self, train_tuple, eval_tuple):
+        from ..answers import to_quesid2ans
+        dset, loader, evaluator = _tuple(train_tuple)
+        resident = _is_store(loader)
+        n_batches = self._n_batches(loader)
+        val_in_epoch = set(int(v) for v in val_schedule(n_batches))
+        seed = int(getattr(self.args, "seed", 0) or 0)
+        best_valid = 0.
+        state = dict(pending=0, train_iter=0)
+
+        def validate(epoch):
+            nonlocal best_valid
+            self._flush_losses(state)
+            valid_score = self.evaluate(eval_tuple)
+            self.valid_scores.append(valid_score)
+            if valid_score > best_valid:
+                best_valid = valid_score
+                self.save("BEST")
+            return valid_score
+
+        for epoch in range(self.args.epochs):
+            if resident:
+                order = loader.order(epoch, shuffle=True, seed=seed, drop_last=True, batch_size=self.B)
+                batches = range(n_batches)
+            else:
+                batches, ques_ids = loader, []
+            for i, item in enumerate(batches):
+                if resident:
+                    tr = self._engine(lambda: self._store_batch(loader, order[:self.B]), self.B, n_batches)
+                    tr.load_resident(loader, i * self.B)
+                else:
+                    batch = self._device_batch(item)
+                    tr = self._engine(lambda: batch, batch["target"].shape[0], n_batches)
+                    tr.load_batch(batch)
+                    ques_ids.extend(item[0].tolist() if torch.is_tensor(item[0]) else item[0])
+                if i == 0:
+                    tr.answer_log.reset()  # nothing has been logged in this epoch: the plain pass below is its first append
+                tr.iteration(pick_branch(self.args.delta, model=self.model))
+                state["pending"] += 1
+                if state["pending"] == self.window:
+                    self._flush_losses(state)
+                if i in val_in_epoch and eval_tuple is not None:
+                    valid_score = validate(epoch)
+                    if self.writer is not None:
+                        self.writer.add_scalar('Val/acc', valid_score, epoch)
+                    print(f"\nEpoch {epoch}: Iter {i}: "
+                          f"Valid {valid_score * 100.:.2f}\n"
+                          f"Epoch {epoch}: Iter {i}: "
+                          f"Best {best_valid * 100.:.2f}\n")
+            self._flush_losses(state)
+            # *compute train score*
+            log = self.trainer.answer_log
+            if resident:
+                train_score = log.score_store(loader, order=loader._order, keep=loader.keep_mask(order))["score"] * 100.
+            else:
+                train_score = evaluator.evaluate(to_quesid2ans(ques_ids, log.read()[0], dset.label2ans)) * 100.
+            valid_score = None
+            if self.writer is not None:
+                self._print_lr()
+                self.writer.add_scalar('Train/acc', train_score, epoch)
+            # *Do Validation*
+            if eval_tuple is not None:
+                valid_score = validate(epoch)
+                self.save(f"BEST_{epoch}")
+                if self.writer is not None:
+                    self.writer.add_scalar('Val/acc', valid_score, epoch)
+            self.history.append(dict(epoch=epoch, train=train_score, valid=valid_score, best=best_valid))
+            log_str = self._epoch_lines(epoch, train_score, valid_score, best_valid)
+            print(log_str, end='')
+            with open(self.output + "/log.log", 'a') as f:
+                f.write(log_str)
+                f.flush()
+        if self.writer is not None and hasattr(self.writer, "close"):
+            self.writer.close()
+
+    def predict(self, eval_tuple, dump=None):
+        """``{question_id: answer}`` of a split (src/vqa/vqacpv2.py:315-339): the module's ``predict`` through this driver's
+        one captured predictor and its answer log"""
+        dset, loader, evaluator = _tuple(eval_tuple)
+        self.sweeps += 1
+        return predict(self.model, (dset, loader, evaluator), dump, predictor=self._predictor(loader),
+                       resident=loader if _is_store(loader) else None)
+
+    def evaluate(self, eval_tuple, dump=None, by_group=False):
+        """the evaluator's score of a split as a float (src/vqa/vqacpv2.py:341-344).  With a resident store and no ``dump``
+        the sweep's answers never leave the device: ``score_store`` scores the log against the store's tables with the keep
+        mask of its data set order.  ``by_group``: ``{"all": score, name: accuracy, ...}`` over the store's groups (no entry
+        for a group without samples); the host path has no groups."""
+        dset, loader, evaluator = _tuple(eval_tuple)
+        if not _is_store(loader) or dump is not None:
+            if by_group:
+                raise ValueError("%s.evaluate: by_group needs a resident store with groups and no dump" % type(self).__name__)
+            return evaluator.evaluate(self.predict(eval_tuple, dump))
+        pred = self._predictor(loader)
+        self.sweeps += 1
+        n = len(loader)
+        loader.order(0, shuffle=False, drop_last=False)
+        pred.log.reset()
+        for start in range(0, n, pred.B):
+            pred.push_resident(loader, start, min(pred.B, n - start))
+        res = pred.log.score_store(loader, keep=loader.keep_mask(), by_group=by_group)
+        return dict(res["by_group"], all=res["score"]) if by_group else res["score"]
+
+    def oracle_score(self, data_tuple):
+        """the score of always answering a target's arg-max (src/vqa/vqacpv2.py:346-359): the target rows are gathered on
+        the device and ``ops.answer_pick`` takes them as if they were logits"""
+        from .. import ops
+        from ..answers import to_quesid2ans
+        dset, loader, evaluator = _tuple(data_tuple)
+        pred = self._predictor(loader)
+        log = pred.log
+        log.reset()
+        if _is_store(loader):
+            n, s = len(loader), pred.static
+            tgt = torch.zeros(pred.B, loader.A, device=self.device)
+            loader.order(0, shuffle=False, drop_last=False)
+            for start in range(0, n, pred.B):
+                b = min(pred.B, n - start)
+                loader.fill(dict(feats=s["feats"], boxes=s["boxes"], input_ids=s["ids"][0], input_mask=s["ids"][1],
+                                 segment_ids=s["ids"][2], target=tgt), start, b)
+                log.note(b)
+                ops.answer_pick(tgt[:b], log)
+            return log.score_store(loader, keep=loader.keep_mask())["score"]
+        ques_ids = []
+        for item in loader:
+            target = item[4].to(self.device).float().contiguous()
+            log.note(target.shape[0])
+            ops.answer_pick(target, log)
+            ques_ids.extend(item[0].tolist() if torch.is_tensor(item[0]) else item[0])
+        return evaluator.evaluate(to_quesid2ans(ques_ids, log.read()[0], dset.label2ans))
+
+    def save(self, name):
+        import os
+        torch.save(self.model.state_dict(), os.path.join(self.output, "%s.pth" % name))
+
+    def load(self, path):
+        print("Load model from %s" % path)
+        state_dict = torch.load("%s.pth" % path, map_location="cpu", weights_only=True)
+        self.model.load_state_dict(state_dict)
+
+
+class VQA(FineTuner):
+    """``class VQA`` of src/vqa/vqacpv2.py:70-368: plain pass first, KL weight 8, ``total_loss`` over the batch size"""
+
+
 def save_training_state(path, model, optim, **extra):
     """everything an exact resume needs, which ``VQA.save`` (src/vqa/vqacpv2.py:361-363, model weights only) leaves
     out: BertAdam moments and step counters (reference state layout), the dropout / noise Philox state, the host
