@@ -1397,6 +1397,82 @@ typedef struct xggm_train_log {
 int xggm_train_log_append(const float* const* src, const float* mul, int n, int kind, const int64_t* step,
                           xggm_train_log* log, xggm_stream_t stream);
 
+/* xggm_tokenize_wordpiece: sentences -> token ids for a whole corpus in ONE launch: what the host does per sentence with
+ * BertTokenizer.tokenize(sent.strip()) (src/lxrt/tokenization.py:72-348) followed by convert_sents_to_features
+ * (src/lxrt/entry.py:37-72; src/pretrain/lxmert_pretrain.py:149 for the pre-training set) -- clean the text, put spaces
+ * around CJK characters, split on whitespace and pass never_split tokens through untouched (:188-207), lower-case, NFD and
+ * drop Mn (:209-218), split on punctuation (:220-240), greedy longest-match-first WordPiece with "##" continuations where a
+ * word of more than XGGM_TOKENIZE_MAX_WORD code points or with an unmatched remainder is [UNK] (:299-348), keep T - 2
+ * tokens, add [CLS] and [SEP], pad with zeros.  Integer work only: every output is exact.
+ *   bytes [n_bytes] uint8: the sentences' UTF-8 one behind the other; offsets [n + 1] int64 (device): sentence i is
+ *   bytes[offsets[i] : offsets[i + 1]].  host_offsets: the same n + 1 values in HOST memory, read here before the launch
+ *   (they are what is refused below); the kernel holds every read inside [offsets[i], offsets[i + 1]) and inside the buffer.
+ * Tables, built on the host (xggm_amd.lxrt.tokenization.device_tables):
+ *   cp_table [0x110000] uint32, one entry per code point: bits 0-2 the action (0 keep, 1 drop: U+0000, U+FFFD, Cc / Cf but
+ *     \t \n \r; 2 whitespace: " \t\n\r", Zs, U+2028, U+2029; 3 CJK: a token of its own; 4 HOST, see below), bits 3-4 the
+ *     length nf of the folded sequence [c for c in NFD(lower(cp)) if category(c) != "Mn"] (0 .. 3), bits 5-7 "folded
+ *     character f is punctuation", bits 8-28 the folded code point (nf == 1) or the index of nf entries of cp_ext (nf > 1).
+ *   cp_ext [n_ext] uint32: the folded sequences longer than one.
+ *   init_slots [init_cap, 4], cont_slots [cont_cap, 4] uint32: open-addressing (linear probing) hash tables over the
+ *     vocabulary -- every token under its own spelling, and every "##x" token under x -- a slot is {hash >> 32, id, offset
+ *     into blob, length}, id -1 = empty; the capacities are powers of two and at least one slot is empty.  The hash of code
+ *     points c_0 .. c_k is h = (.. ((c_0 + 1) M + (c_1 + 1)) M ..) + (c_k + 1) modulo 2^64 with M = XGGM_TOKENIZE_HASH_MUL, the
+ *     first slot (h ^ (h >> 32)) & (cap - 1).  Dropping the last code point is (h - (c_k + 1)) * XGGM_TOKENIZE_HASH_MUL_INV,
+ *     so the longest-match loop walks the candidates of a word without a prefix array.  A hit counts only after the code
+ *     points in blob [n_blob] uint32 compare equal: a collision can cost a probe, never a wrong id.
+ *   never_cps, never_off [n_never + 1] int32: the code points of the never_split tokens (n_never <= XGGM_TOKENIZE_MAX_NEVER).
+ *   cls_id, sep_id, unk_id: the ids of [CLS], [SEP], [UNK].
+ * Outputs, each may be NULL (not all), every element is written:
+ *   ids [n, T] int32, len [n] int32 (tokens with [CLS] and [SEP]): the q_ids / q_len layout of the resident stores;
+ *   block [3, n, T] int64: input_ids, input_mask, segment_ids, what SentenceBatcher returns;
+ *   flags [n] uint8: bit 0 = the row needs the host: up to where the sentence stopped it holds a HOST code point or a
+ *     malformed or cut-off UTF-8 sequence (such a byte is dropped); the row is written all the same, with ids of the tables;
+ *   flagged int32 [1]: += the number of flagged rows (one integer atomic add per flagged row; the caller zeroes it).
+ * HOST code points: the two effects of the host's fold that are not a function of one code point -- U+03A3, whose
+ * lower-case form depends on its neighbours (final sigma), and the code points whose fold keeps a character of non-zero
+ * canonical combining class, which NFD may reorder against a neighbour of the same kind.
+ * A sentence stops once T - 2 tokens exist (the word that reaches the limit is finished first: it may still become ONE
+ * [UNK]); what lies behind that point is not read.
+ * One launch, one thread per sentence, workgroups of one wave; the only runtime-indexed scratch, the folded code points of
+ * the word in flight (XGGM_TOKENIZE_MAX_WORD x 64 dwords), lives in LDS, so xggm_tokenize_workspace_bytes(n, T) is 0 and
+ * nothing is allocated.  No host synchronisation.
+ * Refused before any launch: a null struct, a null bytes (with n_bytes > 0) / offsets / host_offsets / cp_table / blob /
+ * init_slots / cont_slots, every output null, n < 1, T < 2, offsets that are negative or fall ("not monotonic") or lie past
+ * n_bytes, a capacity that is not a power of two, n_never outside [0, MAX_NEVER], offsets / block not 8-byte aligned, ids /
+ * len / flagged or a table not 4-byte aligned, slots not 16-byte aligned. */
+#define XGGM_TOKENIZE_MAX_WORD 100
+#define XGGM_TOKENIZE_MAX_NEVER 8
+#define XGGM_TOKENIZE_HASH_MUL 0x9E3779B97F4A7C15ull
+#define XGGM_TOKENIZE_HASH_MUL_INV 0xF1DE83E19937733Dull
+typedef struct xggm_tokenize_args {
+    const uint8_t* bytes;         /* [n_bytes] */
+    int64_t n_bytes;
+    const int64_t* offsets;       /* [n + 1] device */
+    const int64_t* host_offsets;  /* [n + 1] host */
+    int64_t n;
+    int T;
+    const uint32_t* cp_table;     /* [0x110000] */
+    const uint32_t* cp_ext;       /* [n_ext] */
+    int64_t n_ext;
+    const uint32_t* init_slots;   /* [init_cap, 4] */
+    int64_t init_cap;
+    const uint32_t* cont_slots;   /* [cont_cap, 4] */
+    int64_t cont_cap;
+    const uint32_t* blob;         /* [n_blob] */
+    int64_t n_blob;
+    const uint32_t* never_cps;
+    const int32_t* never_off;     /* [n_never + 1] */
+    int n_never;
+    int32_t cls_id, sep_id, unk_id;
+    int32_t* ids;                 /* [n, T] out or NULL */
+    int32_t* len;                 /* [n] out or NULL */
+    int64_t* block;               /* [3, n, T] out or NULL */
+    uint8_t* flags;               /* [n] out or NULL */
+    int32_t* flagged;             /* [1] in/out or NULL */
+} xggm_tokenize_args;
+int xggm_tokenize_wordpiece(const xggm_tokenize_args* args, xggm_stream_t stream);
+size_t xggm_tokenize_workspace_bytes(int64_t n, int T);
+
 /* ---- utilities ---------------------------------------------------------------------------*/
 int xggm_rng_advance(uint64_t* rng, uint64_t by, xggm_stream_t stream);
 int xggm_cast_f32_to_bf16(const float* x, void* out, int64_t n, xggm_stream_t stream);

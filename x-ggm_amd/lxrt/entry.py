@@ -154,10 +154,22 @@ class LXRTEncoderFeature(nn.Module):
             self._batcher = SentenceBatcher(self.tokenizer, self.max_seq_length)
         return self._batcher
 
+    def enable_device_tokenizer(self, device=None):
+        """from now on a string-fed ``forward`` tokenises on the device: one copy of the packed sentences and one launch
+        (``DeviceTokenizer.features``) instead of the host batcher.  ``device``: default the model's.  -> the tokenizer"""
+        from .tokenization import DeviceTokenizer
+        if self.tokenizer is None:
+            raise RuntimeError("no tokenizer: pass vocab_path/tokenizer before enabling the device tokenizer")
+        device = device if device is not None else next(self.model.parameters()).device
+        self._device_tokenizer = DeviceTokenizer(self.tokenizer, device)
+        return self._device_tokenizer
+
     def forward(self, sents, feats, visual_attention_mask=None):
         device = feats[0].device
         if isinstance(sents, (tuple, list)) and len(sents) == 3 and torch.is_tensor(sents[0]):
             input_ids, input_mask, segment_ids = (t.to(device) for t in sents)
+        elif getattr(self, "_device_tokenizer", None) is not None:
+            input_ids, input_mask, segment_ids = (t.to(device) for t in self._device_tokenizer.features(sents, self.max_seq_length))
         else:
             input_ids, input_mask, segment_ids = self.batcher(sents, device)
         feat_seq, output = self.model(input_ids, segment_ids, input_mask, visual_feats=feats,

@@ -2645,6 +2645,74 @@ def pretrain_gather(tables, order, start, B, out, match_rate=None, rng=None, sid
     return out
 
 
+# ----------------------------------------------------------------------------- tokenisation
+class TokenizeArgs(_ct.Structure):
+    """mirror of ``xggm_tokenize_args`` (include/xggm.h)"""
+    _fields_ = [("bytes", _ct.c_void_p), ("n_bytes", _ct.c_int64), ("offsets", _ct.c_void_p), ("host_offsets", _ct.c_void_p),
+                ("n", _ct.c_int64), ("T", _ct.c_int), ("cp_table", _ct.c_void_p), ("cp_ext", _ct.c_void_p), ("n_ext", _ct.c_int64),
+                ("init_slots", _ct.c_void_p), ("init_cap", _ct.c_int64), ("cont_slots", _ct.c_void_p), ("cont_cap", _ct.c_int64),
+                ("blob", _ct.c_void_p), ("n_blob", _ct.c_int64), ("never_cps", _ct.c_void_p), ("never_off", _ct.c_void_p),
+                ("n_never", _ct.c_int), ("cls_id", _ct.c_int32), ("sep_id", _ct.c_int32), ("unk_id", _ct.c_int32),
+                ("ids", _ct.c_void_p), ("len", _ct.c_void_p), ("block", _ct.c_void_p), ("flags", _ct.c_void_p),
+                ("flagged", _ct.c_void_p)]
+
+
+TOKENIZE_OUTPUTS = ("ids", "len", "block", "flags", "flagged")
+TOKENIZE_TABLES = ("cp_table", "cp_ext", "init_slots", "cont_slots", "blob", "never_cps", "never_off")
+
+
+def tokenize_wordpiece(data, offsets, host_offsets, T, tables, outputs=("ids", "len", "flags", "flagged"), out=None):
+    """WordPiece token ids of n sentences in ONE launch; contract: xggm_tokenize_wordpiece in xggm.h.  ``data`` uint8
+    [n_bytes]: the sentences' UTF-8; ``offsets`` int64 [n + 1] on the device and ``host_offsets``, the same values as a
+    numpy int64 array (checked on the host before the launch); ``tables``: the device tensors and ids of
+    ``lxrt.tokenization.DeviceTokenizer.tables``.  ``outputs``: which of ``TOKENIZE_OUTPUTS`` to produce -- ids int32
+    [n, T], len int32 [n], block int64 [3, n, T] (input_ids, input_mask, segment_ids), flags uint8 [n] (1: the row needs
+    the host tokenizer), flagged int32 [1] (their number; a fresh one starts at 0, a supplied one is added to) -- into
+    ``out`` (a dict) where it holds them.  -> dict of the outputs"""
+    import numpy as np
+    _c(data, torch.uint8, "data"), _c(offsets, torch.int64, "offsets")
+    dev = data.device
+    host_offsets = np.ascontiguousarray(host_offsets, dtype=np.int64)
+    n, T = offsets.numel() - 1, int(T)
+    if n < 1 or host_offsets.shape != (n + 1,):
+        raise ValueError("tokenize_wordpiece: offsets hold %d values, host_offsets %s" % (n + 1, host_offsets.shape))
+    if set(outputs) - set(TOKENIZE_OUTPUTS) or not outputs:
+        raise ValueError("tokenize_wordpiece: outputs %r, some of %r expected" % (outputs, TOKENIZE_OUTPUTS))
+    a = TokenizeArgs()
+    for k in TOKENIZE_TABLES:
+        _c(tables[k], torch.int32, k)
+        setattr(a, k, ptr(tables[k]))
+    if tables["init_slots"].dim() != 2 or tables["init_slots"].shape[1] != 4 or tables["cont_slots"].dim() != 2 \
+            or tables["cont_slots"].shape[1] != 4 or tables["cp_table"].numel() != 0x110000:
+        raise ValueError("tokenize_wordpiece: slots are [capacity, 4], cp_table holds 0x110000 entries")
+    a.n_ext, a.n_blob = min(int(tables["n_ext"]), tables["cp_ext"].numel()), min(int(tables["n_blob"]), tables["blob"].numel())
+    a.init_cap, a.cont_cap = tables["init_slots"].shape[0], tables["cont_slots"].shape[0]
+    a.n_never = tables["never_off"].numel() - 1
+    if tables["never_cps"].numel() < int(tables["never_end"]):
+        raise ValueError("tokenize_wordpiece: never_off points past never_cps")
+    a.cls_id, a.sep_id, a.unk_id = int(tables["cls_id"]), int(tables["sep_id"]), int(tables["unk_id"])
+    shapes = dict(ids=((n, T), torch.int32), len=((n,), torch.int32), block=((3, n, T), torch.int64),
+                  flags=((n,), torch.uint8), flagged=((1,), torch.int32))
+    res = {}
+    for k in outputs:
+        shape, dt = shapes[k]
+        t = (out or {}).get(k)
+        if t is None:
+            t = torch.zeros(1, device=dev, dtype=dt) if k == "flagged" else torch.empty(shape, device=dev, dtype=dt)
+        _c(t, dt, "out " + k)
+        if tuple(t.shape) != shape:
+            raise ValueError("tokenize_wordpiece: out %s is %s, %s expected" % (k, tuple(t.shape), shape))
+        res[k] = t
+        setattr(a, k, ptr(t))
+    for t in [offsets] + [tables[k] for k in TOKENIZE_TABLES] + list(res.values()):
+        if t.device != dev:
+            raise RuntimeError("tokenize_wordpiece: all operands must live on one device")
+    a.bytes, a.n_bytes, a.offsets, a.host_offsets = ptr(data), data.numel(), ptr(offsets), host_offsets.ctypes.data
+    a.n, a.T = n, T
+    call("xggm_tokenize_wordpiece", _ct.addressof(a), stream())
+    return res
+
+
 # ----------------------------------------------------------------------------- graph attention
 def gat_att_fwd(s, adj, alpha):
     _c(s, F32, "s"), _c(adj, F32, "adj")

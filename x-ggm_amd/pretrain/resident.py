@@ -22,6 +22,7 @@ import numpy as np
 import torch
 
 from .. import ops
+from ..lxrt.tokenization import DeviceTokenizer
 from ..tools.resident import ResidentDataset, host_feats
 from ..tools.shards import _bf16_bits
 from .lxmert_pretrain import SID_BASE, image_key
@@ -50,6 +51,9 @@ def pretrain_tables(examples, tokenizer, max_seq_length, max_labels, n_answers=N
     q_ids = np.zeros((n_q, T), dtype=np.int32)
     q_label, q_score = np.full((n_q, K), -1, dtype=np.int32), np.zeros((n_q, K), dtype=np.float32)
     shape = None
+    dev_ids = None
+    if isinstance(tokenizer, DeviceTokenizer):  # every sentence in one launch, one read-back; the checks below stay
+        dev_ids, dev_len = (t.cpu().numpy() for t in tokenizer.encode([ex.sent for ex in examples], T))
     for i, ex in enumerate(examples):
         key = image_key(ex)
         r = rows.get(key)
@@ -75,8 +79,11 @@ def pretrain_tables(examples, tokenizer, max_seq_length, max_labels, n_answers=N
                 raise ValueError("%s: example %r would be image row %d, rows must fit int32" % (who, ex.uid, r))
             per_image.append(arrs)
         q_row[i] = r
-        tokens = ["[CLS]"] + tokenizer.tokenize(ex.sent.strip())[:T - 2] + ["[SEP]"]
-        w = np.asarray(tokenizer.convert_tokens_to_ids(tokens), dtype=np.int64)
+        if dev_ids is not None:
+            w = dev_ids[i, :dev_len[i]].astype(np.int64)
+        else:
+            tokens = ["[CLS]"] + tokenizer.tokenize(ex.sent.strip())[:T - 2] + ["[SEP]"]
+            w = np.asarray(tokenizer.convert_tokens_to_ids(tokens), dtype=np.int64)
         if w.min() < 0 or (vocab_size is not None and w.max() >= vocab_size) or w.max() >= (1 << 31):
             raise ValueError("%s: example %r has a token id outside [0, %s)" % (who, ex.uid, vocab_size))
         q_ids[i, :len(w)], q_len[i] = w, len(w)

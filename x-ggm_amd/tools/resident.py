@@ -20,6 +20,7 @@ refuses CPU tensors like every other op.  Pre-training batches have a store of t
 import numpy as np
 import torch
 
+from ..lxrt.tokenization import DeviceTokenizer
 from .shards import _bf16_bits
 
 FIELDS = ("feats", "boxes", "adj_true", "input_ids", "input_mask", "segment_ids", "target", "bias_index", "sample")
@@ -49,8 +50,11 @@ def sample_tables(ts, batcher, A=None):
     if rows.shape != (n_q,) or rows.min() < 0 or rows.max() >= len(ts.shard):
         raise ValueError("ResidentDataset: image rows outside the shard's %d images" % len(ts.shard))
     q_ids, q_len, pairs = np.zeros((n_q, T), dtype=np.int32), np.zeros(n_q, dtype=np.int32), []
+    dev_ids = None
+    if isinstance(getattr(batcher, "tok", None), DeviceTokenizer):  # every question in one launch, one read-back
+        dev_ids, dev_len = (t.cpu().numpy() for t in batcher.tok.encode([d[ds.sent_key] for d in ts.data], T))
     for i, d in enumerate(ts.data):
-        ids = batcher.ids_of(d[ds.sent_key])
+        ids = dev_ids[i, :dev_len[i]] if dev_ids is not None else batcher.ids_of(d[ds.sent_key])
         if len(ids) > T:
             raise ValueError("ResidentDataset: question %r has %d tokens, max_seq_length is %d" % (d["question_id"], len(ids), T))
         q_ids[i, :len(ids)] = ids
