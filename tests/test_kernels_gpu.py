@@ -11,7 +11,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
-from helpers import assert_excess, gemm_excess, rel_err  # noqa: E402
+from helpers import AttnRef, assert_excess, attn_bwd_excess, attn_fwd_excess, gemm_excess, rel_err  # noqa: E402
 
 
 @pytest.fixture(scope="module")
@@ -251,6 +251,11 @@ def test_attention(ops, dt, Sq, Sk, masked):
     assert rel_err(dq, qa.grad) < tol(dt, 5e-5)
     assert rel_err(dkv[:, :H], ka.grad) < tol(dt, 5e-5)
     assert rel_err(dkv[:, H:], va.grad) < tol(dt, 5e-5)
+    # every element against the derived bound (helpers.AttnRef): bf16 storage runs the matrix-core kernels
+    R = AttnRef(q, k, v, mask, do, None, B, heads)
+    assert_excess(attn_fwd_excess(out, R, dt, dt == torch.bfloat16), "attn_fwd out")
+    for name, exc in attn_bwd_excess(dq, dkv[:, :H], dkv[:, H:], R, dt, dt == torch.bfloat16).items():
+        assert_excess(exc, "attn_bwd " + name)
 
 
 @pytest.mark.parametrize("dt", DTS)
@@ -283,6 +288,11 @@ def test_attention_dropout_consistency(ops, dt):
     ops.attn_bwd(q, k, v, None, do, dq, dk, dv, B, heads, Sq, Sk, p, rng, sid)
     assert rel_err(dq, qa.grad) < tol(dt, 5e-5) and rel_err(dk, ka.grad) < tol(dt, 5e-5)
     assert rel_err(dv, va.grad) < tol(dt, 5e-5)
+    # every element against the derived bound, the reference fed the exported keep-scales
+    R = AttnRef(q, k, v, None, do, mask, B, heads)
+    assert_excess(attn_fwd_excess(out, R, dt, dt == torch.bfloat16), "attn_fwd out (dropout)")
+    for name, exc in attn_bwd_excess(dq, dk, dv, R, dt, dt == torch.bfloat16).items():
+        assert_excess(exc, "attn_bwd %s (dropout)" % name)
     # a different offset gives a different mask
     ops.rng_advance(rng)
     m2 = ops.dropout_mask(B * heads * Sq * Sk, p, rng, sid, DEV).double().cpu()
