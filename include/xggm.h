@@ -195,7 +195,8 @@ size_t xggm_colsum_workspace_bytes(int M, int N);
 /* ---- attention core: src/lxrt/modeling.py:355-373 (BertAttention.forward after the
  * projections).  q/k/v/out rows of sample b start at row b*S of a matrix with the given row
  * stride (so fused-QKV buffers are addressed in place); head h occupies columns
- * [64h, 64h+64).  mask: additive [B,Sk] fp32 or NULL.  Sq, Sk <= 64, head_dim == 64.
+ * [64h, 64h+64).  mask: additive [B,Sk] fp32 or NULL.  Sq, Sk <= 64 through these four entry points (the grouped ones
+ * below take up to 128), head_dim == 64.
  * backward: dbq/dbk/dbv (NULL ok; dbk and dbv go together): fp32 [B][heads*64] PARTIAL rows with batch stride db_bs
  * elements -- row b receives the column sums of dq/dk/dv over sample b's rows, each element written once by the
  * (sample, head) workgroup that owns it, in a fixed order.  Summed over b into the query/key/value bias gradients by
@@ -219,7 +220,14 @@ int xggm_attn_bwd_bf16(const void* q, const void* k, const void* v, const float*
 /* Grouped form: independent attention problems (the language and the vision stream of a layer, or
  * the two directions of a cross-attention layer, src/lxrt/modeling.py:485-516) in one launch; two
  * problems share a grid, more are launched in consecutive pairs.  Fields as the arguments above;
- * the backward fields are ignored by the forward entry points. */
+ * the backward fields are ignored by the forward entry points.
+ * Limits: 1 <= Sq, Sk <= 128.  A problem with Sq > 64 or Sk > 64 ("long": attention_long.hip) is a launch of its own and
+ * ignores the prefetch ranges; the problems of at most 64 x 64 around it are paired, and the first pair carries the ranges,
+ * as if it were not there, so a group may mix both.  out8 (the e4m3 copy) is refused for a long problem.  Every problem of
+ * the group is checked before the first launch: a call that returns XGGM_ERR_ARG has launched nothing.  Same arithmetic
+ * contracts on both sides of 64: fixed summation order (no floating-point atomics), the dropout decision of probability
+ * (i, j) a function of element ((b * heads + h) * Sq + i) * Sk + j, a two-pass softmax over the whole row, fp32 arithmetic
+ * for fp32 storage and for bf16 storage whose pointers are not 16-byte aligned or whose strides are not multiples of 8. */
 typedef struct xggm_attn_problem {
     const void* q;
     const void* k;

@@ -13,12 +13,17 @@
 // bf16 matrix-core versions (attention_mfma.hip): one or two validated problems per launch
 int xggm_attn_fwd_mfma_group(const xggm_attn_problem* probs, int n, const uint64_t* rng, const PrefetchArgs& pf, hipStream_t st);
 int xggm_attn_bwd_mfma_group(const xggm_attn_problem* probs, int n, const uint64_t* rng, const PrefetchArgs& pf, hipStream_t st);
+// problems with 65 .. 128 rows on a side (attention_long.hip): one validated problem per launch
+int xggm_attn_fwd_long(const xggm_attn_problem& q, bool is_bf16, bool matrix_core, const uint64_t* rng, hipStream_t st);
+int xggm_attn_bwd_long(const xggm_attn_problem& q, bool is_bf16, bool matrix_core, const uint64_t* rng, hipStream_t st);
 
 namespace {
 
 constexpr int NT = 256;
 constexpr int D = 64;
 constexpr int LD = D + 4;  // float4-aligned rows, conflict-free 16-byte reads
+constexpr int SHORT_ROWS = 64;  // the kernels of this file and of attention_mfma.hip: a whole problem in one LDS tile
+constexpr int LONG_ROWS = 128;  // attention_long.hip, reached through the grouped entry points only
 bool g_attn_scalar = false;  // test hook (xggm_attn_set_scalar): bf16 on the scalar kernels
 
 inline bool mfma_ok(const void* a, const void* b, const void* c, const void* d, int64_t s0, int64_t s1, int64_t s2, int64_t s3) {
@@ -236,10 +241,16 @@ __global__ __launch_bounds__(NT) void attn_bwd_kernel(AttnArgs a, const T* d_out
     if (dbv) fold(cv, dbv);
 }
 
-int check(const char* who, const AttnArgs& a, int head_dim) {
+inline bool is_long(const xggm_attn_problem& q) { return q.Sq > SHORT_ROWS || q.Sk > SHORT_ROWS; }
+
+// max_rows: SHORT_ROWS for the plain entry points (their contract), LONG_ROWS for the grouped ones
+int check(const char* who, const AttnArgs& a, int head_dim, int max_rows) {
     XGGM_REQUIRE(head_dim == D, "%s: head_dim %d != 64", who, head_dim);
     XGGM_REQUIRE(a.B > 0 && a.heads > 0 && a.Sq > 0 && a.Sk > 0, "%s: empty problem", who);
-    XGGM_REQUIRE(a.Sq <= 64 && a.Sk <= 64, "%s: Sq=%d Sk=%d exceed the 64-row LDS tile", who, a.Sq, a.Sk);
+    if (max_rows <= SHORT_ROWS)
+        XGGM_REQUIRE(a.Sq <= 64 && a.Sk <= 64, "%s: Sq=%d Sk=%d exceed the 64-row LDS tile", who, a.Sq, a.Sk);
+    XGGM_REQUIRE(a.Sq <= LONG_ROWS && a.Sk <= LONG_ROWS, "%s: Sq=%d Sk=%d exceed the 128 rows the attention core serves", who,
+                 a.Sq, a.Sk);
     XGGM_REQUIRE(a.q && a.k && a.v, "%s: null pointer", who);
     XGGM_REQUIRE(a.q_rs % 4 == 0 && a.k_rs % 4 == 0 && a.v_rs % 4 == 0 && a.o_rs % 4 == 0, "%s: row strides must be multiples of 4",
                  who);
@@ -255,19 +266,32 @@ inline AttnArgs args_of(const xggm_attn_problem& q, const uint64_t* rng) {
 // problems that can run on the matrix-core kernels are launched in pairs (the first pair carries `prefetch`), the rest one by one
 template <typename T>
 int attn_fwd_grouped(const xggm_attn_problem* probs, int n, int head_dim, const uint64_t* rng, const xggm_prefetch* prefetch,
-                     hipStream_t st) {
+                     hipStream_t st, int max_rows) {
     XGGM_REQUIRE(probs && n > 0, "xggm_attn_fwd: no problems");
     PrefetchArgs pf;
     if (int e = xggm_prefetch_args(prefetch, &pf, "xggm_attn_fwd")) return e;
+    for (int i = 0; i < n; ++i) {  // every problem is checked before the first launch
+        const xggm_attn_problem& q = probs[i];
+        if (int e = check("xggm_attn_fwd", args_of(q, rng), head_dim, max_rows)) return e;
+        XGGM_REQUIRE(q.out, "xggm_attn_fwd: null output");
+        XGGM_REQUIRE(!q.out8 || (sizeof(T) == 2 && reinterpret_cast<uintptr_t>(q.out8) % 8 == 0),
+                     "xggm_attn_fwd: the e4m3 output copy needs bf16 storage and an 8-byte aligned buffer");
+        XGGM_REQUIRE(!q.out8 || mfma_ok(q.q, q.k, q.v, q.out, q.q_rs, q.k_rs, q.v_rs, q.o_rs),
+                     "xggm_attn_fwd: the e4m3 output copy is written by the matrix-core kernel only (16-byte aligned operands, "
+                     "strides multiples of 8)");
+        XGGM_REQUIRE(!q.out8 || !is_long(q), "xggm_attn_fwd: the e4m3 output copy is written for problems of at most 64 rows "
+                                             "(Sq=%d Sk=%d)", q.Sq, q.Sk);
+    }
     xggm_attn_problem pend[2];
     int np = 0;
     for (int i = 0; i < n; ++i) {
         const xggm_attn_problem& q = probs[i];
         const AttnArgs a = args_of(q, rng);
-        if (int e = check("xggm_attn_fwd", a, head_dim)) return e;
-        XGGM_REQUIRE(q.out, "xggm_attn_fwd: null output");
-        XGGM_REQUIRE(!q.out8 || (sizeof(T) == 2 && reinterpret_cast<uintptr_t>(q.out8) % 8 == 0),
-                     "xggm_attn_fwd: the e4m3 output copy needs bf16 storage and an 8-byte aligned buffer");
+        if (is_long(q)) {  // the short problems around it are paired as if it were not there
+            if (int e = xggm_attn_fwd_long(q, sizeof(T) == 2, mfma_ok(q.q, q.k, q.v, q.out, q.q_rs, q.k_rs, q.v_rs, q.o_rs), rng, st))
+                return e;
+            continue;
+        }
         if (sizeof(T) == 2 && mfma_ok(q.q, q.k, q.v, q.out, q.q_rs, q.k_rs, q.v_rs, q.o_rs)) {
             pend[np++] = q;
             if (np == 2 || i == n - 1) {
@@ -277,8 +301,6 @@ int attn_fwd_grouped(const xggm_attn_problem* probs, int n, int head_dim, const 
             }
             continue;
         }
-        XGGM_REQUIRE(!q.out8, "xggm_attn_fwd: the e4m3 output copy is written by the matrix-core kernel only (16-byte "
-                              "aligned operands, strides multiples of 8)");
         const size_t lds = sizeof(float) * ((size_t)(q.Sq + 2 * q.Sk) * LD + 2 * (size_t)q.Sq * (q.Sk + 1));
         hipLaunchKernelGGL((attn_fwd_kernel<T>), dim3(q.B * q.heads), dim3(NT), lds, st, a, (T*)q.out);
         if (int e = xggm_check_launch("xggm_attn_fwd")) return e;
@@ -289,23 +311,32 @@ int attn_fwd_grouped(const xggm_attn_problem* probs, int n, int head_dim, const 
 
 template <typename T>
 int attn_bwd_grouped(const xggm_attn_problem* probs, int n, int head_dim, const uint64_t* rng, const xggm_prefetch* prefetch,
-                     hipStream_t st) {
+                     hipStream_t st, int max_rows) {
     XGGM_REQUIRE(probs && n > 0, "xggm_attn_bwd: no problems");
     PrefetchArgs pf;
     if (int e = xggm_prefetch_args(prefetch, &pf, "xggm_attn_bwd")) return e;
-    xggm_attn_problem pend[2];
-    int np = 0;
-    for (int i = 0; i < n; ++i) {
+    for (int i = 0; i < n; ++i) {  // every problem is checked before the first launch
         const xggm_attn_problem& q = probs[i];
-        const AttnArgs a = args_of(q, rng);
-        if (int e = check("xggm_attn_bwd", a, head_dim)) return e;
+        if (int e = check("xggm_attn_bwd", args_of(q, rng), head_dim, max_rows)) return e;
         XGGM_REQUIRE(q.d_out && q.dq && q.dk && q.dv, "xggm_attn_bwd: null pointer");
         XGGM_REQUIRE(q.dq_rs % 4 == 0 && q.dk_rs % 4 == 0 && q.dv_rs % 4 == 0, "xggm_attn_bwd: row strides must be multiples of 4");
         XGGM_REQUIRE((q.dbk == nullptr) == (q.dbv == nullptr), "xggm_attn_bwd: dbk and dbv go together");
         XGGM_REQUIRE(!(q.dbq || q.dbk) || q.B == 1 || q.db_bs >= (int64_t)q.heads * D,
                      "xggm_attn_bwd: the bias-gradient partial rows need a batch stride db_bs >= heads * 64 (got %lld)",
                      (long long)q.db_bs);
+    }
+    xggm_attn_problem pend[2];
+    int np = 0;
+    for (int i = 0; i < n; ++i) {
+        const xggm_attn_problem& q = probs[i];
+        const AttnArgs a = args_of(q, rng);
         const bool grads8 = (reinterpret_cast<uintptr_t>(q.dq) | reinterpret_cast<uintptr_t>(q.dk) | reinterpret_cast<uintptr_t>(q.dv)) % 8 == 0;
+        if (is_long(q)) {  // the short problems around it are paired as if it were not there
+            if (int e = xggm_attn_bwd_long(q, sizeof(T) == 2, grads8 && mfma_ok(q.q, q.k, q.v, q.d_out, q.q_rs, q.k_rs, q.v_rs, q.o_rs),
+                                           rng, st))
+                return e;
+            continue;
+        }
         if (sizeof(T) == 2 && grads8 && mfma_ok(q.q, q.k, q.v, q.d_out, q.q_rs, q.k_rs, q.v_rs, q.o_rs)) {  // 8-byte gradient stores
             pend[np++] = q;
             if (np == 2 || i == n - 1) {
@@ -333,7 +364,7 @@ int attn_fwd(const void* q, const void* k, const void* v, const float* mask, voi
     pr.B = B; pr.heads = heads; pr.Sq = Sq; pr.Sk = Sk;
     pr.q_rs = q_rs; pr.k_rs = k_rs; pr.v_rs = v_rs; pr.o_rs = o_rs;
     pr.scale = scale; pr.p = p; pr.sid = sid;
-    return attn_fwd_grouped<T>(&pr, 1, head_dim, rng, nullptr, st);
+    return attn_fwd_grouped<T>(&pr, 1, head_dim, rng, nullptr, st, SHORT_ROWS);
 }
 
 template <typename T>
@@ -349,7 +380,7 @@ int attn_bwd(const void* q, const void* k, const void* v, const float* mask, con
     pr.d_out = d_out; pr.dq = dq; pr.dk = dk; pr.dv = dv;
     pr.dq_rs = dq_rs; pr.dk_rs = dk_rs; pr.dv_rs = dv_rs;
     pr.dbq = dbq; pr.dbk = dbk; pr.dbv = dbv; pr.db_bs = db_bs;
-    return attn_bwd_grouped<T>(&pr, 1, head_dim, rng, nullptr, st);
+    return attn_bwd_grouped<T>(&pr, 1, head_dim, rng, nullptr, st, SHORT_ROWS);
 }
 
 }  // namespace
@@ -372,11 +403,11 @@ int attn_bwd(const void* q, const void* k, const void* v, const float* mask, con
     }                                                                                                                      \
     extern "C" int xggm_attn_fwd_grouped_##SUF(const xggm_attn_problem* probs, int n, int head_dim, const uint64_t* rng,   \
                                                const xggm_prefetch* prefetch, hipStream_t st) {                           \
-        return attn_fwd_grouped<T>(probs, n, head_dim, rng, prefetch, st);                                                 \
+        return attn_fwd_grouped<T>(probs, n, head_dim, rng, prefetch, st, LONG_ROWS);                                      \
     }                                                                                                                      \
     extern "C" int xggm_attn_bwd_grouped_##SUF(const xggm_attn_problem* probs, int n, int head_dim, const uint64_t* rng,   \
                                                const xggm_prefetch* prefetch, hipStream_t st) {                           \
-        return attn_bwd_grouped<T>(probs, n, head_dim, rng, prefetch, st);                                                 \
+        return attn_bwd_grouped<T>(probs, n, head_dim, rng, prefetch, st, LONG_ROWS);                                      \
     }
 
 ATTN_API(f32, float)

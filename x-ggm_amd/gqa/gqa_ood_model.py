@@ -6,4 +6,5 @@ MAX_GQA_LENGTH = 20
 
 class GQAModel(XGGMModel):
     def __init__(self, num_answers, gnn='GCN', n_layers=2, **kw):
-        super().__init__(num_answers, gnn=gnn, n_layers=n_layers, max_seq_length=MAX_GQA_LENGTH, **kw)
+        kw.setdefault("max_seq_length", MAX_GQA_LENGTH)
+        super().__init__(num_answers, gnn=gnn, n_layers=n_layers, **kw)

@@ -5,7 +5,7 @@ import os
 import torch
 import torch.nn as nn
 
-from .modeling import BertConfig, LXRTFeatureExtraction as VisualBertForLXRFeature, VISUAL_CONFIG
+from .modeling import BertConfig, LXRTFeatureExtraction as VisualBertForLXRFeature, VISUAL_CONFIG, check_sequence_limits
 from ..runtime import sync_weights
 
 
@@ -133,6 +133,7 @@ class LXRTEncoderFeature(nn.Module):
         self.tokenizer = tokenizer
         if config is None:
             config = BertConfig(30522)
+        check_sequence_limits("LXRTEncoderFeature", max_seq_length, config=config)
         self.model = VisualBertForLXRFeature(config, mode=mode)
         self._dim = config.hidden_size
 

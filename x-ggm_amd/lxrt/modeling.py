@@ -56,6 +56,22 @@ class VisualConfig(object):
 VISUAL_CONFIG = VisualConfig()
 
 
+MAX_ATTENTION_ROWS = 128  # tokens of a sentence / objects of an image the attention core serves (csrc/attention_long.hip)
+
+
+def check_sequence_limits(who, max_seq_length=None, n_objects=None, config=None):
+    """ValueError for a sentence length or an object count the encoder cannot run: more than MAX_ATTENTION_ROWS rows on a
+    side of the attention core, or more tokens than ``config``'s position table has rows.  Checked where the numbers
+    become known (construction; the shapes of a forward) instead of failing inside the first launch."""
+    for name, n in (("max_seq_length", max_seq_length), ("n_objects", n_objects)):
+        if n is not None and not 1 <= int(n) <= MAX_ATTENTION_ROWS:
+            raise ValueError("%s: %s = %d is outside 1 .. %d, the rows the attention core serves"
+                             % (who, name, int(n), MAX_ATTENTION_ROWS))
+    if max_seq_length is not None and config is not None and int(max_seq_length) > config.max_position_embeddings:
+        raise ValueError("%s: max_seq_length = %d exceeds the position table (max_position_embeddings = %d)"
+                         % (who, int(max_seq_length), config.max_position_embeddings))
+
+
 class BertConfig(object):
     """ref: src/lxrt/modeling.py:182-272"""
 
@@ -465,6 +481,8 @@ class LXRTModel(BertPreTrainedModel):
 
     def forward(self, input_ids, token_type_ids=None, attention_mask=None, visual_feats=None,
                 visual_attention_mask=None):
+        check_sequence_limits("LXRTModel.forward", input_ids.shape[1],
+                              visual_feats[0].shape[1] if visual_feats is not None else None, self.config)
         if attention_mask is None:
             attention_mask = torch.ones_like(input_ids)
         if token_type_ids is None:

@@ -236,6 +236,8 @@ class LXMERT:
     def __init__(self, max_seq_length, model, tokenizer, args=None, use_graph=True, log_every=None, max_labels=4,
                  vocab_size=None, mask_id=None, resident=False):
         from .. import param
+        from ..lxrt.modeling import check_sequence_limits
+        check_sequence_limits("LXMERT", max_seq_length, config=getattr(model, "config", None))
         self.max_seq_length, self.model, self.tokenizer = max_seq_length, model, tokenizer
         self.args = param.args if args is None else args
         self.use_graph, self.log_every, self.max_labels = use_graph, log_every, int(max_labels)

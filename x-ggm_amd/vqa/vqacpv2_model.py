@@ -4,6 +4,7 @@ import torch.nn as nn
 
 from ..heads import MLPHead, SigmoidHead
 from ..lxrt.entry import LXRTEncoderFeature
+from ..lxrt.modeling import check_sequence_limits
 from ..module.graph_generative_modeling import GCNGenerator, GINGenerator, GATGenerator
 from ..runtime import bind_root, sync_weights, root_of
 
@@ -21,6 +22,7 @@ class XGGMModel(nn.Module):
         if args is None:
             from ..param import args as default_args
             args = default_args
+        check_sequence_limits(type(self).__name__, max_seq_length, n_objects)
         self.lxrt_encoder = LXRTEncoderFeature(args, max_seq_length=max_seq_length, mode='lxr', config=config,
                                                tokenizer=tokenizer)
         hid_dim = self.lxrt_encoder.dim
@@ -74,4 +76,5 @@ class XGGMModel(nn.Module):
 
 class VQAModel(XGGMModel):
     def __init__(self, num_answers, gnn='GCN', n_layers=2, **kw):
-        super().__init__(num_answers, gnn=gnn, n_layers=n_layers, max_seq_length=MAX_VQA_LENGTH, **kw)
+        kw.setdefault("max_seq_length", MAX_VQA_LENGTH)
+        super().__init__(num_answers, gnn=gnn, n_layers=n_layers, **kw)
