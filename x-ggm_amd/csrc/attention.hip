@@ -7,63 +7,18 @@
 // P and the Philox dropout mask are recomputed.  Per-row softmax uses wave64 shuffle
 // reductions; fp32 math throughout.  These scalar kernels serve fp32 storage (exact parity
 // mode); bf16 storage runs the matrix-core versions of attention_mfma.hip.
-#include "common.h"
-#include "xggm.h"
-
-// bf16 matrix-core versions (attention_mfma.hip): one or two validated problems per launch
-int xggm_attn_fwd_mfma_group(const xggm_attn_problem* probs, int n, const uint64_t* rng, const PrefetchArgs& pf, hipStream_t st);
-int xggm_attn_bwd_mfma_group(const xggm_attn_problem* probs, int n, const uint64_t* rng, const PrefetchArgs& pf, hipStream_t st);
-// problems with 65 .. 128 rows on a side (attention_long.hip): one validated problem per launch
-int xggm_attn_fwd_long(const xggm_attn_problem& q, bool is_bf16, bool matrix_core, const uint64_t* rng, hipStream_t st);
-int xggm_attn_bwd_long(const xggm_attn_problem& q, bool is_bf16, bool matrix_core, const uint64_t* rng, hipStream_t st);
+// attention_common.h holds what this file shares with attention_mfma.hip and attention_long.hip: the argument structs,
+// load_tile / dot64 / fold_bias and the launch helper.  The grouped dispatcher at the end of this file decides which of
+// the three files serves a problem (route).
+#include "attention_common.h"
 
 namespace {
+using namespace attn;
 
 constexpr int NT = 256;
-constexpr int D = 64;
-constexpr int LD = D + 4;  // float4-aligned rows, conflict-free 16-byte reads
 constexpr int SHORT_ROWS = 64;  // the kernels of this file and of attention_mfma.hip: a whole problem in one LDS tile
 constexpr int LONG_ROWS = 128;  // attention_long.hip, reached through the grouped entry points only
 bool g_attn_scalar = false;  // test hook (xggm_attn_set_scalar): bf16 on the scalar kernels
-
-inline bool mfma_ok(const void* a, const void* b, const void* c, const void* d, int64_t s0, int64_t s1, int64_t s2, int64_t s3) {
-    return !g_attn_scalar &&
-           ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c) |
-             reinterpret_cast<uintptr_t>(d)) % 16 == 0) &&
-           s0 % 8 == 0 && s1 % 8 == 0 && s2 % 8 == 0 && s3 % 8 == 0;
-}
-
-struct AttnArgs {
-    const void *q, *k, *v;
-    const float* mask;  // additive [B, Sk] or null
-    int64_t q_rs, k_rs, v_rs, o_rs;  // row strides in elements
-    int B, heads, Sq, Sk;
-    float scale, p;
-    const uint64_t* rng;
-    uint32_t sid;
-};
-
-template <typename T>
-__device__ __forceinline__ void load_tile(float* lds, const T* base, int64_t rs, int rows, int tid) {
-    // rows x 64 elements, 16 chunks of 4 per row
-    for (int c = tid; c < rows * 16; c += NT) {
-        const int r = c >> 4, cc = (c & 15) * 4;
-        float t[4];
-        load4(base + (int64_t)r * rs + cc, t);
-        *reinterpret_cast<float4*>(lds + r * LD + cc) = make_float4(t[0], t[1], t[2], t[3]);
-    }
-}
-
-__device__ __forceinline__ float dot64(const float* a, const float* b) {
-    float s = 0.f;
-#pragma unroll
-    for (int c = 0; c < D; c += 4) {
-        const float4 x = *reinterpret_cast<const float4*>(a + c);
-        const float4 y = *reinterpret_cast<const float4*>(b + c);
-        s += x.x * y.x + x.y * y.y + x.z * y.z + x.w * y.w;
-    }
-    return s;
-}
 
 // scores + softmax (+ dropout scale matrix) into LDS.  P: probabilities, Dm: dropout scale
 // (only written when p > 0).  Wave w owns rows w, w+4, ...
@@ -110,9 +65,9 @@ template <typename T> __global__ __launch_bounds__(NT) void attn_fwd_kernel(Attn
     float* Vs = Ks + Sk * LD;
     float* P = Vs + Sk * LD;
     float* Dm = P + Sq * ldp;
-    load_tile<T>(Qs, (const T*)a.q + (int64_t)b * Sq * a.q_rs + h * D, a.q_rs, Sq, tid);
-    load_tile<T>(Ks, (const T*)a.k + (int64_t)b * Sk * a.k_rs + h * D, a.k_rs, Sk, tid);
-    load_tile<T>(Vs, (const T*)a.v + (int64_t)b * Sk * a.v_rs + h * D, a.v_rs, Sk, tid);
+    load_tile<NT>(Qs, (const T*)a.q + (int64_t)b * Sq * a.q_rs + h * D, a.q_rs, Sq, tid);
+    load_tile<NT>(Ks, (const T*)a.k + (int64_t)b * Sk * a.k_rs + h * D, a.k_rs, Sk, tid);
+    load_tile<NT>(Vs, (const T*)a.v + (int64_t)b * Sk * a.v_rs + h * D, a.v_rs, Sk, tid);
     __syncthreads();
     scores_softmax(a, Qs, Ks, P, Dm, b, h, tid);
     // O[i][c..c+3] = sum_j P[i][j] * D[i][j] * V[j][c..c+3]
@@ -122,11 +77,7 @@ template <typename T> __global__ __launch_bounds__(NT) void attn_fwd_kernel(Attn
         for (int j = 0; j < Sk; ++j) {
             float pj = P[i * ldp + j];
             if (a.p > 0.f) pj *= Dm[i * ldp + j];
-            const float4 vv = *reinterpret_cast<const float4*>(Vs + j * LD + c);
-            o[0] += pj * vv.x;
-            o[1] += pj * vv.y;
-            o[2] += pj * vv.z;
-            o[3] += pj * vv.w;
+            axpy4(o, pj, Vs + j * LD + c);
         }
         store4(out + ((int64_t)b * Sq + i) * a.o_rs + h * D + c, o);
     }
@@ -136,10 +87,7 @@ template <typename T>
 __global__ __launch_bounds__(NT) void attn_bwd_kernel(AttnArgs a, const T* d_out, T* dq, T* dk, T* dv, int64_t dq_rs,
                                                       int64_t dk_rs, int64_t dv_rs, float* dbq, float* dbk, float* dbv,
                                                       int64_t db_bs) {
-    // column sums of dQ / dK / dV over this sample's rows (bias gradients): every thread keeps the sums of ITS column
-    // group over its rows (NT % 16 == 0: a thread's columns never change), the threads of a column group are added in
-    // index order through `red`, and the result is a partial row of this (sample, head) nobody else writes
-    __shared__ float red[NT / 16][D];
+    __shared__ float red[NT / 16][D];  // bias gradients, see fold_bias
     float cq[4] = {0.f, 0.f, 0.f, 0.f}, ck[4] = {0.f, 0.f, 0.f, 0.f}, cv[4] = {0.f, 0.f, 0.f, 0.f};
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int tid = threadIdx.x;
@@ -152,10 +100,10 @@ __global__ __launch_bounds__(NT) void attn_bwd_kernel(AttnArgs a, const T* d_out
     float* P = dOs + Sq * LD;
     float* Dm = P + Sq * ldp;
     float* dS = Dm + Sq * ldp;
-    load_tile<T>(Qs, (const T*)a.q + (int64_t)b * Sq * a.q_rs + h * D, a.q_rs, Sq, tid);
-    load_tile<T>(Ks, (const T*)a.k + (int64_t)b * Sk * a.k_rs + h * D, a.k_rs, Sk, tid);
-    load_tile<T>(Vs, (const T*)a.v + (int64_t)b * Sk * a.v_rs + h * D, a.v_rs, Sk, tid);
-    load_tile<T>(dOs, d_out + (int64_t)b * Sq * a.o_rs + h * D, a.o_rs, Sq, tid);
+    load_tile<NT>(Qs, (const T*)a.q + (int64_t)b * Sq * a.q_rs + h * D, a.q_rs, Sq, tid);
+    load_tile<NT>(Ks, (const T*)a.k + (int64_t)b * Sk * a.k_rs + h * D, a.k_rs, Sk, tid);
+    load_tile<NT>(Vs, (const T*)a.v + (int64_t)b * Sk * a.v_rs + h * D, a.v_rs, Sk, tid);
+    load_tile<NT>(dOs, d_out + (int64_t)b * Sq * a.o_rs + h * D, a.o_rs, Sq, tid);
     __syncthreads();
     scores_softmax(a, Qs, Ks, P, Dm, b, h, tid);
     // dP[i][j] = D[i][j] * sum_c dO[i][c] V[j][c]
@@ -185,11 +133,7 @@ __global__ __launch_bounds__(NT) void attn_bwd_kernel(AttnArgs a, const T* d_out
         float o[4] = {0.f, 0.f, 0.f, 0.f};
         for (int j = 0; j < (valid ? Sk : 0); ++j) {
             const float s = dS[i * ldp + j];
-            const float4 kk = *reinterpret_cast<const float4*>(Ks + j * LD + c);
-            o[0] += s * kk.x;
-            o[1] += s * kk.y;
-            o[2] += s * kk.z;
-            o[3] += s * kk.w;
+            axpy4(o, s, Ks + j * LD + c);
         }
         if (valid) store4(dq + ((int64_t)b * Sq + i) * dq_rs + h * D + c, o);
 #pragma unroll
@@ -204,16 +148,8 @@ __global__ __launch_bounds__(NT) void attn_bwd_kernel(AttnArgs a, const T* d_out
             const float s = dS[i * ldp + j];
             float pj = P[i * ldp + j];
             if (a.p > 0.f) pj *= Dm[i * ldp + j];
-            const float4 qq = *reinterpret_cast<const float4*>(Qs + i * LD + c);
-            const float4 gg = *reinterpret_cast<const float4*>(dOs + i * LD + c);
-            ok[0] += s * qq.x;
-            ok[1] += s * qq.y;
-            ok[2] += s * qq.z;
-            ok[3] += s * qq.w;
-            ov[0] += pj * gg.x;
-            ov[1] += pj * gg.y;
-            ov[2] += pj * gg.z;
-            ov[3] += pj * gg.w;
+            axpy4(ok, s, Qs + i * LD + c);
+            axpy4(ov, pj, dOs + i * LD + c);
         }
         if (valid) {
             store4(dk + ((int64_t)b * Sk + j) * dk_rs + h * D + c, ok);
@@ -225,146 +161,149 @@ __global__ __launch_bounds__(NT) void attn_bwd_kernel(AttnArgs a, const T* d_out
             cv[e] += ov[e];
         }
     }
-    auto fold = [&](const float (&c4)[4], float* dst) {  // uniform: every thread of the workgroup calls it
-        __syncthreads();
-#pragma unroll
-        for (int e = 0; e < 4; ++e) red[tid >> 4][(tid & 15) * 4 + e] = c4[e];
-        __syncthreads();
-        if (tid < D) {
-            float s = 0.f;
-            for (int g = 0; g < NT / 16; ++g) s += red[g][tid];  // fixed order
-            dst[(int64_t)b * db_bs + h * D + tid] = s;
-        }
-    };
-    if (dbq) fold(cq, dbq);
-    if (dbk) fold(ck, dbk);
-    if (dbv) fold(cv, dbv);
+    const int64_t po = (int64_t)b * db_bs + h * D;  // this (sample, head)'s partial row
+    if (dbq) fold_bias<NT>(red, cq, dbq + po, tid);
+    if (dbk) fold_bias<NT>(red, ck, dbk + po, tid);
+    if (dbv) fold_bias<NT>(red, cv, dbv + po, tid);
 }
 
-inline bool is_long(const xggm_attn_problem& q) { return q.Sq > SHORT_ROWS || q.Sk > SHORT_ROWS; }
+// ---- which kernels serve a problem -------------------------------------------------------------------------------
+// bit 0: matrix cores (attention_mfma.hip, or the matrix-core kernels of attention_long.hip), bit 1: attention_long.hip
+enum Path { SHORT_SCALAR = 0, SHORT_MFMA = 1, LONG_SCALAR = 2, LONG_MFMA = 3 };
+constexpr int PATH_MFMA = 1, PATH_LONG = 2;
 
+// The only place that decides it.  Matrix cores: bf16 storage whose operands (q, k, v and out, in the backward dO) are
+// 16-byte aligned with row strides that are multiples of 8 -- the tiles are fetched in 16-byte chunks -- and, in the
+// backward, 8-byte aligned gradients (8-byte gradient stores); never under the xggm_attn_set_scalar hook.
+Path route(const xggm_attn_problem& q, bool is_bf16, bool backward) {
+    const auto bits = [](const void* p) { return reinterpret_cast<uintptr_t>(p); };
+    const bool operands16 = (bits(q.q) | bits(q.k) | bits(q.v) | bits(backward ? q.d_out : q.out)) % 16 == 0 && q.q_rs % 8 == 0 &&
+                            q.k_rs % 8 == 0 && q.v_rs % 8 == 0 && q.o_rs % 8 == 0;
+    const bool grads8 = !backward || (bits(q.dq) | bits(q.dk) | bits(q.dv)) % 8 == 0;
+    const bool mfma = is_bf16 && !g_attn_scalar && operands16 && grads8;
+    const bool is_long = q.Sq > SHORT_ROWS || q.Sk > SHORT_ROWS;
+    return Path((mfma ? PATH_MFMA : 0) | (is_long ? PATH_LONG : 0));
+}
+
+// ---- argument checks ---------------------------------------------------------------------------------------------
 // max_rows: SHORT_ROWS for the plain entry points (their contract), LONG_ROWS for the grouped ones
-int check(const char* who, const AttnArgs& a, int head_dim, int max_rows) {
+int check(const char* who, const xggm_attn_problem& q, const uint64_t* rng, int head_dim, int max_rows) {
     XGGM_REQUIRE(head_dim == D, "%s: head_dim %d != 64", who, head_dim);
-    XGGM_REQUIRE(a.B > 0 && a.heads > 0 && a.Sq > 0 && a.Sk > 0, "%s: empty problem", who);
+    XGGM_REQUIRE(q.B > 0 && q.heads > 0 && q.Sq > 0 && q.Sk > 0, "%s: empty problem", who);
     if (max_rows <= SHORT_ROWS)
-        XGGM_REQUIRE(a.Sq <= 64 && a.Sk <= 64, "%s: Sq=%d Sk=%d exceed the 64-row LDS tile", who, a.Sq, a.Sk);
-    XGGM_REQUIRE(a.Sq <= LONG_ROWS && a.Sk <= LONG_ROWS, "%s: Sq=%d Sk=%d exceed the 128 rows the attention core serves", who,
-                 a.Sq, a.Sk);
-    XGGM_REQUIRE(a.q && a.k && a.v, "%s: null pointer", who);
-    XGGM_REQUIRE(a.q_rs % 4 == 0 && a.k_rs % 4 == 0 && a.v_rs % 4 == 0 && a.o_rs % 4 == 0, "%s: row strides must be multiples of 4",
+        XGGM_REQUIRE(q.Sq <= 64 && q.Sk <= 64, "%s: Sq=%d Sk=%d exceed the 64-row LDS tile", who, q.Sq, q.Sk);
+    XGGM_REQUIRE(q.Sq <= LONG_ROWS && q.Sk <= LONG_ROWS, "%s: Sq=%d Sk=%d exceed the 128 rows the attention core serves", who,
+                 q.Sq, q.Sk);
+    XGGM_REQUIRE(q.q && q.k && q.v, "%s: null pointer", who);
+    XGGM_REQUIRE(q.q_rs % 4 == 0 && q.k_rs % 4 == 0 && q.v_rs % 4 == 0 && q.o_rs % 4 == 0, "%s: row strides must be multiples of 4",
                  who);
-    XGGM_REQUIRE(a.p >= 0.f && a.p < 1.f && (a.p == 0.f || a.rng), "%s: bad dropout arguments", who);
-    XGGM_REQUIRE((int64_t)a.B * a.heads < (1 << 30), "%s: grid too large", who);
+    XGGM_REQUIRE(q.p >= 0.f && q.p < 1.f && (q.p == 0.f || rng), "%s: bad dropout arguments", who);
+    XGGM_REQUIRE((int64_t)q.B * q.heads < (1 << 30), "%s: grid too large", who);
     return XGGM_OK;
 }
 
-inline AttnArgs args_of(const xggm_attn_problem& q, const uint64_t* rng) {
-    return AttnArgs{q.q, q.k, q.v, q.mask, q.q_rs, q.k_rs, q.v_rs, q.o_rs, q.B, q.heads, q.Sq, q.Sk, q.scale, q.p, rng, q.sid};
-}
-
-// problems that can run on the matrix-core kernels are launched in pairs (the first pair carries `prefetch`), the rest one by one
-template <typename T>
-int attn_fwd_grouped(const xggm_attn_problem* probs, int n, int head_dim, const uint64_t* rng, const xggm_prefetch* prefetch,
-                     hipStream_t st, int max_rows) {
-    XGGM_REQUIRE(probs && n > 0, "xggm_attn_fwd: no problems");
-    PrefetchArgs pf;
-    if (int e = xggm_prefetch_args(prefetch, &pf, "xggm_attn_fwd")) return e;
-    for (int i = 0; i < n; ++i) {  // every problem is checked before the first launch
-        const xggm_attn_problem& q = probs[i];
-        if (int e = check("xggm_attn_fwd", args_of(q, rng), head_dim, max_rows)) return e;
-        XGGM_REQUIRE(q.out, "xggm_attn_fwd: null output");
-        XGGM_REQUIRE(!q.out8 || (sizeof(T) == 2 && reinterpret_cast<uintptr_t>(q.out8) % 8 == 0),
-                     "xggm_attn_fwd: the e4m3 output copy needs bf16 storage and an 8-byte aligned buffer");
-        XGGM_REQUIRE(!q.out8 || mfma_ok(q.q, q.k, q.v, q.out, q.q_rs, q.k_rs, q.v_rs, q.o_rs),
-                     "xggm_attn_fwd: the e4m3 output copy is written by the matrix-core kernel only (16-byte aligned operands, "
-                     "strides multiples of 8)");
-        XGGM_REQUIRE(!q.out8 || !is_long(q), "xggm_attn_fwd: the e4m3 output copy is written for problems of at most 64 rows "
-                                             "(Sq=%d Sk=%d)", q.Sq, q.Sk);
-    }
-    xggm_attn_problem pend[2];
-    int np = 0;
-    for (int i = 0; i < n; ++i) {
-        const xggm_attn_problem& q = probs[i];
-        const AttnArgs a = args_of(q, rng);
-        if (is_long(q)) {  // the short problems around it are paired as if it were not there
-            if (int e = xggm_attn_fwd_long(q, sizeof(T) == 2, mfma_ok(q.q, q.k, q.v, q.out, q.q_rs, q.k_rs, q.v_rs, q.o_rs), rng, st))
-                return e;
-            continue;
-        }
-        if (sizeof(T) == 2 && mfma_ok(q.q, q.k, q.v, q.out, q.q_rs, q.k_rs, q.v_rs, q.o_rs)) {
-            pend[np++] = q;
-            if (np == 2 || i == n - 1) {
-                if (int e = xggm_attn_fwd_mfma_group(pend, np, rng, pf, st)) return e;
-                np = 0;
-                pf = PrefetchArgs{};
-            }
-            continue;
-        }
-        const size_t lds = sizeof(float) * ((size_t)(q.Sq + 2 * q.Sk) * LD + 2 * (size_t)q.Sq * (q.Sk + 1));
-        hipLaunchKernelGGL((attn_fwd_kernel<T>), dim3(q.B * q.heads), dim3(NT), lds, st, a, (T*)q.out);
-        if (int e = xggm_check_launch("xggm_attn_fwd")) return e;
-    }
-    if (np) return xggm_attn_fwd_mfma_group(pend, np, rng, pf, st);
+int check_fwd(const xggm_attn_problem& q, const uint64_t* rng, int head_dim, int max_rows, bool is_bf16) {
+    if (int e = check("xggm_attn_fwd", q, rng, head_dim, max_rows)) return e;
+    const Path r = route(q, is_bf16, false);
+    XGGM_REQUIRE(q.out, "xggm_attn_fwd: null output");
+    XGGM_REQUIRE(!q.out8 || (is_bf16 && reinterpret_cast<uintptr_t>(q.out8) % 8 == 0),
+                 "xggm_attn_fwd: the e4m3 output copy needs bf16 storage and an 8-byte aligned buffer");
+    XGGM_REQUIRE(!q.out8 || (r & PATH_MFMA),
+                 "xggm_attn_fwd: the e4m3 output copy is written by the matrix-core kernel only (16-byte aligned operands, "
+                 "strides multiples of 8)");
+    XGGM_REQUIRE(!q.out8 || !(r & PATH_LONG), "xggm_attn_fwd: the e4m3 output copy is written for problems of at most 64 rows "
+                                              "(Sq=%d Sk=%d)", q.Sq, q.Sk);
     return XGGM_OK;
 }
 
+int check_bwd(const xggm_attn_problem& q, const uint64_t* rng, int head_dim, int max_rows) {
+    if (int e = check("xggm_attn_bwd", q, rng, head_dim, max_rows)) return e;
+    XGGM_REQUIRE(q.d_out && q.dq && q.dk && q.dv, "xggm_attn_bwd: null pointer");
+    XGGM_REQUIRE(q.dq_rs % 4 == 0 && q.dk_rs % 4 == 0 && q.dv_rs % 4 == 0, "xggm_attn_bwd: row strides must be multiples of 4");
+    XGGM_REQUIRE((q.dbk == nullptr) == (q.dbv == nullptr), "xggm_attn_bwd: dbk and dbv go together");
+    XGGM_REQUIRE(!(q.dbq || q.dbk) || q.B == 1 || q.db_bs >= (int64_t)q.heads * D,
+                 "xggm_attn_bwd: the bias-gradient partial rows need a batch stride db_bs >= heads * 64 (got %lld)",
+                 (long long)q.db_bs);
+    return XGGM_OK;
+}
+
+// ---- the grouped dispatcher, forward and backward ----------------------------------------------------------------
+// A whole (sample, head) of a short scalar problem in the LDS of one workgroup.  These two launches do not go through
+// attn::launch: they have never asked for the large-LDS opt-in, although their fp32 images pass 48 KiB well inside the
+// 64 x 64 they serve (the 64 x 64 backward takes 117 KiB), and these launches have been accepted all along.  Whether
+// they should reserve as well is a separate question; this keeps them launching as they always have.
 template <typename T>
-int attn_bwd_grouped(const xggm_attn_problem* probs, int n, int head_dim, const uint64_t* rng, const xggm_prefetch* prefetch,
-                     hipStream_t st, int max_rows) {
-    XGGM_REQUIRE(probs && n > 0, "xggm_attn_bwd: no problems");
-    PrefetchArgs pf;
-    if (int e = xggm_prefetch_args(prefetch, &pf, "xggm_attn_bwd")) return e;
-    for (int i = 0; i < n; ++i) {  // every problem is checked before the first launch
-        const xggm_attn_problem& q = probs[i];
-        if (int e = check("xggm_attn_bwd", args_of(q, rng), head_dim, max_rows)) return e;
-        XGGM_REQUIRE(q.d_out && q.dq && q.dk && q.dv, "xggm_attn_bwd: null pointer");
-        XGGM_REQUIRE(q.dq_rs % 4 == 0 && q.dk_rs % 4 == 0 && q.dv_rs % 4 == 0, "xggm_attn_bwd: row strides must be multiples of 4");
-        XGGM_REQUIRE((q.dbk == nullptr) == (q.dbv == nullptr), "xggm_attn_bwd: dbk and dbv go together");
-        XGGM_REQUIRE(!(q.dbq || q.dbk) || q.B == 1 || q.db_bs >= (int64_t)q.heads * D,
-                     "xggm_attn_bwd: the bias-gradient partial rows need a batch stride db_bs >= heads * 64 (got %lld)",
-                     (long long)q.db_bs);
-    }
-    xggm_attn_problem pend[2];
-    int np = 0;
-    for (int i = 0; i < n; ++i) {
-        const xggm_attn_problem& q = probs[i];
-        const AttnArgs a = args_of(q, rng);
-        const bool grads8 = (reinterpret_cast<uintptr_t>(q.dq) | reinterpret_cast<uintptr_t>(q.dk) | reinterpret_cast<uintptr_t>(q.dv)) % 8 == 0;
-        if (is_long(q)) {  // the short problems around it are paired as if it were not there
-            if (int e = xggm_attn_bwd_long(q, sizeof(T) == 2, grads8 && mfma_ok(q.q, q.k, q.v, q.d_out, q.q_rs, q.k_rs, q.v_rs, q.o_rs),
-                                           rng, st))
-                return e;
-            continue;
-        }
-        if (sizeof(T) == 2 && grads8 && mfma_ok(q.q, q.k, q.v, q.d_out, q.q_rs, q.k_rs, q.v_rs, q.o_rs)) {  // 8-byte gradient stores
-            pend[np++] = q;
-            if (np == 2 || i == n - 1) {
-                if (int e = xggm_attn_bwd_mfma_group(pend, np, rng, pf, st)) return e;
-                np = 0;
-                pf = PrefetchArgs{};
-            }
-            continue;
-        }
-        const size_t lds = sizeof(float) * ((size_t)(2 * q.Sq + 2 * q.Sk) * LD + 3 * (size_t)q.Sq * (q.Sk + 1));
+int launch_short_scalar(bool backward, const xggm_attn_problem& q, const uint64_t* rng, hipStream_t st) {
+    const AttnArgs a = args_of(q, rng);
+    const size_t score = sizeof(float) * (size_t)q.Sq * (q.Sk + 1);  // P, Dm (and dS)
+    if (backward) {
+        const size_t lds = sizeof(float) * (size_t)(2 * q.Sq + 2 * q.Sk) * LD + 3 * score;
         hipLaunchKernelGGL((attn_bwd_kernel<T>), dim3(q.B * q.heads), dim3(NT), lds, st, a, (const T*)q.d_out, (T*)q.dq, (T*)q.dk,
                            (T*)q.dv, q.dq_rs, q.dk_rs, q.dv_rs, q.dbq, q.dbk, q.dbv, q.db_bs);
-        if (int e = xggm_check_launch("xggm_attn_bwd")) return e;
+    } else {
+        const size_t lds = sizeof(float) * (size_t)(q.Sq + 2 * q.Sk) * LD + 2 * score;
+        hipLaunchKernelGGL((attn_fwd_kernel<T>), dim3(q.B * q.heads), dim3(NT), lds, st, a, (T*)q.out);
     }
-    if (np) return xggm_attn_bwd_mfma_group(pend, np, rng, pf, st);
-    return XGGM_OK;
+    return xggm_check_launch(backward ? "xggm_attn_bwd" : "xggm_attn_fwd");
+}
+
+// every problem is checked before the first launch.  Problems that can run on the short matrix-core kernels are launched
+// in pairs (the first pair carries `prefetch`), the rest one by one; the short problems around a long or a scalar one
+// are paired as if it were not there.
+template <typename T>
+int run_grouped(bool backward, const xggm_attn_problem* probs, int n, int head_dim, const uint64_t* rng,
+                const xggm_prefetch* prefetch, hipStream_t st, int max_rows) {
+    constexpr bool is_bf16 = sizeof(T) == 2;
+    const char* who = backward ? "xggm_attn_bwd" : "xggm_attn_fwd";
+    XGGM_REQUIRE(probs && n > 0, "%s: no problems", who);
+    PrefetchArgs pf;
+    if (int e = xggm_prefetch_args(prefetch, &pf, who)) return e;
+    for (int i = 0; i < n; ++i)
+        if (int e = backward ? check_bwd(probs[i], rng, head_dim, max_rows) : check_fwd(probs[i], rng, head_dim, max_rows, is_bf16))
+            return e;
+    xggm_attn_problem pend[2];
+    int np = 0;
+    const auto flush = [&]() {
+        const int e = (backward ? xggm_attn_bwd_mfma_group : xggm_attn_fwd_mfma_group)(pend, np, rng, pf, st);
+        np = 0;
+        pf = PrefetchArgs{};
+        return e;
+    };
+    for (int i = 0; i < n; ++i) {
+        const xggm_attn_problem& q = probs[i];
+        const Path r = route(q, is_bf16, backward);
+        int e = XGGM_OK;
+        if (r == SHORT_MFMA) {
+            pend[np++] = q;
+            if (np == 2 || i == n - 1) e = flush();
+        } else if (r == SHORT_SCALAR) {
+            e = launch_short_scalar<T>(backward, q, rng, st);
+        } else {
+            e = (backward ? xggm_attn_bwd_long : xggm_attn_fwd_long)(q, is_bf16, r == LONG_MFMA, rng, st);
+        }
+        if (e) return e;
+    }
+    return np ? flush() : XGGM_OK;
+}
+
+// the plain entry points: one problem of at most 64 x 64
+xggm_attn_problem plain_problem(const void* q, const void* k, const void* v, const float* mask, int B, int heads, int Sq, int Sk,
+                                int64_t q_rs, int64_t k_rs, int64_t v_rs, int64_t o_rs, float scale, float p, uint32_t sid) {
+    xggm_attn_problem pr{};
+    pr.q = q; pr.k = k; pr.v = v; pr.mask = mask;
+    pr.B = B; pr.heads = heads; pr.Sq = Sq; pr.Sk = Sk;
+    pr.q_rs = q_rs; pr.k_rs = k_rs; pr.v_rs = v_rs; pr.o_rs = o_rs;
+    pr.scale = scale; pr.p = p; pr.sid = sid;
+    return pr;
 }
 
 template <typename T>
 int attn_fwd(const void* q, const void* k, const void* v, const float* mask, void* out, int B, int heads, int Sq, int Sk,
              int head_dim, int64_t q_rs, int64_t k_rs, int64_t v_rs, int64_t o_rs, float scale, float p, const uint64_t* rng,
              uint32_t sid, hipStream_t st) {
-    xggm_attn_problem pr{};
-    pr.q = q; pr.k = k; pr.v = v; pr.mask = mask; pr.out = out;
-    pr.B = B; pr.heads = heads; pr.Sq = Sq; pr.Sk = Sk;
-    pr.q_rs = q_rs; pr.k_rs = k_rs; pr.v_rs = v_rs; pr.o_rs = o_rs;
-    pr.scale = scale; pr.p = p; pr.sid = sid;
-    return attn_fwd_grouped<T>(&pr, 1, head_dim, rng, nullptr, st, SHORT_ROWS);
+    xggm_attn_problem pr = plain_problem(q, k, v, mask, B, heads, Sq, Sk, q_rs, k_rs, v_rs, o_rs, scale, p, sid);
+    pr.out = out;
+    return run_grouped<T>(false, &pr, 1, head_dim, rng, nullptr, st, SHORT_ROWS);
 }
 
 template <typename T>
@@ -372,15 +311,11 @@ int attn_bwd(const void* q, const void* k, const void* v, const float* mask, con
              int B, int heads, int Sq, int Sk, int head_dim, int64_t q_rs, int64_t k_rs, int64_t v_rs, int64_t o_rs,
              int64_t dq_rs, int64_t dk_rs, int64_t dv_rs, float scale, float p, const uint64_t* rng, uint32_t sid,
              float* dbq, float* dbk, float* dbv, int64_t db_bs, hipStream_t st) {
-    xggm_attn_problem pr{};
-    pr.q = q; pr.k = k; pr.v = v; pr.mask = mask;
-    pr.B = B; pr.heads = heads; pr.Sq = Sq; pr.Sk = Sk;
-    pr.q_rs = q_rs; pr.k_rs = k_rs; pr.v_rs = v_rs; pr.o_rs = o_rs;
-    pr.scale = scale; pr.p = p; pr.sid = sid;
+    xggm_attn_problem pr = plain_problem(q, k, v, mask, B, heads, Sq, Sk, q_rs, k_rs, v_rs, o_rs, scale, p, sid);
     pr.d_out = d_out; pr.dq = dq; pr.dk = dk; pr.dv = dv;
     pr.dq_rs = dq_rs; pr.dk_rs = dk_rs; pr.dv_rs = dv_rs;
     pr.dbq = dbq; pr.dbk = dbk; pr.dbv = dbv; pr.db_bs = db_bs;
-    return attn_bwd_grouped<T>(&pr, 1, head_dim, rng, nullptr, st, SHORT_ROWS);
+    return run_grouped<T>(true, &pr, 1, head_dim, rng, nullptr, st, SHORT_ROWS);
 }
 
 }  // namespace
@@ -403,11 +338,11 @@ int attn_bwd(const void* q, const void* k, const void* v, const float* mask, con
     }                                                                                                                      \
     extern "C" int xggm_attn_fwd_grouped_##SUF(const xggm_attn_problem* probs, int n, int head_dim, const uint64_t* rng,   \
                                                const xggm_prefetch* prefetch, hipStream_t st) {                           \
-        return attn_fwd_grouped<T>(probs, n, head_dim, rng, prefetch, st, LONG_ROWS);                                      \
+        return run_grouped<T>(false, probs, n, head_dim, rng, prefetch, st, LONG_ROWS);                                   \
     }                                                                                                                      \
     extern "C" int xggm_attn_bwd_grouped_##SUF(const xggm_attn_problem* probs, int n, int head_dim, const uint64_t* rng,   \
                                                const xggm_prefetch* prefetch, hipStream_t st) {                           \
-        return attn_bwd_grouped<T>(probs, n, head_dim, rng, prefetch, st, LONG_ROWS);                                      \
+        return run_grouped<T>(true, probs, n, head_dim, rng, prefetch, st, LONG_ROWS);                                    \
     }
 
 ATTN_API(f32, float)

@@ -18,82 +18,25 @@
 // fp32 storage, and bf16 storage that fails the alignment rule, run fp32 arithmetic throughout: K and V stay resident
 // in LDS as fp32 and the query rows are walked in blocks of 32; the dK / dV tiles of a thread stay in its registers
 // across the blocks.
-#include "common.h"
-#include "xggm.h"
-
-int xggm_attn_fwd_long(const xggm_attn_problem& q, bool is_bf16, bool matrix_core, const uint64_t* rng, hipStream_t st);
-int xggm_attn_bwd_long(const xggm_attn_problem& q, bool is_bf16, bool matrix_core, const uint64_t* rng, hipStream_t st);
+// attention_common.h holds what this file shares with attention.hip and attention_mfma.hip: the argument structs, Drop,
+// the MFMA fragments, store_grad_tile, load_tile / dot64 / axpy4 / fold_bias of the fp32 kernels, the LDS sizes
+// (mfma_fwd_lds, mfma_bwd_lds) and the launch helper.
+#include "attention_common.h"
 
 namespace {
+using namespace attn;
 
-constexpr int D = 64;
 constexpr int SMAX = 128;  // rows of either side
-
-struct LArgs {
-    const void *q, *k, *v;
-    const float* mask;  // additive [B, Sk] or null
-    int64_t q_rs, k_rs, v_rs, o_rs;  // row strides in elements
-    int B, heads, Sq, Sk;
-    float scale, p;
-    const uint64_t* rng;
-    uint32_t sid;
-};
-struct LGrad {
-    const void* d_out;
-    void *dq, *dk, *dv;
-    int64_t dq_rs, dk_rs, dv_rs;
-    float *dbq, *dbk, *dbv;
-    int64_t db_bs;
-};
-
-// dropout keep-scale of probability (i, j) of this (sample, head): a pure function of the Philox state
-struct Drop {
-    float p, ik;
-    uint64_t seed, off, base;
-    uint32_t sid;
-    __device__ __forceinline__ Drop(const LArgs& a, int b, int h) : p(a.p), ik(a.p > 0.f ? 1.f / (1.f - a.p) : 1.f), seed(0), off(0),
-                                                                  base(((uint64_t)b * a.heads + h) * a.Sq * a.Sk), sid(a.sid) {
-        if (a.p > 0.f) {
-            seed = a.rng[0];
-            off = a.rng[1];
-        }
-    }
-    __device__ __forceinline__ float scale(int i, int j, int Sk) const {
-        return p > 0.f ? dropout_scale(p, ik, seed, off, sid, base + (uint64_t)i * Sk + j) : 1.f;
-    }
-    // keep-scales of (i, j0 .. j0 + 3), j0 % 4 == 0, keys past Sk get 1: one Philox call when the four element indices
-    // share it (Sk % 4 == 0), one per key otherwise
-    __device__ __forceinline__ void scale4(int i, int j0, int Sk, float (&s)[4]) const {
-        s[0] = s[1] = s[2] = s[3] = 1.f;
-        if (p <= 0.f) return;
-        if ((Sk & 3) == 0) {
-            dropout_scale4(p, ik, seed, off, sid, base + (uint64_t)i * Sk + j0, s);
-        } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-                if (j0 + e < Sk) s[e] = dropout_scale(p, ik, seed, off, sid, base + (uint64_t)i * Sk + j0 + e);
-        }
-    }
-};
 
 // ================================================================================================ matrix cores (bf16)
 namespace mc {
 
 constexpr int NT = 512;      // 8 waves: wave w owns query rows 16 w .. 16 w + 15 in the row phase
-constexpr int LDT = D + 16;  // tile row stride in elements (160 B), as attention_mfma.hip
 constexpr int TJ = SMAX / 16;  // key tiles of a row
 
-typedef __attribute__((ext_vector_type(8))) short short8_t;
-typedef __attribute__((ext_vector_type(4))) short short4_t;
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
-typedef __attribute__((ext_vector_type(4))) float float4_t;
-
-#define LMFMA(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0)
-
-__host__ __device__ constexpr int rup(int x, int m) { return (x + m - 1) / m * m; }
-
 // rows (<= 128) x 64 bf16 tile: two 16-byte chunks per thread.  fetch only issues the loads of the rows inside the
-// problem (the loads of all tiles of a workgroup are in flight together); commit zeroes the padding rows.
+// problem (the loads of all tiles of a workgroup are in flight together); the padding rows are zeros from the fetch on.
+// (attention_mfma.hip has its own pair on purpose: a 64-row tile with clamped, branch-free loads, zeroed at the commit.)
 struct TileRegs { short8_t v[2]; };
 __device__ __forceinline__ TileRegs tile_fetch(const bf16* base, int64_t rs, int valid, int tid) {
     TileRegs t;
@@ -113,23 +56,6 @@ __device__ __forceinline__ void tile_commit(bf16* lds, const TileRegs& t, int ro
     }
 }
 
-// operand whose reduction index k is contiguous: lane (fr, fq) gets row row0+fr, k = k0+8fq .. +7
-__device__ __forceinline__ bf16x8_t frag_rows(const bf16* lds, int ld, int row0, int k0, int lane) {
-    const int fr = lane & 15, fq = lane >> 4;
-    return __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const short8_t*>(lds + (row0 + fr) * ld + k0 + fq * 8));
-}
-// operand stored [k][n] (n contiguous): lane gets n = n0+fr, k = k0+8fq .. +7 through two transposing reads
-__device__ __forceinline__ bf16x8_t frag_tr(const bf16* lds, int ld, int k0, int n0, int lane) {
-    const int fr = lane & 15, fq = lane >> 4, q = fr >> 2, p = fr & 3;
-    const bf16* a0 = lds + (k0 + 8 * fq + q) * ld + n0 + 4 * p;
-    const short4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) short4_t*)(a0));
-    const short4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) short4_t*)(a0 + 4 * ld));
-    short8_t v;
-    v[0] = lo[0]; v[1] = lo[1]; v[2] = lo[2]; v[3] = lo[3];
-    v[4] = hi[0]; v[5] = hi[1]; v[6] = hi[2]; v[7] = hi[3];
-    return __builtin_bit_cast(bf16x8_t, v);
-}
-
 // a query row's 128 scores live in the lanes fr, fr + 16, fr + 32, fr + 48: two exchanges finish a row reduction
 __device__ __forceinline__ float row4_max(float v) {
     v = fmaxf(v, __shfl_xor(v, 16));
@@ -142,7 +68,7 @@ __device__ __forceinline__ float row4_sum(float v) {
 
 // transposed score tiles of query rows row0 .. row0 + 15 against the key tiles [0, ntk): s[tj][r] = score of query
 // row0 + fr and key 16 tj + 4 fq + r, -inf outside the problem.  Returns the lane's maximum.
-__device__ __forceinline__ float score_tiles(const LArgs& a, const bf16* Qs, const bf16* Ks, int row0, int ntk, int b, int lane,
+__device__ __forceinline__ float score_tiles(const AttnArgs& a, const bf16* Qs, const bf16* Ks, int row0, int ntk, int b, int lane,
                                              float4_t (&s)[TJ]) {
     const int fr = lane & 15, fq = lane >> 4;
     const bf16x8_t q0 = frag_rows(Qs, LDT, row0, 0, lane), q1 = frag_rows(Qs, LDT, row0, 32, lane);
@@ -152,8 +78,8 @@ __device__ __forceinline__ float score_tiles(const LArgs& a, const bf16* Qs, con
     for (int tj = 0; tj < TJ; ++tj) {
         if (tj < ntk) {
             float4_t acc = {0.f, 0.f, 0.f, 0.f};
-            acc = LMFMA(frag_rows(Ks, LDT, tj * 16, 0, lane), q0, acc);
-            acc = LMFMA(frag_rows(Ks, LDT, tj * 16, 32, lane), q1, acc);
+            acc = ATTN_MFMA(frag_rows(Ks, LDT, tj * 16, 0, lane), q0, acc);
+            acc = ATTN_MFMA(frag_rows(Ks, LDT, tj * 16, 32, lane), q1, acc);
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int j = tj * 16 + fq * 4 + r;
@@ -167,12 +93,12 @@ __device__ __forceinline__ float score_tiles(const LArgs& a, const bf16* Qs, con
     return m;
 }
 
-__global__ __launch_bounds__(NT) void attn_long_fwd_mc(LArgs a, bf16* out) {
+__global__ __launch_bounds__(NT) void attn_long_fwd_mc(AttnArgs a, bf16* out) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, fr = lane & 15, fq = lane >> 4;
     const int b = blockIdx.x / a.heads, h = blockIdx.x % a.heads;
     const int Sq = a.Sq, Sk = a.Sk;
-    const int RQ = rup(Sq, 16), RK = rup(Sk, 32), LDP = RK + 8;
+    const int RQ = rup(Sq, 16), RK = rup(Sk, 32), LDP = RK + 8;  // mfma_fwd_lds has the same counts
     bf16* Qs = reinterpret_cast<bf16*>(smem_raw);
     bf16* Ks = Qs + RQ * LDT;
     bf16* Vs = Ks + RK * LDT;
@@ -209,7 +135,7 @@ __global__ __launch_bounds__(NT) void attn_long_fwd_mc(LArgs a, bf16* out) {
             if (tj < ntk) {
                 const int j0 = tj * 16 + fq * 4;
                 float ds[4] = {1.f, 1.f, 1.f, 1.f};
-                if (i < Sq && j0 < Sk) dr.scale4(i, j0, Sk, ds);
+                if (i < Sq && j0 < Sk) dr.scale4<true>(i, j0, Sk, ds);
                 short4_t pk;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) pk[e] = __builtin_bit_cast(short, __float2bfloat16(s[tj][e] * inv * ds[e]));
@@ -225,7 +151,7 @@ __global__ __launch_bounds__(NT) void attn_long_fwd_mc(LArgs a, bf16* out) {
         for (int tc = 0; tc < 4; ++tc) {
             float4_t acc = {0.f, 0.f, 0.f, 0.f};
             for (int ks = 0; ks < RK; ks += 32)
-                acc = LMFMA(frag_rows(Pb, LDP, row0, ks, lane), frag_tr(Vs, LDT, ks, tc * 16, lane), acc);
+                acc = ATTN_MFMA(frag_rows(Pb, LDP, row0, ks, lane), frag_tr(Vs, LDT, ks, tc * 16, lane), acc);
 #pragma unroll
             for (int r = 0; r < 4; ++r) Os[(row0 + fq * 4 + r) * LDT + tc * 16 + fr] = __float2bfloat16(acc[r]);
         }
@@ -238,34 +164,7 @@ __global__ __launch_bounds__(NT) void attn_long_fwd_mc(LArgs a, bf16* out) {
     }
 }
 
-// store a 16x16 gradient tile (rows row0.., 16 columns at col0) and fold its column sums into csum.  The tile comes out
-// of an MFMA with swapped operands: lane (fr, fq) holds row fr, columns 4 fq .. 4 fq + 3 -- one 8-byte store per lane,
-// column sums by DPP moves inside the 16-lane rows.
-__device__ __forceinline__ void store_grad_tile(const float4_t& acc, bf16* dst, int64_t rs, int64_t row_base, int rows_valid,
-                                                int row0, int col0, float* csum, int lane) {
-    const int fr = lane & 15, fq = lane >> 4;
-    const int i = row0 + fr;
-    const bool ok = i < rows_valid;
-    if (ok) {
-        short4_t pk;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) pk[r] = __builtin_bit_cast(short, __float2bfloat16(acc[r]));
-        *reinterpret_cast<short4_t*>(dst + (row_base + i) * rs + col0 + 4 * fq) = pk;
-    }
-    if (csum) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            float s = ok ? acc[r] : 0.f;
-            s += dpp_move<0xB1>(s);
-            s += dpp_move<0x4E>(s);
-            s += dpp_move<0x141>(s);
-            s += dpp_move<0x140>(s);  // every lane of the 16-lane row holds the column's sum over the tile's rows
-            if (fr == 0) csum[col0 + 4 * fq + r] = s;  // this row tile's own slot: no atomics, see the kernel's tail
-        }
-    }
-}
-
-__global__ __launch_bounds__(NT) void attn_long_bwd_mc(LArgs a, LGrad g) {
+__global__ __launch_bounds__(NT) void attn_long_bwd_mc(AttnArgs a, AttnGrad g) {
     // bias gradients: column sums of dQ / dK / dV, one slot per 16-row tile (<= 8), written by the wave that owns the
     // tile and added in tile order at the end -- the same bits whatever the scheduling
     __shared__ float csum[3][TJ][D];
@@ -273,7 +172,7 @@ __global__ __launch_bounds__(NT) void attn_long_bwd_mc(LArgs a, LGrad g) {
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, fr = lane & 15, fq = lane >> 4;
     const int b = blockIdx.x / a.heads, h = blockIdx.x % a.heads;
     const int Sq = a.Sq, Sk = a.Sk;
-    const int RQ = rup(Sq, 32), RK = rup(Sk, 32), LDP = RK + 8;  // both row counts also serve as reduction lengths
+    const int RQ = rup(Sq, 32), RK = rup(Sk, 32), LDP = RK + 8;  // both also serve as reduction lengths; mfma_bwd_lds has the same counts
     bf16* Qs = reinterpret_cast<bf16*>(smem_raw);
     bf16* Ks = Qs + RQ * LDT;
     bf16* Vs = Ks + RK * LDT;
@@ -303,8 +202,8 @@ __global__ __launch_bounds__(NT) void attn_long_bwd_mc(LArgs a, LGrad g) {
             for (int tj = 0; tj < TJ; ++tj)
                 if (tj < ntk) {
                     float4_t acc = {0.f, 0.f, 0.f, 0.f};
-                    acc = LMFMA(frag_rows(Vs, LDT, tj * 16, 0, lane), o0, acc);
-                    dp[tj] = LMFMA(frag_rows(Vs, LDT, tj * 16, 32, lane), o1, acc);
+                    acc = ATTN_MFMA(frag_rows(Vs, LDT, tj * 16, 0, lane), o0, acc);
+                    dp[tj] = ATTN_MFMA(frag_rows(Vs, LDT, tj * 16, 32, lane), o1, acc);
                 }
         }
         float sum = 0.f;
@@ -326,7 +225,7 @@ __global__ __launch_bounds__(NT) void attn_long_bwd_mc(LArgs a, LGrad g) {
             if (tj < ntk) {
                 const int j0 = tj * 16 + fq * 4;
                 float dm[4] = {1.f, 1.f, 1.f, 1.f};
-                if (i < Sq && j0 < Sk) dr.scale4(i, j0, Sk, dm);
+                if (i < Sq && j0 < Sk) dr.scale4<true>(i, j0, Sk, dm);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     const float pr = s[tj][e] * inv;   // P (zero outside the problem)
@@ -354,6 +253,9 @@ __global__ __launch_bounds__(NT) void attn_long_bwd_mc(LArgs a, LGrad g) {
             }
     }
     __syncthreads();
+    // third phase and bias tail: the same text as in attn_bwd_mfma_kernel (attention_mfma.hip) but for the 64-bit row
+    // base.  Moved into one shared device function it compiles to other code in both kernels -- here from 101 VGPRs to
+    // all 128 plus spills (584 bytes of scratch) -- so the two copies stay, next to the kernels whose registers they share.
     bf16 *dq = (bf16*)g.dq, *dk = (bf16*)g.dk, *dv = (bf16*)g.dv;
     const int tq = rup(Sq, 16) / 16, tk = rup(Sk, 16) / 16;
     // 4 column tiles each for dQ (tq row tiles), dK and dV (tk row tiles): one list shared by the waves
@@ -363,17 +265,17 @@ __global__ __launch_bounds__(NT) void attn_long_bwd_mc(LArgs a, LGrad g) {
         if (t < n_dq) {
             const int ti = t >> 2, tc = t & 3;  // dQ = dS K: k = j
             for (int ks = 0; ks < RK; ks += 32)
-                acc = LMFMA(frag_tr(Ks, LDT, ks, tc * 16, lane), frag_rows(dSb, LDP, ti * 16, ks, lane), acc);
+                acc = ATTN_MFMA(frag_tr(Ks, LDT, ks, tc * 16, lane), frag_rows(dSb, LDP, ti * 16, ks, lane), acc);
             store_grad_tile(acc, dq + h * D, g.dq_rs, (int64_t)b * Sq, Sq, ti * 16, tc * 16, g.dbq ? csum[0][ti] : nullptr, lane);
         } else if (t < n_dq + n_dk) {
             const int u = t - n_dq, tj = u >> 2, tc = u & 3;  // dK = dS^T Q: k = i
             for (int ks = 0; ks < RQ; ks += 32)
-                acc = LMFMA(frag_tr(Qs, LDT, ks, tc * 16, lane), frag_tr(dSb, LDP, ks, tj * 16, lane), acc);
+                acc = ATTN_MFMA(frag_tr(Qs, LDT, ks, tc * 16, lane), frag_tr(dSb, LDP, ks, tj * 16, lane), acc);
             store_grad_tile(acc, dk + h * D, g.dk_rs, (int64_t)b * Sk, Sk, tj * 16, tc * 16, g.dbk ? csum[1][tj] : nullptr, lane);
         } else {
             const int u = t - n_dq - n_dk, tj = u >> 2, tc = u & 3;  // dV = (P D)^T dO: k = i
             for (int ks = 0; ks < RQ; ks += 32)
-                acc = LMFMA(frag_tr(dOs, LDT, ks, tc * 16, lane), frag_tr(Pdb, LDP, ks, tj * 16, lane), acc);
+                acc = ATTN_MFMA(frag_tr(dOs, LDT, ks, tc * 16, lane), frag_tr(Pdb, LDP, ks, tj * 16, lane), acc);
             store_grad_tile(acc, dv + h * D, g.dv_rs, (int64_t)b * Sk, Sk, tj * 16, tc * 16, g.dbv ? csum[2][tj] : nullptr, lane);
         }
     }
@@ -391,14 +293,6 @@ __global__ __launch_bounds__(NT) void attn_long_bwd_mc(LArgs a, LGrad g) {
 }
 
 constexpr size_t BWD_STATIC_LDS = sizeof(float) * 3 * TJ * D;  // csum of attn_long_bwd_mc
-inline size_t fwd_lds(int Sq, int Sk) {
-    const int RQ = rup(Sq, 16), RK = rup(Sk, 32);
-    return sizeof(bf16) * ((size_t)(RQ + 2 * RK) * LDT + (size_t)RQ * (RK + 8));
-}
-inline size_t bwd_lds(int Sq, int Sk) {
-    const int RQ = rup(Sq, 32), RK = rup(Sk, 32);
-    return sizeof(bf16) * ((size_t)(2 * RQ + 2 * RK) * LDT + 2 * (size_t)RQ * (RK + 8));
-}
 
 }  // namespace mc
 
@@ -406,35 +300,12 @@ inline size_t bwd_lds(int Sq, int Sk) {
 namespace sc {
 
 constexpr int NT = 512;
-constexpr int LD = D + 4;  // float4-aligned rows, conflict-free 16-byte reads
 constexpr int QB = 32;     // query rows per block: K and V stay resident, Q (dO) and the score rows are per block
 constexpr int KI = SMAX * 16 / NT;  // (key row, column group) items of dK / dV per thread
 
-template <typename T>
-__device__ __forceinline__ void load_tile(float* lds, const T* base, int64_t rs, int rows, int tid) {
-    // rows x 64 elements, 16 chunks of 4 per row
-    for (int c = tid; c < rows * 16; c += NT) {
-        const int r = c >> 4, cc = (c & 15) * 4;
-        float t[4];
-        load4(base + (int64_t)r * rs + cc, t);
-        *reinterpret_cast<float4*>(lds + r * LD + cc) = make_float4(t[0], t[1], t[2], t[3]);
-    }
-}
-
-__device__ __forceinline__ float dot64(const float* a, const float* b) {
-    float s = 0.f;
-#pragma unroll
-    for (int c = 0; c < D; c += 4) {
-        const float4 x = *reinterpret_cast<const float4*>(a + c);
-        const float4 y = *reinterpret_cast<const float4*>(b + c);
-        s += x.x * y.x + x.y * y.y + x.z * y.z + x.w * y.w;
-    }
-    return s;
-}
-
 // scores + softmax (+ dropout scale matrix) of the nq query rows from q0 into LDS.  P: probabilities, Dm: dropout
 // scale (only written when p > 0).  Wave w owns rows w, w + 8, ...; a lane holds keys lane and lane + 64.
-__device__ __forceinline__ void scores_softmax(const LArgs& a, const float* Qs, const float* Ks, float* P, float* Dm, int b, int h,
+__device__ __forceinline__ void scores_softmax(const AttnArgs& a, const float* Qs, const float* Ks, float* P, float* Dm, int b, int h,
                                                int q0, int nq, int tid) {
     const int Sk = a.Sk, ldp = Sk + 1;
     for (int s = tid; s < nq * Sk; s += NT) {
@@ -466,7 +337,7 @@ __device__ __forceinline__ void scores_softmax(const LArgs& a, const float* Qs, 
     __syncthreads();
 }
 
-template <typename T> __global__ __launch_bounds__(NT) void attn_long_fwd_sc(LArgs a, T* out) {
+template <typename T> __global__ __launch_bounds__(NT) void attn_long_fwd_sc(AttnArgs a, T* out) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int tid = threadIdx.x;
     const int b = blockIdx.x / a.heads, h = blockIdx.x % a.heads;
@@ -476,12 +347,12 @@ template <typename T> __global__ __launch_bounds__(NT) void attn_long_fwd_sc(LAr
     float* Qs = Vs + Sk * LD;
     float* P = Qs + QB * LD;
     float* Dm = P + QB * ldp;
-    load_tile<T>(Ks, (const T*)a.k + (int64_t)b * Sk * a.k_rs + h * D, a.k_rs, Sk, tid);
-    load_tile<T>(Vs, (const T*)a.v + (int64_t)b * Sk * a.v_rs + h * D, a.v_rs, Sk, tid);
+    load_tile<NT>(Ks, (const T*)a.k + (int64_t)b * Sk * a.k_rs + h * D, a.k_rs, Sk, tid);
+    load_tile<NT>(Vs, (const T*)a.v + (int64_t)b * Sk * a.v_rs + h * D, a.v_rs, Sk, tid);
     for (int q0 = 0; q0 < Sq; q0 += QB) {
         const int nq = min(QB, Sq - q0);
         __syncthreads();  // the block before is read to the end
-        load_tile<T>(Qs, (const T*)a.q + ((int64_t)b * Sq + q0) * a.q_rs + h * D, a.q_rs, nq, tid);
+        load_tile<NT>(Qs, (const T*)a.q + ((int64_t)b * Sq + q0) * a.q_rs + h * D, a.q_rs, nq, tid);
         __syncthreads();
         scores_softmax(a, Qs, Ks, P, Dm, b, h, q0, nq, tid);
         // O[i][c..c+3] = sum_j P[i][j] * D[i][j] * V[j][c..c+3]
@@ -491,22 +362,15 @@ template <typename T> __global__ __launch_bounds__(NT) void attn_long_fwd_sc(LAr
             for (int j = 0; j < Sk; ++j) {
                 float pj = P[i * ldp + j];
                 if (a.p > 0.f) pj *= Dm[i * ldp + j];
-                const float4 vv = *reinterpret_cast<const float4*>(Vs + j * LD + c);
-                o[0] += pj * vv.x;
-                o[1] += pj * vv.y;
-                o[2] += pj * vv.z;
-                o[3] += pj * vv.w;
+                axpy4(o, pj, Vs + j * LD + c);
             }
             store4(out + ((int64_t)b * Sq + q0 + i) * a.o_rs + h * D + c, o);
         }
     }
 }
 
-template <typename T> __global__ __launch_bounds__(NT) void attn_long_bwd_sc(LArgs a, LGrad g) {
-    // column sums of dQ / dK / dV over this sample's rows (bias gradients): every thread keeps the sums of ITS column
-    // group over its rows (NT % 16 == 0: a thread's columns never change), the threads of a column group are added in
-    // index order through `red`, and the result is a partial row of this (sample, head) nobody else writes
-    __shared__ float red[NT / 16][D];
+template <typename T> __global__ __launch_bounds__(NT) void attn_long_bwd_sc(AttnArgs a, AttnGrad g) {
+    __shared__ float red[NT / 16][D];  // bias gradients, see fold_bias
     float cq[4] = {0.f, 0.f, 0.f, 0.f};
     float ok[KI][4], ov[KI][4];  // dK / dV of items tid, tid + NT, ...: summed over the query blocks in row order
 #pragma unroll
@@ -526,13 +390,13 @@ template <typename T> __global__ __launch_bounds__(NT) void attn_long_bwd_sc(LAr
     float* P = dOs + QB * LD;
     float* Dm = P + QB * ldp;
     float* dS = Dm + QB * ldp;
-    load_tile<T>(Ks, (const T*)a.k + (int64_t)b * Sk * a.k_rs + h * D, a.k_rs, Sk, tid);
-    load_tile<T>(Vs, (const T*)a.v + (int64_t)b * Sk * a.v_rs + h * D, a.v_rs, Sk, tid);
+    load_tile<NT>(Ks, (const T*)a.k + (int64_t)b * Sk * a.k_rs + h * D, a.k_rs, Sk, tid);
+    load_tile<NT>(Vs, (const T*)a.v + (int64_t)b * Sk * a.v_rs + h * D, a.v_rs, Sk, tid);
     for (int q0 = 0; q0 < Sq; q0 += QB) {
         const int nq = min(QB, Sq - q0);
         __syncthreads();  // the block before is read to the end
-        load_tile<T>(Qs, (const T*)a.q + ((int64_t)b * Sq + q0) * a.q_rs + h * D, a.q_rs, nq, tid);
-        load_tile<T>(dOs, d_out + ((int64_t)b * Sq + q0) * a.o_rs + h * D, a.o_rs, nq, tid);
+        load_tile<NT>(Qs, (const T*)a.q + ((int64_t)b * Sq + q0) * a.q_rs + h * D, a.q_rs, nq, tid);
+        load_tile<NT>(dOs, d_out + ((int64_t)b * Sq + q0) * a.o_rs + h * D, a.o_rs, nq, tid);
         __syncthreads();
         scores_softmax(a, Qs, Ks, P, Dm, b, h, q0, nq, tid);
         // dP[i][j] = D[i][j] * sum_c dO[i][c] V[j][c]
@@ -562,11 +426,7 @@ template <typename T> __global__ __launch_bounds__(NT) void attn_long_bwd_sc(LAr
             float o[4] = {0.f, 0.f, 0.f, 0.f};
             for (int j = 0; j < Sk; ++j) {
                 const float s = dS[i * ldp + j];
-                const float4 kk = *reinterpret_cast<const float4*>(Ks + j * LD + c);
-                o[0] += s * kk.x;
-                o[1] += s * kk.y;
-                o[2] += s * kk.z;
-                o[3] += s * kk.w;
+                axpy4(o, s, Ks + j * LD + c);
             }
             store4(dq + ((int64_t)b * Sq + q0 + i) * g.dq_rs + h * D + c, o);
 #pragma unroll
@@ -581,16 +441,8 @@ template <typename T> __global__ __launch_bounds__(NT) void attn_long_bwd_sc(LAr
                     const float s = dS[i * ldp + j];
                     float pj = P[i * ldp + j];
                     if (a.p > 0.f) pj *= Dm[i * ldp + j];
-                    const float4 qq = *reinterpret_cast<const float4*>(Qs + i * LD + c);
-                    const float4 gg = *reinterpret_cast<const float4*>(dOs + i * LD + c);
-                    ok[n][0] += s * qq.x;
-                    ok[n][1] += s * qq.y;
-                    ok[n][2] += s * qq.z;
-                    ok[n][3] += s * qq.w;
-                    ov[n][0] += pj * gg.x;
-                    ov[n][1] += pj * gg.y;
-                    ov[n][2] += pj * gg.z;
-                    ov[n][3] += pj * gg.w;
+                    axpy4(ok[n], s, Qs + i * LD + c);
+                    axpy4(ov[n], pj, dOs + i * LD + c);
                 }
             }
         }
@@ -609,20 +461,10 @@ template <typename T> __global__ __launch_bounds__(NT) void attn_long_bwd_sc(LAr
             }
         }
     }
-    auto fold = [&](const float (&c4)[4], float* dst) {  // uniform: every thread of the workgroup calls it
-        __syncthreads();
-#pragma unroll
-        for (int e = 0; e < 4; ++e) red[tid >> 4][(tid & 15) * 4 + e] = c4[e];
-        __syncthreads();
-        if (tid < D) {
-            float s = 0.f;
-            for (int gI = 0; gI < NT / 16; ++gI) s += red[gI][tid];  // fixed order
-            dst[(int64_t)b * g.db_bs + h * D + tid] = s;
-        }
-    };
-    if (g.dbq) fold(cq, g.dbq);
-    if (g.dbk) fold(ck, g.dbk);
-    if (g.dbv) fold(cv, g.dbv);
+    const int64_t po = (int64_t)b * g.db_bs + h * D;  // this (sample, head)'s partial row
+    if (g.dbq) fold_bias<NT>(red, cq, g.dbq + po, tid);
+    if (g.dbk) fold_bias<NT>(red, ck, g.dbk + po, tid);
+    if (g.dbv) fold_bias<NT>(red, cv, g.dbv + po, tid);
 }
 
 constexpr size_t BWD_STATIC_LDS = sizeof(float) * (NT / 16) * D;  // red of attn_long_bwd_sc
@@ -631,41 +473,26 @@ inline size_t bwd_lds(int Sk) { return sizeof(float) * ((size_t)(2 * Sk + 2 * QB
 
 }  // namespace sc
 
-inline LArgs args_of(const xggm_attn_problem& q, const uint64_t* rng) {
-    return LArgs{q.q, q.k, q.v, q.mask, q.q_rs, q.k_rs, q.v_rs, q.o_rs, q.B, q.heads, q.Sq, q.Sk, q.scale, q.p, rng, q.sid};
-}
-
-// `lds` bytes of dynamic LDS on top of the kernel's `fixed` bytes of static LDS.  xggm_reserve_lds opts in by the dynamic
-// size alone and does nothing up to 48 KiB: where only the sum passes 48 KiB the opt-in is asked for all the same.
-constexpr size_t LDS_NO_OPT_IN = 48 * 1024;
-template <typename K, typename... A>
-int launch(K kernel, const char* who, int grid, int nt, size_t lds, size_t fixed, hipStream_t st, A... args) {
-    const size_t reserve = (lds <= LDS_NO_OPT_IN && lds + fixed > LDS_NO_OPT_IN) ? LDS_NO_OPT_IN + 1024 : lds;
-    if (int e = xggm_reserve_lds(reinterpret_cast<const void*>(kernel), reserve, who)) return e;
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(nt), lds, st, args...);
-    return xggm_check_launch(who);
-}
-
 }  // namespace
 
 // called by attention.hip with validated problems, 1 <= Sq, Sk <= 128.  matrix_core: bf16 storage whose pointers and
 // strides pass the alignment rule of the matrix-core kernels (16-byte operands, 8-byte gradients)
 int xggm_attn_fwd_long(const xggm_attn_problem& q, bool is_bf16, bool matrix_core, const uint64_t* rng, hipStream_t st) {
-    const LArgs a = args_of(q, rng);
+    const AttnArgs a = args_of(q, rng);
     const int grid = q.B * q.heads;
     if (is_bf16 && matrix_core)
-        return launch(mc::attn_long_fwd_mc, "xggm_attn_fwd(long, mfma)", grid, mc::NT, mc::fwd_lds(q.Sq, q.Sk), 0, st, a, (bf16*)q.out);
+        return launch(mc::attn_long_fwd_mc, "xggm_attn_fwd(long, mfma)", grid, mc::NT, mfma_fwd_lds(q.Sq, q.Sk, false), 0, st, a, (bf16*)q.out);
     if (is_bf16)
         return launch(sc::attn_long_fwd_sc<bf16>, "xggm_attn_fwd(long)", grid, sc::NT, sc::fwd_lds(q.Sk), 0, st, a, (bf16*)q.out);
     return launch(sc::attn_long_fwd_sc<float>, "xggm_attn_fwd(long)", grid, sc::NT, sc::fwd_lds(q.Sk), 0, st, a, (float*)q.out);
 }
 
 int xggm_attn_bwd_long(const xggm_attn_problem& q, bool is_bf16, bool matrix_core, const uint64_t* rng, hipStream_t st) {
-    const LArgs a = args_of(q, rng);
-    const LGrad g{q.d_out, q.dq, q.dk, q.dv, q.dq_rs, q.dk_rs, q.dv_rs, q.dbq, q.dbk, q.dbv, q.db_bs};
+    const AttnArgs a = args_of(q, rng);
+    const AttnGrad g = grad_of(q);
     const int grid = q.B * q.heads;
     if (is_bf16 && matrix_core)
-        return launch(mc::attn_long_bwd_mc, "xggm_attn_bwd(long, mfma)", grid, mc::NT, mc::bwd_lds(q.Sq, q.Sk), mc::BWD_STATIC_LDS, st, a, g);
+        return launch(mc::attn_long_bwd_mc, "xggm_attn_bwd(long, mfma)", grid, mc::NT, mfma_bwd_lds(q.Sq, q.Sk, false), mc::BWD_STATIC_LDS, st, a, g);
     if (is_bf16) return launch(sc::attn_long_bwd_sc<bf16>, "xggm_attn_bwd(long)", grid, sc::NT, sc::bwd_lds(q.Sk), sc::BWD_STATIC_LDS, st, a, g);
     return launch(sc::attn_long_bwd_sc<float>, "xggm_attn_bwd(long)", grid, sc::NT, sc::bwd_lds(q.Sk), sc::BWD_STATIC_LDS, st, a, g);
 }

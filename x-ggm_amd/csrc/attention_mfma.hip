@@ -8,44 +8,26 @@
 // fp32 for the wave-per-row softmax (shuffle reductions) and return as bf16 operands.  All five
 // products of the backward are 108 MFMAs per (b, h) at S = 36 instead of ~420 K scalar FMAs.
 // Sequences are padded to the MFMA granularity with zero rows, which contribute nothing.
-#include "common.h"
-#include "xggm.h"
+// attention_common.h holds what this file shares with attention_long.hip: the argument structs, Drop, the MFMA
+// fragments, store_grad_tile, the LDS sizes (mfma_fwd_lds, mfma_bwd_lds) and the launch helper.
+#include "attention_common.h"
 
 namespace {
+using namespace attn;
 
 constexpr int NT = 512;  // 8 waves (measured: 256 threads 1.97 ms, 512 1.46 ms, 1024 1.77 ms for the backward launches of three passes): every phase (tile products, row softmax, gradient tiles) is spread over twice the waves
 constexpr int TILE_IT = NT >= 512 ? 1 : 512 / NT;  // 16-byte chunks per thread of a 64 x 64 bf16 tile
-constexpr int D = 64;
-constexpr int LDT = D + 16;  // tile row stride in elements (160 B): b128 rows 16-B aligned; tr-reads of k-rows 8 apart share banks (2-way; the GEMM swaps half-blocks against this, see gemm.hip fast_frag -- here the phases are barrier-latency-bound)
-
-typedef __attribute__((ext_vector_type(8))) short short8_t;
-typedef __attribute__((ext_vector_type(4))) short short4_t;
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
-typedef __attribute__((ext_vector_type(4))) float float4_t;
-
-struct MArgs {
-    const bf16 *q, *k, *v;
-    const float* mask;
-    int64_t q_rs, k_rs, v_rs, o_rs;
-    int B, heads, Sq, Sk;
-    float scale, p;
-    const uint64_t* rng;
-    uint32_t sid;
-};
+constexpr int ROW_TILES = 4;  // 16-row tiles of a side (S <= 64)
 
 // one or two independent problems per launch: workgroups [0, start1) run s[0], the rest s[1]
 struct MSeg {
-    MArgs a;
+    AttnArgs a;
     bf16* out;
     unsigned char* out8;  // or null: e4m3 copy of the output (operand of the fp8 output projection)
     const float* qscale;
     float* amax;
     int amax_slots;
-    const bf16* d_out;
-    bf16 *dq, *dk, *dv;
-    int64_t dq_rs, dk_rs, dv_rs;
-    float *dbq, *dbk, *dbv;
-    int64_t db_bs;
+    AttnGrad g;
 };
 struct MGroup {
     MSeg s[2];
@@ -57,11 +39,10 @@ struct MGroup {
 #endif
 };
 
-__device__ __forceinline__ int rup(int x, int m) { return (x + m - 1) / m * m; }
-
 // rows (<= 64) x 64 bf16 tile: two 16-byte chunks per thread.  tile_fetch only ISSUES the loads
 // (addresses clamped into the tile, no branches) so the loads of all tiles of a workgroup are in
 // flight together; tile_commit zeroes the padding rows and writes LDS (row stride LDT).
+// (attention_long.hip has its own pair on purpose: a 128-row tile with predicated loads, zeroed at the fetch.)
 struct TileRegs { short8_t v[TILE_IT]; };
 __device__ __forceinline__ TileRegs tile_fetch(const bf16* base, int64_t rs, int valid, int tid) {
     TileRegs t;
@@ -81,25 +62,6 @@ __device__ __forceinline__ void tile_commit(bf16* lds, const TileRegs& t, int va
     }
 }
 
-// operand whose reduction index k is contiguous: lane (fr, fq) gets row row0+fr, k = k0+8fq .. +7
-__device__ __forceinline__ bf16x8_t frag_rows(const bf16* lds, int ld, int row0, int k0, int lane) {
-    const int fr = lane & 15, fq = lane >> 4;
-    return __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const short8_t*>(lds + (row0 + fr) * ld + k0 + fq * 8));
-}
-// operand stored [k][n] (n contiguous): lane gets n = n0+fr, k = k0+8fq .. +7 through two transposing reads
-__device__ __forceinline__ bf16x8_t frag_tr(const bf16* lds, int ld, int k0, int n0, int lane) {
-    const int fr = lane & 15, fq = lane >> 4, q = fr >> 2, p = fr & 3;
-    const bf16* a0 = lds + (k0 + 8 * fq + q) * ld + n0 + 4 * p;
-    const short4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) short4_t*)(a0));
-    const short4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) short4_t*)(a0 + 4 * ld));
-    short8_t v;
-    v[0] = lo[0]; v[1] = lo[1]; v[2] = lo[2]; v[3] = lo[3];
-    v[4] = hi[0]; v[5] = hi[1]; v[6] = hi[2]; v[7] = hi[3];
-    return __builtin_bit_cast(bf16x8_t, v);
-}
-
-#define MFMA(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0)
-
 #ifdef XGGM_STAMP
 // instrumented build (make stamp, tools/attn_stamps.py): 16 cycle-counter slots per workgroup
 long long* g_attn_stamp = nullptr;
@@ -114,7 +76,7 @@ long long* g_attn_stamp = nullptr;
 // S = scale * Q K^T + mask  ->  Sf (fp32, row stride lds_s), tiles shared round-robin by the waves
 // (staging the sample's mask row in LDS with the Q / K / V tiles instead of reading it inside the tile loop was
 // measured: 7.68 -> 7.77 us forward, 13.0 -> 13.3 us backward -- the other waves cover that round trip already)
-__device__ __forceinline__ void scores(const MArgs& a, const bf16* Qs, const bf16* Ks, float* Sf, int lds_s, int b, int tid) {
+__device__ __forceinline__ void scores(const AttnArgs& a, const bf16* Qs, const bf16* Ks, float* Sf, int lds_s, int b, int tid) {
     const int lane = tid & 63, wid = tid >> 6, fr = lane & 15, fq = lane >> 4;
     const int tq = rup(a.Sq, 16) / 16, tk = rup(a.Sk, 16) / 16;
     for (int t = wid; t < tq * tk; t += NT / 64) {
@@ -122,7 +84,7 @@ __device__ __forceinline__ void scores(const MArgs& a, const bf16* Qs, const bf1
         float4_t acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int ks = 0; ks < D; ks += 32)
-            acc = MFMA(frag_rows(Qs, LDT, ti * 16, ks, lane), frag_rows(Ks, LDT, tj * 16, ks, lane), acc);
+            acc = ATTN_MFMA(frag_rows(Qs, LDT, ti * 16, ks, lane), frag_rows(Ks, LDT, tj * 16, ks, lane), acc);
         const int j = tj * 16 + fr;
         const float mk = (a.mask && j < a.Sk) ? a.mask[(int64_t)b * a.Sk + j] : 0.f;
 #pragma unroll
@@ -133,47 +95,6 @@ __device__ __forceinline__ void scores(const MArgs& a, const bf16* Qs, const bf1
     }
 }
 
-// dropout keep-scale of probability (i, j) of this (sample, head): a pure function of the Philox
-// state, recomputed wherever it is needed instead of being parked in LDS
-struct Drop {
-    float p, ik;
-    uint64_t seed, off, base;
-    uint32_t sid;
-    __device__ __forceinline__ Drop(const MArgs& a, int b, int h) : p(a.p), ik(a.p > 0.f ? 1.f / (1.f - a.p) : 1.f), seed(0), off(0),
-                                                                  base(((uint64_t)b * a.heads + h) * a.Sq * a.Sk), sid(a.sid) {
-        if (a.p > 0.f) {
-            seed = a.rng[0];
-            off = a.rng[1];
-        }
-    }
-    __device__ __forceinline__ float scale(int i, int j, int Sk) const {
-        return p > 0.f ? dropout_scale(p, ik, seed, off, sid, base + (uint64_t)i * Sk + j) : 1.f;
-    }
-    // keep-scales of (i, j0 .. j0 + 3): one Philox call when the four element indices share it
-    __device__ __forceinline__ void scale4(int i, int j0, int Sk, float (&s)[4]) const {
-        if (p <= 0.f) {
-            s[0] = s[1] = s[2] = s[3] = 1.f;
-        } else if ((Sk & 3) == 0) {
-            dropout_scale4(p, ik, seed, off, sid, base + (uint64_t)i * Sk + j0, s);
-        } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) s[e] = dropout_scale(p, ik, seed, off, sid, base + (uint64_t)i * Sk + j0 + e);
-        }
-    }
-};
-
-// row softmax of Sf in place (fp32).  wave w owns rows w, w+4, ...
-__device__ __forceinline__ void softmax_rows(const MArgs& a, float* Sf, int lds_s, int tid) {
-    const int lane = tid & 63, wid = tid >> 6;
-    for (int i = wid; i < a.Sq; i += NT / 64) {
-        const float v = lane < a.Sk ? Sf[i * lds_s + lane] : -INFINITY;
-        const float m = wave_max(v);
-        const float e = lane < a.Sk ? __expf(v - m) : 0.f;
-        const float sum = wave_sum(e);
-        if (lane < a.Sk) Sf[i * lds_s + lane] = e / sum;
-    }
-}
-
 // ---- row phase: EIGHT lanes per score row, no wave-wide shuffles -------------------------------------------------
 // The first version gave every row to a whole wave (wave_max / wave_sum = 12 ds_bpermute round trips per row, then a
 // second pass over all elements for dropout + bf16): in-kernel stamps put 66 % of the forward and 58 % of the
@@ -181,26 +102,17 @@ __device__ __forceinline__ void softmax_rows(const MArgs& a, float* Sf, int lds_
 // values, kept in registers) of row r: maximum and sum are finished with three DPP moves (quad permutes, half-row mirror), one
 // Philox call serves the four dropout decisions of a group (their element indices share idx >> 2 when Sk % 4 == 0),
 // and the probabilities leave as 8-byte bf16 stores.  Rows / columns outside the problem are written as zeros.
-__device__ __forceinline__ float quad_xor1(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true));
-}
-__device__ __forceinline__ float quad_xor2(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, true));
-}
-// lanes i <-> 7 - i of every group of eight (DPP row_half_mirror): after the two quad steps each quad holds its own
-// result, so the mirrored lane supplies the other quad's
-__device__ __forceinline__ float half_mirror(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0x141, 0xF, 0xF, true));
-}
 __device__ __forceinline__ float quad_max(float v) {  // over the ROW_L = 8 lanes of a row
-    v = fmaxf(v, quad_xor1(v));
-    v = fmaxf(v, quad_xor2(v));
-    return fmaxf(v, half_mirror(v));
+    v = fmaxf(v, dpp_move<0xB1>(v));  // quad_perm [1,0,3,2]
+    v = fmaxf(v, dpp_move<0x4E>(v));  // quad_perm [2,3,0,1]
+    // row_half_mirror, lanes i <-> 7 - i of every group of eight: after the two quad steps each quad holds its own
+    // result, so the mirrored lane supplies the other quad's
+    return fmaxf(v, dpp_move<0x141>(v));
 }
 __device__ __forceinline__ float quad_sum(float v) {
-    v += quad_xor1(v);
-    v += quad_xor2(v);
-    return v + half_mirror(v);
+    v += dpp_move<0xB1>(v);
+    v += dpp_move<0x4E>(v);
+    return v + dpp_move<0x141>(v);
 }
 constexpr int ROW_L = 8;  // lanes per score row
 constexpr int ROW_G = 2;  // column groups per lane: 8 lanes x 2 groups x 4 columns = 64 keys
@@ -213,14 +125,14 @@ __global__ __launch_bounds__(NT) void attn_fwd_mfma_kernel(MGroup G) {
     }
     const int si = (int)blockIdx.x >= G.start1 ? 1 : 0;
     const MSeg sg = G.s[si];
-    const MArgs& a = sg.a;
+    const AttnArgs& a = sg.a;
     bf16* out = sg.out;
     const int blk = blockIdx.x - (si ? G.start1 : 0);
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, fr = lane & 15, fq = lane >> 4;
     const int b = blk / a.heads, h = blk % a.heads;
     const int Sq = a.Sq, Sk = a.Sk;
     const int RQ = rup(Sq, 16), RK = rup(Sk, 32);  // Q rows (M of every product), K/V rows (k of P V)
-    const int LDP = RK + 8, lds_s = rup(Sk, 16) + 1;
+    const int LDP = RK + 8, lds_s = rup(Sk, 16) + 1;  // mfma_fwd_lds has the same counts
     bf16* Qs = reinterpret_cast<bf16*>(smem_raw);
     bf16* Ks = Qs + RQ * LDT;
     bf16* Vs = Ks + RK * LDT;
@@ -231,9 +143,9 @@ __global__ __launch_bounds__(NT) void attn_fwd_mfma_kernel(MGroup G) {
 #endif
     ASTAMP(stp, 0);
     {
-        const TileRegs tq_ = tile_fetch(a.q + (int64_t)b * Sq * a.q_rs + h * D, a.q_rs, Sq, tid);
-        const TileRegs tk_ = tile_fetch(a.k + (int64_t)b * Sk * a.k_rs + h * D, a.k_rs, Sk, tid);
-        const TileRegs tv_ = tile_fetch(a.v + (int64_t)b * Sk * a.v_rs + h * D, a.v_rs, Sk, tid);
+        const TileRegs tq_ = tile_fetch((const bf16*)a.q + (int64_t)b * Sq * a.q_rs + h * D, a.q_rs, Sq, tid);
+        const TileRegs tk_ = tile_fetch((const bf16*)a.k + (int64_t)b * Sk * a.k_rs + h * D, a.k_rs, Sk, tid);
+        const TileRegs tv_ = tile_fetch((const bf16*)a.v + (int64_t)b * Sk * a.v_rs + h * D, a.v_rs, Sk, tid);
         tile_commit(Qs, tq_, Sq, RQ, tid);
         tile_commit(Ks, tk_, Sk, RK, tid);
         tile_commit(Vs, tv_, Sk, RK, tid);
@@ -277,7 +189,7 @@ __global__ __launch_bounds__(NT) void attn_fwd_mfma_kernel(MGroup G) {
                 const int g = part + ROW_L * gi, j0 = 4 * g;
                 if (g < NG) {
                     float ds[4] = {1.f, 1.f, 1.f, 1.f};
-                    if (row < Sq && j0 < Sk) dr.scale4(row, j0, Sk, ds);
+                    if (row < Sq && j0 < Sk) dr.scale4<false>(row, j0, Sk, ds);
                     short4_t pk;
 #pragma unroll
                     for (int e = 0; e < 4; ++e) pk[e] = __builtin_bit_cast(short, __float2bfloat16(v[gi][e] * inv * ds[e]));
@@ -297,7 +209,7 @@ __global__ __launch_bounds__(NT) void attn_fwd_mfma_kernel(MGroup G) {
         const int ti = t >> 2, tc = t & 3;
         float4_t acc = {0.f, 0.f, 0.f, 0.f};
         for (int ks = 0; ks < RK; ks += 32)
-            acc = MFMA(frag_rows(Pb, LDP, ti * 16, ks, lane), frag_tr(Vs, LDT, ks, tc * 16, lane), acc);
+            acc = ATTN_MFMA(frag_rows(Pb, LDP, ti * 16, ks, lane), frag_tr(Vs, LDT, ks, tc * 16, lane), acc);
 #pragma unroll
         for (int r = 0; r < 4; ++r) Os[(ti * 16 + fq * 4 + r) * LDT + tc * 16 + fr] = __float2bfloat16(acc[r]);
     }
@@ -336,37 +248,10 @@ __global__ __launch_bounds__(NT) void attn_fwd_mfma_kernel(MGroup G) {
     }
 }
 
-// store a 16x16 gradient tile (rows row0.., 16 columns at col0) and fold its column sums into csum.  The tile comes out
-// of an MFMA with SWAPPED operands: lane (fr, fq) holds row fr, columns 4 fq .. 4 fq + 3 -- one 8-byte store per lane
-// (was four 2-byte ones) and column sums by DPP moves inside the 16-lane rows (was two ds_bpermute round trips).
-__device__ __forceinline__ void store_grad_tile(const float4_t& acc, bf16* dst, int64_t rs, int row_base, int rows_valid,
-                                                int row0, int col0, float* csum, int lane) {
-    const int fr = lane & 15, fq = lane >> 4;
-    const int i = row0 + fr;
-    const bool ok = i < rows_valid;
-    if (ok) {
-        short4_t pk;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) pk[r] = __builtin_bit_cast(short, __float2bfloat16(acc[r]));
-        *reinterpret_cast<short4_t*>(dst + (int64_t)(row_base + i) * rs + col0 + 4 * fq) = pk;
-    }
-    if (csum) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            float s = ok ? acc[r] : 0.f;
-            s += dpp_move<0xB1>(s);
-            s += dpp_move<0x4E>(s);
-            s += dpp_move<0x141>(s);
-            s += dpp_move<0x140>(s);  // every lane of the 16-lane row holds the column's sum over the tile's rows
-            if (fr == 0) csum[col0 + 4 * fq + r] = s;  // this row tile's own slot: no atomics, see the kernel's tail
-        }
-    }
-}
-
 __global__ __launch_bounds__(NT) void attn_bwd_mfma_kernel(MGroup G) {
     // bias gradients: column sums of dQ / dK / dV, one slot per 16-row tile (<= 4: S <= 64), written by the wave that
     // owns the tile and added in tile order at the end -- the same bits whatever the scheduling
-    __shared__ float csum[3][4][D];
+    __shared__ float csum[3][ROW_TILES][D];
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     if ((int)blockIdx.x >= G.total) {
         prefetch_role(G.pf, (int)blockIdx.x - G.total);
@@ -374,17 +259,17 @@ __global__ __launch_bounds__(NT) void attn_bwd_mfma_kernel(MGroup G) {
     }
     const int si = (int)blockIdx.x >= G.start1 ? 1 : 0;
     const MSeg sg = G.s[si];
-    const MArgs& a = sg.a;
-    const bf16* d_out = sg.d_out;
-    bf16 *dq = sg.dq, *dk = sg.dk, *dv = sg.dv;
-    const int64_t dq_rs = sg.dq_rs, dk_rs = sg.dk_rs, dv_rs = sg.dv_rs;
-    float *dbq = sg.dbq, *dbk = sg.dbk, *dbv = sg.dbv;
+    const AttnArgs& a = sg.a;
+    const bf16* d_out = (const bf16*)sg.g.d_out;
+    bf16 *dq = (bf16*)sg.g.dq, *dk = (bf16*)sg.g.dk, *dv = (bf16*)sg.g.dv;
+    const int64_t dq_rs = sg.g.dq_rs, dk_rs = sg.g.dk_rs, dv_rs = sg.g.dv_rs;
+    float *dbq = sg.g.dbq, *dbk = sg.g.dbk, *dbv = sg.g.dbv;
     const int blk = blockIdx.x - (si ? G.start1 : 0);
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, fr = lane & 15, fq = lane >> 4;
     const int b = blk / a.heads, h = blk % a.heads;
     const int Sq = a.Sq, Sk = a.Sk;
     const int RQ = rup(Sq, 32), RK = rup(Sk, 32);  // both row counts also serve as reduction lengths here
-    const int LDP = RK + 8, R16 = rup(Sq, 16), lds_s = rup(Sk, 16) + 1;
+    const int LDP = RK + 8, R16 = rup(Sq, 16), lds_s = rup(Sk, 16) + 1;  // mfma_bwd_lds has the same counts
     bf16* Qs = reinterpret_cast<bf16*>(smem_raw);
     bf16* Ks = Qs + RQ * LDT;
     bf16* Vs = Ks + RK * LDT;
@@ -398,9 +283,9 @@ __global__ __launch_bounds__(NT) void attn_bwd_mfma_kernel(MGroup G) {
 #endif
     ASTAMP(stp, 0);
     {
-        const TileRegs tq_ = tile_fetch(a.q + (int64_t)b * Sq * a.q_rs + h * D, a.q_rs, Sq, tid);
-        const TileRegs tk_ = tile_fetch(a.k + (int64_t)b * Sk * a.k_rs + h * D, a.k_rs, Sk, tid);
-        const TileRegs tv_ = tile_fetch(a.v + (int64_t)b * Sk * a.v_rs + h * D, a.v_rs, Sk, tid);
+        const TileRegs tq_ = tile_fetch((const bf16*)a.q + (int64_t)b * Sq * a.q_rs + h * D, a.q_rs, Sq, tid);
+        const TileRegs tk_ = tile_fetch((const bf16*)a.k + (int64_t)b * Sk * a.k_rs + h * D, a.k_rs, Sk, tid);
+        const TileRegs tv_ = tile_fetch((const bf16*)a.v + (int64_t)b * Sk * a.v_rs + h * D, a.v_rs, Sk, tid);
         const TileRegs to_ = tile_fetch(d_out + (int64_t)b * Sq * a.o_rs + h * D, a.o_rs, Sq, tid);
         tile_commit(Qs, tq_, Sq, RQ, tid);
         tile_commit(Ks, tk_, Sk, RK, tid);
@@ -418,7 +303,7 @@ __global__ __launch_bounds__(NT) void attn_bwd_mfma_kernel(MGroup G) {
             float4_t acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int ks = 0; ks < D; ks += 32)
-                acc = MFMA(frag_rows(dOs, LDT, ti * 16, ks, lane), frag_rows(Vs, LDT, tj * 16, ks, lane), acc);
+                acc = ATTN_MFMA(frag_rows(dOs, LDT, ti * 16, ks, lane), frag_rows(Vs, LDT, tj * 16, ks, lane), acc);
             const int j = tj * 16 + fr;
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
@@ -465,7 +350,7 @@ __global__ __launch_bounds__(NT) void attn_bwd_mfma_kernel(MGroup G) {
             for (int gi = 0; gi < ROW_G; ++gi) {
                 const int j0 = 4 * (part + ROW_L * gi);
                 dm[gi][0] = dm[gi][1] = dm[gi][2] = dm[gi][3] = 1.f;
-                if (row < Sq && j0 < Sk) dr.scale4(row, j0, Sk, dm[gi]);
+                if (row < Sq && j0 < Sk) dr.scale4<false>(row, j0, Sk, dm[gi]);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     v[gi][e] *= inv;          // P
@@ -492,6 +377,7 @@ __global__ __launch_bounds__(NT) void attn_bwd_mfma_kernel(MGroup G) {
     }
     __syncthreads();
     ASTAMP(stp, 4);
+    // third phase and bias tail: the same steps as in attn_long_bwd_mc (attention_long.hip), see the note there
     const int tq = rup(Sq, 16) / 16, tk = rup(Sk, 16) / 16;
     // 4 column tiles each for dQ (tq row tiles), dK and dV (tk row tiles): one list shared by the waves
     const int n_dq = tq * 4, n_dk = tk * 4;
@@ -500,17 +386,17 @@ __global__ __launch_bounds__(NT) void attn_bwd_mfma_kernel(MGroup G) {
         if (t < n_dq) {
             const int ti = t >> 2, tc = t & 3;  // dQ = dS K: k = j
             for (int ks = 0; ks < RK; ks += 32)
-                acc = MFMA(frag_tr(Ks, LDT, ks, tc * 16, lane), frag_rows(dSb, LDP, ti * 16, ks, lane), acc);
+                acc = ATTN_MFMA(frag_tr(Ks, LDT, ks, tc * 16, lane), frag_rows(dSb, LDP, ti * 16, ks, lane), acc);
             store_grad_tile(acc, dq + h * D, dq_rs, b * Sq, Sq, ti * 16, tc * 16, dbq ? csum[0][ti] : nullptr, lane);
         } else if (t < n_dq + n_dk) {
             const int u = t - n_dq, tj = u >> 2, tc = u & 3;  // dK = dS^T Q: k = i
             for (int ks = 0; ks < RQ; ks += 32)
-                acc = MFMA(frag_tr(Qs, LDT, ks, tc * 16, lane), frag_tr(dSb, LDP, ks, tj * 16, lane), acc);
+                acc = ATTN_MFMA(frag_tr(Qs, LDT, ks, tc * 16, lane), frag_tr(dSb, LDP, ks, tj * 16, lane), acc);
             store_grad_tile(acc, dk + h * D, dk_rs, b * Sk, Sk, tj * 16, tc * 16, dbk ? csum[1][tj] : nullptr, lane);
         } else {
             const int u = t - n_dq - n_dk, tj = u >> 2, tc = u & 3;  // dV = (P D)^T dO: k = i
             for (int ks = 0; ks < RQ; ks += 32)
-                acc = MFMA(frag_tr(dOs, LDT, ks, tc * 16, lane), frag_tr(Pdb, LDP, ks, tj * 16, lane), acc);
+                acc = ATTN_MFMA(frag_tr(dOs, LDT, ks, tc * 16, lane), frag_tr(Pdb, LDP, ks, tj * 16, lane), acc);
             store_grad_tile(acc, dv + h * D, dv_rs, b * Sk, Sk, tj * 16, tc * 16, dbv ? csum[2][tj] : nullptr, lane);
         }
     }
@@ -523,34 +409,38 @@ __global__ __launch_bounds__(NT) void attn_bwd_mfma_kernel(MGroup G) {
             const int nt = kind == 0 ? tq : tk;
             float s = csum[kind][0][c];
             for (int u = 1; u < nt; ++u) s += csum[kind][u][c];
-            dst[(int64_t)b * sg.db_bs + h * D + c] = s;  // partial row of this sample: summed over the batch by the reduce launch
+            dst[(int64_t)b * sg.g.db_bs + h * D + c] = s;  // partial row of this sample: summed over the batch by the reduce launch
         }
     }
 }
 
-}  // namespace
-
 // called by attention.hip for bf16 storage (arguments already validated there): n = 1 or 2 problems
-namespace {
 MSeg make_seg(const xggm_attn_problem& q, const uint64_t* rng) {
-    MSeg g;
-    g.a = MArgs{(const bf16*)q.q, (const bf16*)q.k, (const bf16*)q.v, q.mask, q.q_rs, q.k_rs, q.v_rs, q.o_rs,
-                q.B, q.heads, q.Sq, q.Sk, q.scale, q.p, rng, q.sid};
-    g.out = (bf16*)q.out;
-    g.out8 = (unsigned char*)q.out8;
-    g.qscale = q.qscale;
-    g.amax = q.amax;
-    g.amax_slots = q.amax_slots > 1 ? q.amax_slots : 1;
-    g.d_out = (const bf16*)q.d_out;
-    g.dq = (bf16*)q.dq; g.dk = (bf16*)q.dk; g.dv = (bf16*)q.dv;
-    g.dq_rs = q.dq_rs; g.dk_rs = q.dk_rs; g.dv_rs = q.dv_rs;
-    g.dbq = q.dbq; g.dbk = q.dbk; g.dbv = q.dbv; g.db_bs = q.db_bs;
-    return g;
+    MSeg s;
+    s.a = args_of(q, rng);
+    s.out = (bf16*)q.out;
+    s.out8 = (unsigned char*)q.out8;
+    s.qscale = q.qscale;
+    s.amax = q.amax;
+    s.amax_slots = q.amax_slots > 1 ? q.amax_slots : 1;
+    s.g = grad_of(q);
+    return s;
 }
 
-// one launch of G's one or two segments (`total` workgroups), the ranges of `pf` on top
+// one launch of one or two segments, the ranges of `pf` on top.  `fixed`: the kernel's static LDS
 template <typename K>
-int launch_group(K kernel, MGroup& G, int n, int total, size_t lds, const PrefetchArgs& pf, hipStream_t st, const char* who) {
+int launch_group(K kernel, bool backward, size_t fixed, const xggm_attn_problem* probs, int n, const uint64_t* rng,
+                 const PrefetchArgs& pf, hipStream_t st, const char* who) {
+    MGroup G;
+    size_t lds = 0;
+    int total = 0;
+    for (int i = 0; i < n; ++i) {
+        const xggm_attn_problem& q = probs[i];
+        G.s[i] = make_seg(q, rng);
+        lds = std::max(lds, backward ? mfma_bwd_lds(q.Sq, q.Sk, true) : mfma_fwd_lds(q.Sq, q.Sk, true));
+        if (i == 1) G.start1 = total;
+        total += q.B * q.heads;
+    }
     if (n == 1) {
         G.s[1] = G.s[0];
         G.start1 = total;
@@ -558,44 +448,19 @@ int launch_group(K kernel, MGroup& G, int n, int total, size_t lds, const Prefet
 #ifdef XGGM_STAMP
     G.stamp = g_attn_stamp;
 #endif
-    if (int e = xggm_reserve_lds(reinterpret_cast<const void*>(kernel), lds, who)) return e;
     G.total = total;
     G.pf = pf;
-    hipLaunchKernelGGL(kernel, dim3(total + pf.blocks), dim3(NT), lds, st, G);
-    return xggm_check_launch(who);
+    return launch(kernel, who, total + pf.blocks, NT, lds, fixed, st, G);
 }
+
 }  // namespace
 
 int xggm_attn_fwd_mfma_group(const xggm_attn_problem* probs, int n, const uint64_t* rng, const PrefetchArgs& pf, hipStream_t st) {
-    MGroup G;
-    size_t lds = 0;
-    int total = 0;
-    for (int i = 0; i < n; ++i) {
-        const xggm_attn_problem& q = probs[i];
-        G.s[i] = make_seg(q, rng);
-        const int RQ = (q.Sq + 15) / 16 * 16, RK = (q.Sk + 31) / 32 * 32, lds_s = (q.Sk + 15) / 16 * 16 + 1;
-        lds = std::max(lds, sizeof(bf16) * ((size_t)(RQ + 2 * RK) * LDT + (size_t)RQ * (RK + 8)) + sizeof(float) * RQ * lds_s);
-        if (i == 1) G.start1 = total;
-        total += q.B * q.heads;
-    }
-    return launch_group(attn_fwd_mfma_kernel, G, n, total, lds, pf, st, "xggm_attn_fwd(mfma)");
+    return launch_group(attn_fwd_mfma_kernel, false, sizeof(float) * (NT / 64) /* red8 */, probs, n, rng, pf, st, "xggm_attn_fwd(mfma)");
 }
 
 int xggm_attn_bwd_mfma_group(const xggm_attn_problem* probs, int n, const uint64_t* rng, const PrefetchArgs& pf, hipStream_t st) {
-    MGroup G;
-    size_t lds = 0;
-    int total = 0;
-    for (int i = 0; i < n; ++i) {
-        const xggm_attn_problem& q = probs[i];
-        G.s[i] = make_seg(q, rng);
-        const int RQ = (q.Sq + 31) / 32 * 32, RK = (q.Sk + 31) / 32 * 32, lds_s = (q.Sk + 15) / 16 * 16 + 1;
-        const int R16 = (q.Sq + 15) / 16 * 16;
-        lds = std::max(lds, sizeof(bf16) * ((size_t)(2 * RQ + 2 * RK) * LDT + 2 * (size_t)RQ * (RK + 8)) +
-                                sizeof(float) * 2 * R16 * lds_s);
-        if (i == 1) G.start1 = total;
-        total += q.B * q.heads;
-    }
-    return launch_group(attn_bwd_mfma_kernel, G, n, total, lds, pf, st, "xggm_attn_bwd(mfma)");
+    return launch_group(attn_bwd_mfma_kernel, true, sizeof(float) * 3 * ROW_TILES * D /* csum */, probs, n, rng, pf, st, "xggm_attn_bwd(mfma)");
 }
 
 #ifdef XGGM_STAMP
