@@ -523,6 +523,39 @@ int xggm_dropout_f32(const void* x, void* out, int64_t n, float p, const uint64_
 int xggm_dropout_bf16(const void* x, void* out, int64_t n, float p, const uint64_t* rng, uint32_t sid,
                       xggm_stream_t stream);
 
+/* ---- the graph kernels for 64 < N <= 128 objects (graph_long.hip) -------------------------------
+ * Each takes the arguments of its twin above and computes the same thing; N <= 64 and N > 128 are refused on the host
+ * before any launch (the twins keep refusing N > 64).  fp32 needs H % 4 == 0, the bf16 matrix-core path H % 8 == 0.
+ * GCNConv aggregate src/module/gcn.py:28; GIN src/module/gin.py:32. */
+int xggm_aggregate_long_f32(const float* M, const void* x, void* out, int B, int N, int H, int mode, float scale,
+                            const float* scale_ptr, float self_w, int accumulate, xggm_stream_t stream);
+int xggm_aggregate_long_bf16(const float* M, const void* x, void* out, int B, int N, int H, int mode, float scale,
+                             const float* scale_ptr, float self_w, int accumulate, xggm_stream_t stream);
+/* *out += sum_{b,i,c} dh[b,i,c] * (M @ x)[b,i,c]   (gradient of GIN's eps); ws: see XGGM_SUM_WS_FLOATS */
+int xggm_agg_dot_long_f32(const float* M, const void* x, const void* dh, float* out, int B, int N, int H, float* ws,
+                          xggm_stream_t stream);
+int xggm_agg_dot_long_bf16(const float* M, const void* x, const void* dh, float* out, int B, int N, int H, float* ws,
+                           xggm_stream_t stream);
+/* adjacency regeneration from S = x x^T: src/module/graph_generative_modeling.py:225-228 (argmax = first index of the
+ * column maximum, as torch.max) */
+int xggm_adj_regen_long_fwd(const float* S, float* adj, float* colmax, int32_t* argmax, int B, int N, xggm_stream_t stream);
+int xggm_adj_regen_long_bwd(const float* d_adj, const float* S, const float* adj, const float* colmax, const int32_t* argmax,
+                            float* dS, int B, int N, xggm_stream_t stream);
+/* adjacency initialisation: src/vqa/vqacpv2.py:195-202 + src/module/graph_utils.py:162-168; the enumeration of
+ * xggm_triu_index */
+int xggm_adj_init_long_fwd(const float* e, const float* randn, float* adj, float* gradlog, int B, int N, float sigma,
+                           const uint64_t* rng, uint32_t sid, xggm_stream_t stream);
+int xggm_adj_init_long_bwd(const float* d_adj, float* d_e, int B, int N, xggm_stream_t stream);
+/* graph attention (GATConv, src/module/gat.py:25-49) */
+int xggm_gat_att_long_fwd(const float* s, const float* adj, float* att, int B, int N, float alpha, xggm_stream_t stream);
+int xggm_gat_att_long_bwd_f32(const float* d_att, const float* att, const float* s, const float* adj, void* ds, int B, int N,
+                              float alpha, xggm_stream_t stream);
+int xggm_gat_att_long_bwd_bf16(const float* d_att, const float* att, const float* s, const float* adj, void* ds, int B, int N,
+                               float alpha, xggm_stream_t stream);
+/* adj_true of 65..128 objects: data/preprocess/vqa/compute_adjacency.py:38-45 + :90 (see xggm_cosine_adjacency_f32) */
+int xggm_cosine_adjacency_long_f32(const float* cls, const float* attr, float* adj, int n_img, int N, int D, float eps,
+                                   xggm_stream_t stream);
+
 /* ---- losses (scalars are device fp32; *loss must hold the running value, usually 0) ------
  * Sums over the whole grid are taken WITHOUT floating-point atomics: every workgroup leaves its partial in `ws`, the
  * workgroup that finishes last adds the partials in index order and updates *loss (same bits whatever the

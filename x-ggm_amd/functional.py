@@ -36,6 +36,7 @@ class Runtime:
         self.p_hidden = 0.1   # config.hidden_dropout_prob (src/lxrt/modeling.py:196)
         self.p_attn = 0.1     # config.attention_probs_dropout_prob
         self.p_readout = 0.5  # GCN/GIN read-out dropout (src/module/gcn.py:33)
+        self.long_graph = False  # opt-in of the root model: graph kernels for 65..128 objects (ops: ``long=``)
         self.pending = []     # deferred second stages of the LN backwards of the running backward pass
         self._hold_flush = False  # staged backward: the flushes of the stages below stage 0 are merged into one (``backward``)
         self._task = -1       # autograd graph task the pending jobs belong to
@@ -748,6 +749,7 @@ class GCNFn(Function):
         # bf16 storage: W (A x) = A (x W^T) -- the product first, then aggregate + residual + LayerNorm as ONE kernel
         # (xggm_agg_residual_ln_bf16) instead of three launches; the backward follows the same order (d y = A^T d t)
         swapped = ops.agg_residual_ln_ok(x, N)
+        lg = ctx.long = rt.long_graph
         for conv in gcn.gnn_layers:
             if swapped:
                 y, _ = ops.linear_fwd(hs[-1].view(B * N, H), a.w(conv.ctx_layer.weight), None)
@@ -755,7 +757,7 @@ class GCNFn(Function):
                                                   conv.layer_norm.bias.data, 1e-5)
                 convs.append((y, z.view(B * N, H), stats))
             else:
-                agg = ops.aggregate(adj, hs[-1])
+                agg = ops.aggregate(adj, hs[-1], long=lg)
                 t, _ = ops.linear_fwd(agg.view(B * N, H), a.w(conv.ctx_layer.weight), None)
                 h, z, stats = ops.ln_fwd(t, None, hs[-1].view(B * N, H), conv.layer_norm.weight.data,
                                          conv.layer_norm.bias.data, 1e-5)
@@ -805,7 +807,7 @@ class GCNFn(Function):
                                 d_res=dh[k], defer=rt.defer_list())
             if ctx.swapped:
                 # t = A y, y = h_k W^T (agg holds y): d y = A^T d t; d W = d y^T h_k; d h_k += d y W; d A += d t y^T
-                d_y = ops.aggregate(adj, d_t.view(B, N, H), mode=ops.AGG_TRANSPOSE).view(B * N, H)
+                d_y = ops.aggregate(adj, d_t.view(B, N, H), mode=ops.AGG_TRANSPOSE, long=ctx.long).view(B * N, H)
                 pd, _ = ops.p_dgrad(d_y, a.w(conv.ctx_layer.weight), into=dh[k])
                 ops.gemm_group(d_t.dtype, [_p_wgrad(rt, d_y, hs[k].view(B * N, H), conv.ctx_layer.weight), pd])
                 if ctx.needs_input_grad[3]:
@@ -814,7 +816,7 @@ class GCNFn(Function):
             pd, d_agg = ops.p_dgrad(d_t, a.w(conv.ctx_layer.weight))
             ops.gemm_group(d_t.dtype, [_p_wgrad(rt, d_t, agg.view(B * N, H), conv.ctx_layer.weight), pd])
             d_agg = d_agg.view(B, N, H)
-            ops.aggregate(adj, d_agg, mode=ops.AGG_TRANSPOSE, out=dh[k].view(B, N, H))
+            ops.aggregate(adj, d_agg, mode=ops.AGG_TRANSPOSE, out=dh[k].view(B, N, H), long=ctx.long)
             if ctx.needs_input_grad[3]:
                 d_adj = ops.bmm_nt(d_agg, hs[k], into=d_adj)  # the second layer's product adds into the first one's
         dx = dh[0].view(B, N, H) if ctx.needs_input_grad[2] else None
@@ -833,7 +835,8 @@ class GINFn(Function):
         x = x.contiguous()
         conv = gin.gnn_convs[0]
         eps = conv.eps.data
-        hin = ops.aggregate(adj, x, scale_ptr=eps, self_w=1.0)
+        ctx.long = rt.long_graph
+        hin = ops.aggregate(adj, x, scale_ptr=eps, self_w=1.0, long=ctx.long)
         act, u = ops.linear_fwd(hin.view(B * N, H), a.w(conv.linear[0].weight), conv.linear[0].bias.data,
                                 act=ops.ACT_GELU, want_preact=True)
         h1, z1, st1 = ops.ln_fwd(act, None, None, conv.linear[2].weight.data, conv.linear[2].bias.data, 1e-5)
@@ -875,9 +878,9 @@ class GINFn(Function):
         _wgrad(rt, d_u, hin.view(B * N, H), conv.linear[0].weight)
         d_hin = ops.linear_dgrad(d_u, a.w(conv.linear[0].weight)).view(B, N, H)
         # hin = x + (1+eps) A x
-        ops.agg_dot(adj, hs[0], d_hin, a.atomic_target(conv.eps))
+        ops.agg_dot(adj, hs[0], d_hin, a.atomic_target(conv.eps), long=ctx.long)
         dx = dh[0].view(B, N, H)
-        ops.aggregate(adj, d_hin, mode=ops.AGG_TRANSPOSE, scale_ptr=conv.eps.data, self_w=1.0, out=dx)
+        ops.aggregate(adj, d_hin, mode=ops.AGG_TRANSPOSE, scale_ptr=conv.eps.data, self_w=1.0, out=dx, long=ctx.long)
         d_adj = None
         if ctx.needs_input_grad[3]:
             d_adj = ops.bmm_nt(ops.scale(d_hin, 1.0, conv.eps.data), hs[0])
@@ -888,18 +891,19 @@ class RegenFn(Function):
     """adjacency regeneration (src/module/graph_generative_modeling.py:225-228)."""
 
     @staticmethod
-    def forward(ctx, x):
+    def forward(ctx, x, long=False):
         x = x.contiguous()
         S = ops.bmm_nt(x, x)
-        adj, colmax, argmax = ops.adj_regen_fwd(S)
+        ctx.long = long
+        adj, colmax, argmax = ops.adj_regen_fwd(S, long=long)
         ctx.saved = (x, S, adj, colmax, argmax)
         return adj
 
     @staticmethod
     def backward(ctx, d_adj):
         x, S, adj, colmax, argmax = ctx.saved
-        dS = ops.adj_regen_bwd(d_adj.contiguous(), S, adj, colmax, argmax)
-        return ops.aggregate(dS, x, mode=ops.AGG_SYMMETRIZE)
+        dS = ops.adj_regen_bwd(d_adj.contiguous(), S, adj, colmax, argmax, long=ctx.long)
+        return ops.aggregate(dS, x, mode=ops.AGG_SYMMETRIZE, long=ctx.long), None
 
 
 class AdjInitFn(Function):
@@ -907,15 +911,16 @@ class AdjInitFn(Function):
     src/module/graph_utils.py:162-168).  Returns (adj_noisy, grad_log_noise)."""
 
     @staticmethod
-    def forward(ctx, e, N, sigma, randn, rng, sid):
-        adj, g = ops.adj_init_fwd(e.contiguous(), N, sigma, randn=randn, rng=rng, sid=sid)
+    def forward(ctx, e, N, sigma, randn, rng, sid, long=False):
+        ctx.long = long
+        adj, g = ops.adj_init_fwd(e.contiguous(), N, sigma, randn=randn, rng=rng, sid=sid, long=long)
         ctx.mark_non_differentiable(g)
         ctx.set_materialize_grads(False)  # no zero-filled "gradient" of g (a framework fill per pass)
         return adj, g
 
     @staticmethod
     def backward(ctx, d_adj, _):
-        return (None if d_adj is None else ops.adj_init_bwd(d_adj.contiguous())), None, None, None, None, None
+        return (None if d_adj is None else ops.adj_init_bwd(d_adj.contiguous(), long=ctx.long)), None, None, None, None, None, None
 
 
 class FeatureNoiseFn(Function):
@@ -1177,11 +1182,11 @@ class GATFn(Function):
             h, _ = ops.linear_fwd(x2, a.w(conv.linear_layer.weight), None)
             a2 = a.w(conv.attn_layer.weight).view(2, D)
             s, _ = ops.linear_fwd(h, a2, None, out_f32=True)          # [B*N, 2]: a1.h_i, a2.h_j
-            att = ops.gat_att_fwd(s, adj, conv.alpha)
-            pre = ops.aggregate(att, h.view(B, N, D))
+            att = ops.gat_att_fwd(s, adj, conv.alpha, long=rt.long_graph)
+            pre = ops.aggregate(att, h.view(B, N, D), long=rt.long_graph)
             ops.elu_fwd(pre.view(B * N, D), out, k * D)
             saved.append((h, s, att))
-        ctx.rt, ctx.gat, ctx.p = rt, gat, p
+        ctx.rt, ctx.gat, ctx.p, ctx.long = rt, gat, p, rt.long_graph
         ctx.saved = (x2, adj, out, saved)
         ctx.dims = (B, N, H, D)
         return out.view(B, N, -1)
@@ -1198,8 +1203,8 @@ class GATFn(Function):
             h, s, att = saved[k]
             d_pre = ops.elu_bwd(d_out, out, k * D, D)
             d_att = ops.bmm_nt(d_pre.view(B, N, D), h.view(B, N, D))
-            d_h = ops.aggregate(att, d_pre.view(B, N, D), mode=ops.AGG_TRANSPOSE).view(B * N, D)
-            ds = ops.gat_att_bwd(d_att, att, s, adj, conv.alpha, h.dtype)
+            d_h = ops.aggregate(att, d_pre.view(B, N, D), mode=ops.AGG_TRANSPOSE, long=ctx.long).view(B * N, D)
+            ds = ops.gat_att_bwd(d_att, att, s, adj, conv.alpha, h.dtype, long=ctx.long)
             a2 = a.w(conv.attn_layer.weight).view(2, D)
             ga, acc = a.target(conv.attn_layer.weight)
             ops.linear_wgrad(ds, h, ga.view(2, D), acc)

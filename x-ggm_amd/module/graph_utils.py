@@ -30,12 +30,13 @@ def advance(device):
         ops.rng_advance(st, 1)
 
 
-def add_edge_noise_v2(adjs, sigma=0.2, randn=None):
+def add_edge_noise_v2(adjs, sigma=0.2, randn=None, long_graph=False):
     """noise = triu(randn,1)*sigma mirrored; returns (adjs + noise, -noise/sigma^2).
-    ``adjs`` fp32 [B,N,N].  ref: src/module/graph_utils.py:162-168"""
+    ``adjs`` fp32 [B,N,N] (more than 64 nodes: ``long_graph=True``, a model's ``Runtime.long_graph``).
+    ref: src/module/graph_utils.py:162-168"""
     B, N, _ = adjs.shape
     rng = None if randn is not None else _rng_for(adjs)
-    noise, g = ops.adj_init_fwd(None, N, sigma, randn=randn, rng=rng, sid=7001, B=B)
+    noise, g = ops.adj_init_fwd(None, N, sigma, randn=randn, rng=rng, sid=7001, B=B, long=long_graph)
     if randn is None:
         advance(adjs.device)
     return adjs + noise, g

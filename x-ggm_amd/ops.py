@@ -923,7 +923,16 @@ def visn_embed_bwd(dy, z1, z2, stats, boxes, g1, g2, grads, p, rng, sid):
 
 
 # ----------------------------------------------------------------------------- graph kernels
-def aggregate(Mx, x, mode=AGG_PLAIN, scale=1.0, scale_ptr=None, self_w=0.0, out=None):
+SHORT_N = 64  # objects the graph kernels of graph.hip / gat.hip / preprocess.hip take; 65..128: the _long twins (graph_long.hip)
+
+
+def _lg(name, N, long, suffix=""):
+    """symbol of a graph kernel: the ``_long`` twin only when the caller opted in AND N > 64.  N <= 64 always runs
+    today's kernel (same launches, same bits); N > 64 without the opt-in reaches today's entry point and its refusal."""
+    return name + ("_long" if long and N > SHORT_N else "") + suffix
+
+
+def aggregate(Mx, x, mode=AGG_PLAIN, scale=1.0, scale_ptr=None, self_w=0.0, out=None, long=False):
     """out = [out +] self_w*x + scale*(1+*scale_ptr) * M' @ x.  Mx fp32 [B,N,N], x T [B,N,H]."""
     _c(Mx, F32, "adjacency"), _c(x)
     B, N, H = x.shape
@@ -933,7 +942,7 @@ def aggregate(Mx, x, mode=AGG_PLAIN, scale=1.0, scale_ptr=None, self_w=0.0, out=
         out = torch.empty_like(x)
     else:
         assert out.shape == x.shape and out.dtype == x.dtype and out.is_contiguous()
-    call("xggm_aggregate_" + sfx(x.dtype), ptr(Mx), ptr(x), ptr(out), B, N, H, mode, float(scale),
+    call(_lg("xggm_aggregate", N, long, "_" + sfx(x.dtype)), ptr(Mx), ptr(x), ptr(out), B, N, H, mode, float(scale),
          ptr(scale_ptr), float(self_w), int(acc), stream())
     return out
 
@@ -956,33 +965,33 @@ def agg_residual_ln_ok(x, N):
     return x.dtype == BF16 and x.shape[-1] in (64, 128, 256, 768) and N <= 64
 
 
-def agg_dot(Mx, x, dh, out):
+def agg_dot(Mx, x, dh, out, long=False):
     B, N, H = x.shape
     _c(Mx, F32), _c(x), _c(dh, x.dtype), _c(out, F32)
     assert tuple(Mx.shape) == (B, N, N) and dh.shape == x.shape
-    call("xggm_agg_dot_" + sfx(x.dtype), ptr(Mx), ptr(x), ptr(dh), ptr(out), B, N, H, ptr(sum_ws(x.device)), stream())
+    call(_lg("xggm_agg_dot", N, long, "_" + sfx(x.dtype)), ptr(Mx), ptr(x), ptr(dh), ptr(out), B, N, H, ptr(sum_ws(x.device)), stream())
 
 
-def adj_regen_fwd(S):
+def adj_regen_fwd(S, long=False):
     _c(S, F32, "S")
     B, N, _ = S.shape
     adj = torch.empty_like(S)
     colmax = torch.empty((B, N), device=S.device, dtype=F32)
     argmax = torch.empty((B, N), device=S.device, dtype=torch.int32)
-    call("xggm_adj_regen_fwd", ptr(S), ptr(adj), ptr(colmax), ptr(argmax), B, N, stream())
+    call(_lg("xggm_adj_regen", N, long, "_fwd"), ptr(S), ptr(adj), ptr(colmax), ptr(argmax), B, N, stream())
     return adj, colmax, argmax
 
 
-def adj_regen_bwd(d_adj, S, adj, colmax, argmax):
+def adj_regen_bwd(d_adj, S, adj, colmax, argmax, long=False):
     _c(d_adj, F32, "d_adj")
     B, N, _ = S.shape
     assert d_adj.shape == S.shape
     dS = torch.empty_like(S)
-    call("xggm_adj_regen_bwd", ptr(d_adj), ptr(S), ptr(adj), ptr(colmax), ptr(argmax), ptr(dS), B, N, stream())
+    call(_lg("xggm_adj_regen", N, long, "_bwd"), ptr(d_adj), ptr(S), ptr(adj), ptr(colmax), ptr(argmax), ptr(dS), B, N, stream())
     return dS
 
 
-def adj_init_fwd(e, N, sigma, randn=None, rng=None, sid=0, B=None, want_gradlog=True):
+def adj_init_fwd(e, N, sigma, randn=None, rng=None, sid=0, B=None, want_gradlog=True, long=False):
     if e is not None:
         _c(e, F32, "encoder_adj output")
         B = e.shape[0]
@@ -993,15 +1002,15 @@ def adj_init_fwd(e, N, sigma, randn=None, rng=None, sid=0, B=None, want_gradlog=
         assert tuple(randn.shape) == (B, N, N)
     adj = torch.empty((B, N, N), device=dev, dtype=F32)
     g = torch.empty_like(adj) if want_gradlog else None
-    call("xggm_adj_init_fwd", ptr(e), ptr(randn), ptr(adj), ptr(g), B, N, float(sigma), ptr(rng), sid, stream())
+    call(_lg("xggm_adj_init", N, long, "_fwd"), ptr(e), ptr(randn), ptr(adj), ptr(g), B, N, float(sigma), ptr(rng), sid, stream())
     return adj, g
 
 
-def adj_init_bwd(d_adj):
+def adj_init_bwd(d_adj, long=False):
     _c(d_adj, F32, "d_adj")
     B, N, _ = d_adj.shape
     d_e = torch.empty((B, N * (N - 1) // 2), device=d_adj.device, dtype=F32)
-    call("xggm_adj_init_bwd", ptr(d_adj), ptr(d_e), B, N, stream())
+    call(_lg("xggm_adj_init", N, long, "_bwd"), ptr(d_adj), ptr(d_e), B, N, stream())
     return d_e
 
 
@@ -2714,20 +2723,20 @@ def tokenize_wordpiece(data, offsets, host_offsets, T, tables, outputs=("ids", "
 
 
 # ----------------------------------------------------------------------------- graph attention
-def gat_att_fwd(s, adj, alpha):
+def gat_att_fwd(s, adj, alpha, long=False):
     _c(s, F32, "s"), _c(adj, F32, "adj")
     B, N, _ = adj.shape
     assert tuple(s.shape) == (B * N, 2)
     att = torch.empty_like(adj)
-    call("xggm_gat_att_fwd", ptr(s), ptr(adj), ptr(att), B, N, float(alpha), stream())
+    call(_lg("xggm_gat_att", N, long, "_fwd"), ptr(s), ptr(adj), ptr(att), B, N, float(alpha), stream())
     return att
 
 
-def gat_att_bwd(d_att, att, s, adj, alpha, dt):
+def gat_att_bwd(d_att, att, s, adj, alpha, dt, long=False):
     _c(d_att, F32), _c(att, F32), _c(s, F32), _c(adj, F32)
     B, N, _ = adj.shape
     ds = torch.empty((B * N, 2), device=adj.device, dtype=dt)
-    call("xggm_gat_att_bwd_" + sfx(dt), ptr(d_att), ptr(att), ptr(s), ptr(adj), ptr(ds), B, N, float(alpha), stream())
+    call(_lg("xggm_gat_att", N, long, "_bwd_" + sfx(dt)), ptr(d_att), ptr(att), ptr(s), ptr(adj), ptr(ds), B, N, float(alpha), stream())
     return ds
 
 

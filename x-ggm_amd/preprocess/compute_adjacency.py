@@ -6,7 +6,8 @@ of 666 ``torch.cosine_similarity`` calls filling the upper triangle incl. the di
 ``matrix / matrix.max()`` (:90).  The GQA twin (data/preprocess/gqa/compute_adjacency.py) is the same arithmetic.
 The embedding extraction itself needs ``bert-base-uncased`` (a download) and stays outside: this module takes
 the embeddings -- in practice a [vocabulary, 768] table per label file, gathered by the objects' ids -- and runs
-the similarity for a whole split in one launch (``xggm_cosine_adjacency_f32``), one workgroup per image."""
+the similarity for a whole split in one launch (``xggm_cosine_adjacency_f32``; ``xggm_cosine_adjacency_long_f32``
+for 65..128 objects), one workgroup per image."""
 import torch
 
 from .. import _lib
@@ -26,7 +27,9 @@ def compute_cosin_sim_v2(matrix1, matrix2, normalize=False):
     n, N, D = a.shape
     assert b.shape == a.shape
     out = torch.empty((n, N, N), device=a.device, dtype=torch.float32)
-    call("xggm_cosine_adjacency_f32", ptr(a), ptr(b), ptr(out), n, N, D, 1e-6, stream())
+    # 65..128 objects (100-box features): the kernel laid out for them, picked by N alone -- there is no model to opt in on
+    call("xggm_cosine_adjacency_long_f32" if N > 64 else "xggm_cosine_adjacency_f32", ptr(a), ptr(b), ptr(out), n, N, D,
+         1e-6, stream())
     if not normalize:
         # un-normalised form: the maximum of adj + adj^T is max over (i <= j) of (1 + [i == j]) cos_ij; recover it
         # from the diagonal-doubled matrix the kernel divided by it

@@ -35,7 +35,7 @@ def _gather_before_state_dict(module, prefix, keep_vars):
         rt.arena.gather_sharded_state()
 
 
-def bind_root(root, compute_dtype=None):
+def bind_root(root, compute_dtype=None, long_graph=None):
     """(re)bind all sub-modules of ``root``; the outermost model calls this last, so nested
     roots (an encoder inside a VQAModel) end up pointing at the outermost one."""
     ref = weakref.ref(root)
@@ -50,6 +50,12 @@ def bind_root(root, compute_dtype=None):
         object.__setattr__(root, "compute_dtype", compute_dtype)
     elif not hasattr(root, "compute_dtype"):
         object.__setattr__(root, "compute_dtype", DEFAULT_DTYPE)
+    # graph kernels for 65..128 objects: the root's opt-in (a plain attribute, no parameter or buffer: state_dict keys are
+    # the same with and without it); ``runtime_of`` copies it to ``Runtime.long_graph``
+    if long_graph is not None:
+        object.__setattr__(root, "long_graph", bool(long_graph))
+    elif not hasattr(root, "long_graph"):
+        object.__setattr__(root, "long_graph", False)
     object.__setattr__(root, "_xg_arena", None)
     object.__setattr__(root, "_xg_rt", None)
     object.__setattr__(root, "_xg_shadow_dirty", False)
@@ -83,6 +89,7 @@ def runtime_of(module):
         rt.arena.sync_shadow()
         object.__setattr__(root, "_xg_shadow_dirty", False)
     rt.training = root.training
+    rt.long_graph = bool(getattr(root, "long_graph", False))
     return rt
 
 

@@ -222,7 +222,8 @@ def forward_backward_ggm(model, bce_loss, feats, boxes, sent, target, adj_true, 
     x, x_fuse = XF.fan_out(x, 2)
     if branch == "rel":
         e = model.encoder_adj(x)
-        adj_noise, grad_log_noise = XF.AdjInitFn.apply(e, N, sigma, randn, None if randn is not None else rt.rng, 9001)
+        adj_noise, grad_log_noise = XF.AdjInitFn.apply(e, N, sigma, randn, None if randn is not None else rt.rng, 9001,
+                                                       rt.long_graph)
         node_feats, adj_noise = model.generator(feat_seq[1], adj_noise)
         adj_noise, adj_kl = XF.fan_out(adj_noise, 2)
         # loss = bce * A + 6 * (kl_weight * (kl * A) + dsm), the weights folded into the loss kernels

@@ -17,7 +17,7 @@ class XGGMModel(nn.Module):
     src/vqa/vqacpv2_model.py:52-131, src/gqa/gqa_ood_model.py:52-123)."""
 
     def __init__(self, num_answers, gnn='GCN', n_layers=2, args=None, max_seq_length=MAX_VQA_LENGTH,
-                 compute_dtype=None, config=None, tokenizer=None, n_objects=36):
+                 compute_dtype=None, config=None, tokenizer=None, n_objects=36, long_graph=False):
         super().__init__()
         if args is None:
             from ..param import args as default_args
@@ -30,11 +30,11 @@ class XGGMModel(nn.Module):
         self.logit_fc = MLPHead(hid_dim, hid_dim * 2, 1e-12, d_out=num_answers, out_f32=True)
         self.logit_fc.apply(self.lxrt_encoder.model.init_bert_weights)
         if gnn == 'GCN':
-            self.generator = GCNGenerator(hidden_dim=hid_dim, n_layers=n_layers)
+            self.generator = GCNGenerator(hidden_dim=hid_dim, n_layers=n_layers, long_graph=long_graph)
         elif gnn == 'GIN':
-            self.generator = GINGenerator(hidden_dim=hid_dim, n_layers=n_layers)
+            self.generator = GINGenerator(hidden_dim=hid_dim, n_layers=n_layers, long_graph=long_graph)
         elif gnn == 'GAT':
-            self.generator = GATGenerator(hidden_dim=hid_dim, n_layers=n_layers)
+            self.generator = GATGenerator(hidden_dim=hid_dim, n_layers=n_layers, long_graph=long_graph)
         else:
             raise ModuleNotFoundError
         # relation / node initialisation (nn.LayerNorm default eps 1e-5)
@@ -49,7 +49,9 @@ class XGGMModel(nn.Module):
             self._enc_tail_prefixes = tuple(base + s for s in ("visn_self_att.", "visn_inter.", "visn_output."))
         else:
             self._enc_tail_prefixes = ()
-        bind_root(self, compute_dtype)
+        # long_graph: GGM passes with 65..128 objects run the graph kernels built for them (off: such a pass is refused,
+        # as before; at <= 64 objects the flag changes nothing)
+        bind_root(self, compute_dtype, long_graph=long_graph)
 
     def forward(self, feat, pos, sent):
         """feat (b, o, f), pos (b, o, 4), sent: list of strings (needs a tokenizer) or a tuple
