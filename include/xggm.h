@@ -1255,7 +1255,9 @@ int xggm_add_n_f32(const float* a, const float* b, const float* c, const float* 
 int xggm_add_n_bf16(const void* a, const void* b, const void* c, const void* d, void* out, int64_t n, xggm_stream_t stream);
 /* Rows of a [V, H] table by index (H % 4 == 0; indices outside [0, V) are skipped): dst[i, :] = bf16(src[idx[i], :]) and
  * dst[idx[i], :] = src[i, :] (duplicate indices must carry identical rows).  Data parallelism exchanges only the rows of
- * the word-embedding gradient (nn.Embedding(30522, 768), src/lxrt/modeling.py:283) that some rank touched. */
+ * the word-embedding gradient (nn.Embedding(30522, 768), src/lxrt/modeling.py:283) that some rank touched.
+ * Four elements per access: gather needs src 16-byte and dst 8-byte aligned, scatter src and dst 8-byte aligned; a
+ * misaligned pointer is refused on the host. */
 int xggm_gather_rows_bf16(const float* src, const int64_t* idx, void* dst, int n, int H, int64_t V, xggm_stream_t stream);
 int xggm_scatter_rows_bf16(const void* src, const int64_t* idx, void* dst, int n, int H, int64_t V, xggm_stream_t stream);
 /* dst [rows, ld] bf16 = cast(src [rows, n], fp32 if src_f32 else bf16), columns n .. ld - 1 zero: the padded row stride
@@ -1280,7 +1282,8 @@ int xggm_sigmoid_bwd_bf16(const float* dy, const float* y, void* out, int64_t n,
 /* out(T) = dy(T) * (1 - y(T)^2): backward of BertPooler's tanh (src/lxrt/modeling.py:619) */
 int xggm_tanh_bwd_f32(const void* dy, const void* y, void* out, int64_t n, xggm_stream_t stream);
 int xggm_tanh_bwd_bf16(const void* dy, const void* y, void* out, int64_t n, xggm_stream_t stream);
-/* out(T) = x(fp32): loader tensors (feats, boxes) and fp32 logit gradients entering the T path */
+/* out(T) = x(fp32): loader tensors (feats, boxes) and fp32 logit gradients entering the T path.  Four elements per
+ * access: x 16-byte aligned, out 16-byte (fp32) / 8-byte (bf16) aligned, else refused on the host. */
 int xggm_cast_from_f32_f32(const float* x, void* out, int64_t n, xggm_stream_t stream);
 int xggm_cast_from_f32_bf16(const float* x, void* out, int64_t n, xggm_stream_t stream);
 

@@ -41,26 +41,27 @@ template <typename T> __global__ __launch_bounds__(NT) void cast_kernel(const fl
 #define EW_API(SUF, T)                                                                                                   \
     extern "C" int xggm_scale_##SUF(const void* x, void* out, int64_t n, float scale, const float* scale_ptr,          \
                                     hipStream_t st) {                                                                   \
-        XGGM_REQUIRE(x && out && n > 0, "xggm_scale: bad arguments");                                                    \
+        XGGM_REQUIRE(x && out && n > 0, "xggm_scale_" #SUF ": bad arguments");                                           \
         hipLaunchKernelGGL((scale_kernel<T>), dim3(grid1d(n)), dim3(NT), 0, st, (const T*)x, (T*)out, n, scale,         \
                            scale_ptr);                                                                                  \
         return xggm_check_launch("xggm_scale");                                                                         \
     }                                                                                                                    \
     extern "C" int xggm_sigmoid_bwd_##SUF(const float* dy, const float* y, void* out, int64_t n, hipStream_t st) {      \
-        XGGM_REQUIRE(dy && y && out && n > 0, "xggm_sigmoid_bwd: bad arguments");                                        \
+        XGGM_REQUIRE(dy && y && out && n > 0, "xggm_sigmoid_bwd_" #SUF ": bad arguments");                               \
         hipLaunchKernelGGL((sigmoid_bwd_kernel<T>), dim3(grid1d(n)), dim3(NT), 0, st, dy, y, (T*)out, n);               \
         return xggm_check_launch("xggm_sigmoid_bwd");                                                                   \
     }                                                                                                                    \
     extern "C" int xggm_tanh_bwd_##SUF(const void* dy, const void* y, void* out, int64_t n, hipStream_t st) {           \
-        XGGM_REQUIRE(dy && y && out && n > 0, "xggm_tanh_bwd: bad arguments");                                           \
+        XGGM_REQUIRE(dy && y && out && n > 0, "xggm_tanh_bwd_" #SUF ": bad arguments");                                  \
         hipLaunchKernelGGL((tanh_bwd_kernel<T>), dim3(grid1d(n)), dim3(NT), 0, st, (const T*)dy, (const T*)y, (T*)out,  \
                            n);                                                                                          \
         return xggm_check_launch("xggm_tanh_bwd");                                                                      \
     }                                                                                                                    \
     extern "C" int xggm_cast_from_f32_##SUF(const float* x, void* out, int64_t n, hipStream_t st) {                     \
-        XGGM_REQUIRE(x && out && n > 0, "xggm_cast_from_f32: bad arguments");                                            \
-        XGGM_REQUIRE(reinterpret_cast<uintptr_t>(x) % 16 == 0 && reinterpret_cast<uintptr_t>(out) % 8 == 0,             \
-                     "xggm_cast_from_f32: misaligned pointers");                                                        \
+        XGGM_REQUIRE(x && out && n > 0, "xggm_cast_from_f32_" #SUF ": bad arguments");                                   \
+        /* four elements per store: 16 bytes of fp32, 8 bytes of bf16 */                                                 \
+        XGGM_REQUIRE(reinterpret_cast<uintptr_t>(x) % 16 == 0 && reinterpret_cast<uintptr_t>(out) % (4 * sizeof(T)) == 0, \
+                     "xggm_cast_from_f32_" #SUF ": misaligned pointers");                                                \
         hipLaunchKernelGGL((cast_kernel<T>), dim3(grid1d(n / 4 + 1)), dim3(NT), 0, st, x, (T*)out, n);                  \
         return xggm_check_launch("xggm_cast_from_f32");                                                                 \
     }
@@ -260,11 +261,16 @@ extern "C" int xggm_pad_rows_bf16(const void* src, int src_f32, void* dst, int r
 
 extern "C" int xggm_gather_rows_bf16(const float* src, const int64_t* idx, void* dst, int n, int H, int64_t V, hipStream_t st) {
     XGGM_REQUIRE(src && idx && dst && n > 0 && H > 0 && H % 4 == 0 && V > 0, "xggm_gather_rows_bf16: bad arguments");
+    // a lane reads four floats (16 bytes) and writes four bf16 (8 bytes); H % 4 == 0 keeps every row on that grid
+    XGGM_REQUIRE(reinterpret_cast<uintptr_t>(src) % 16 == 0 && reinterpret_cast<uintptr_t>(dst) % 8 == 0,
+                 "xggm_gather_rows_bf16: misaligned pointers (src 16 bytes, dst 8 bytes)");
     hipLaunchKernelGGL(gather_rows_kernel, dim3(std::min(ceil_div(n, NT / 64), 2048)), dim3(NT), 0, st, src, idx, (bf16*)dst, n, H, V);
     return xggm_check_launch("xggm_gather_rows_bf16");
 }
 extern "C" int xggm_scatter_rows_bf16(const void* src, const int64_t* idx, void* dst, int n, int H, int64_t V, hipStream_t st) {
     XGGM_REQUIRE(src && idx && dst && n > 0 && H > 0 && H % 4 == 0 && V > 0, "xggm_scatter_rows_bf16: bad arguments");
+    XGGM_REQUIRE((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) % 8 == 0,
+                 "xggm_scatter_rows_bf16: misaligned pointers (src and dst 8 bytes)");
     hipLaunchKernelGGL(scatter_rows_kernel, dim3(std::min(ceil_div(n, NT / 64), 2048)), dim3(NT), 0, st, (const bf16*)src, idx, (bf16*)dst, n, H, V);
     return xggm_check_launch("xggm_scatter_rows_bf16");
 }

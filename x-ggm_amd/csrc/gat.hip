@@ -109,21 +109,21 @@ extern "C" int xggm_gat_att_fwd(const float* s, const float* adj, float* att, in
         return xggm_check_launch("xggm_gat_att_bwd");                                                                   \
     }                                                                                                                    \
     extern "C" int xggm_elu_fwd_##SUF(const void* x, void* out, int M, int D, int64_t ld_out, hipStream_t st) {         \
-        XGGM_REQUIRE(x && out && M > 0 && D > 0 && ld_out >= D, "xggm_elu_fwd: bad arguments");                          \
+        XGGM_REQUIRE(x && out && M > 0 && D > 0 && ld_out >= D, "xggm_elu_fwd_" #SUF ": bad arguments");                 \
         hipLaunchKernelGGL((elu_fwd_kernel<T>), dim3(grid1d((int64_t)M * D)), dim3(NT), 0, st, (const T*)x, (T*)out, M,  \
                            D, ld_out);                                                                                  \
         return xggm_check_launch("xggm_elu_fwd");                                                                       \
     }                                                                                                                    \
     extern "C" int xggm_elu_bwd_##SUF(const void* dy, const void* y, void* dx, int M, int D, int64_t ld,                \
                                       hipStream_t st) {                                                                 \
-        XGGM_REQUIRE(dy && y && dx && M > 0 && D > 0 && ld >= D, "xggm_elu_bwd: bad arguments");                         \
+        XGGM_REQUIRE(dy && y && dx && M > 0 && D > 0 && ld >= D, "xggm_elu_bwd_" #SUF ": bad arguments");                \
         hipLaunchKernelGGL((elu_bwd_kernel<T>), dim3(grid1d((int64_t)M * D)), dim3(NT), 0, st, (const T*)dy,            \
                            (const T*)y, (T*)dx, M, D, ld);                                                              \
         return xggm_check_launch("xggm_elu_bwd");                                                                       \
     }                                                                                                                    \
     extern "C" int xggm_dropout_##SUF(const void* x, void* out, int64_t n, float p, const uint64_t* rng, uint32_t sid,  \
                                       hipStream_t st) {                                                                 \
-        XGGM_REQUIRE(x && out && n > 0 && p > 0.f && p < 1.f && rng, "xggm_dropout: bad arguments");                     \
+        XGGM_REQUIRE(x && out && n > 0 && p > 0.f && p < 1.f && rng, "xggm_dropout_" #SUF ": bad arguments");            \
         hipLaunchKernelGGL((dropout_kernel<T>), dim3(grid1d(n)), dim3(NT), 0, st, (const T*)x, (T*)out, n, p, rng,      \
                            sid);                                                                                        \
         return xggm_check_launch("xggm_dropout");                                                                       \
