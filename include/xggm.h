@@ -1441,6 +1441,32 @@ typedef struct xggm_train_log {
 int xggm_train_log_append(const float* const* src, const float* mul, int n, int kind, const int64_t* step,
                           xggm_train_log* log, xggm_stream_t stream);
 
+/* xggm_train_log_fold: the mean of the data-parallel ranks' logs, folded into this rank's ring.  The reference averages
+ * the per-replica losses of every step, `loss.mean()` and `losses.mean(0)` (src/pretrain/lxmert_pretrain.py:311-313,
+ * :323-325); here every rank appends to a log of its own and, at read-back time, the rings are all-gathered into device
+ * buffers -- one collective per read-back, never per step -- and ONE launch folds them.
+ *
+ * The n records are ALL records of the log since its reset, not wrapped: record i lives in row i (n <= capacity).  Rank
+ * r's copy of record i: values vals[r * val_stride + i * COLS + c], kind word kinds[r * kind_stride + i] (kind | present
+ * mask << 8, as the append stores it), step steps[r * step_stride + i] (steps NULL: not compared), cursor
+ * cursors[r * cursor_stride] (cursors NULL: not compared); strides in elements of the respective type.  Per record and
+ * column the `world` fp32 values are added in rank order (((v0 + v1) + v2) ...) and multiplied once by the fp32 value
+ * 1 / world; a column is present in the result only if it is present on EVERY rank, an absent one holds 0.  world == 1
+ * is the identity on values and kind words.  A NaN on any rank is a NaN in the mean.  Written: log->values and
+ * log->kinds rows [0, n), log->sums and log->counts (all KINDS: recomputed in fp64 over the folded records in record
+ * order, as the appends would have accumulated them), log->first_bad (-1, or *cursor - n + the first folded record with
+ * a non-finite present column) and *flag: -1 when for every record the kind word and the step are the same on every rank
+ * and every cursor equals n; else the index of the first record that disagrees, or n when only a cursor does.  The fold
+ * is carried out either way; log->steps and log->cursor are left alone.
+ *
+ * One workgroup, fixed orders, no floating-point atomics: the same bits on every rank.  No store leaves the described
+ * buffers under any input; no allocation, no host synchronisation.  Refused before any launch: world < 1, a null log /
+ * ring buffer / vals / kinds / flag, capacity <= 0 or >= 2^31 - 1, n outside [1, capacity], (world > 1) a rank stride
+ * shorter than n records, 64-bit buffers that are not 8-byte aligned, values / kinds that are not 4-byte aligned. */
+int xggm_train_log_fold(const float* vals, const int32_t* kinds, const int64_t* steps, const int64_t* cursors,
+                        int64_t val_stride, int64_t kind_stride, int64_t step_stride, int64_t cursor_stride, int world,
+                        int64_t n, xggm_train_log* log, int64_t* flag, xggm_stream_t stream);
+
 /* xggm_tokenize_wordpiece: sentences -> token ids for a whole corpus in ONE launch: what the host does per sentence with
  * BertTokenizer.tokenize(sent.strip()) (src/lxrt/tokenization.py:72-348) followed by convert_sents_to_features
  * (src/lxrt/entry.py:37-72; src/pretrain/lxmert_pretrain.py:149 for the pre-training set) -- clean the text, put spaces

@@ -220,6 +220,48 @@ class TrainLog:
         torch.cuda.current_stream(self.buf.device).synchronize()
         return decode_packed(self.host, self.capacity)
 
+    def fold(self, n, group=None):
+        """COLLECTIVE read-back under data parallelism (every rank of ``group`` calls it with the same ``n``): the ranks'
+        rings are all-gathered -- ONE collective per read-back, never per step --, one launch (``ops.train_log_fold``) replaces
+        this rank's ``n`` records, all of them since ``reset()``, by their mean over the ranks (the reference's
+        ``loss.mean()`` / ``losses.mean(0)`` over its replicas, src/pretrain/lxmert_pretrain.py:311-313), and the log is
+        read as ``read()`` reads it: the same bits on every rank.  RuntimeError (on every rank: the flag is computed from
+        the same gathered words) when the ranks disagree on the kind, the present columns or the step of a record or have
+        not logged ``n`` records each -- replicas that have come apart.  A one-rank group: ``read()``."""
+        import torch.distributed as dist
+        from . import trainlog as T
+        world = dist.get_world_size(group) if dist.is_initialized() else 1
+        n = int(n)
+        if world == 1:
+            return self.read()
+        if not 1 <= n <= self.capacity:
+            raise ValueError("TrainLog.fold: %d records, the log holds 1 .. %d" % (n, self.capacity))
+        dev, W = self.buf.device, self.buf.numel()
+        if getattr(self, "_gathered", None) is None or self._gathered.shape[0] != world:
+            self._gathered = torch.zeros((world, W), dtype=torch.int64, device=dev)
+            self._flag = torch.zeros(1, dtype=torch.int64, device=dev)
+            self._flag_host = torch.zeros(1, dtype=torch.int64).pin_memory()
+        if dist.get_backend(group) == "nccl":
+            dist.all_gather_into_tensor(self._gathered, self.buf, group=group)
+        else:  # gloo, the test transport: through the host
+            self.host.copy_(self.buf, non_blocking=True)
+            torch.cuda.current_stream(dev).synchronize()
+            parts = [torch.empty(W, dtype=torch.int64) for _ in range(world)]
+            dist.all_gather(parts, self.host.clone(), group=group)
+            self._gathered.copy_(torch.stack(parts))
+        flat, C, cap = self._gathered.view(-1), T.COLS, self.capacity
+        o = T.HEADER + cap
+        ops.train_log_fold(self, flat[o:].view(torch.float32), flat[o + cap * C // 2:].view(torch.int32), world, n, self._flag,
+                           steps=flat[T.HEADER:], cursors=flat, strides=(2 * W, 2 * W, W, W))
+        self._flag_host.copy_(self._flag, non_blocking=True)
+        rec = self.read()  # one wait for both transfers
+        flag = int(self._flag_host[0])
+        if flag >= 0:
+            raise RuntimeError("training log fold: " + ("a rank has not logged %d records" % n if flag == n else
+                               "the ranks disagree on record %d (its kind, its present columns or its optimiser step)" % flag)
+                               + " -- the data-parallel replicas have come apart")
+        return rec
+
     def average_loss(self, batch_size, rec=None):
         """the reference's Train/average_loss (src/vqa/vqacpv2.py:179, :262): the sum of the plain passes' losses since
         ``reset()``, each divided by the batch size, over their count -- sums[PLAIN][LOSS] / batch_size / counts[PLAIN].
@@ -744,7 +786,17 @@ class CapturedPredictor:
 
 class CapturedPretrainer:
     """The LXMERT pre-training step (``LXMERT.train_batch`` / ``valid_batch``, src/pretrain/lxmert_pretrain.py:308-326) as
-    ONE replayed graph per step: one pass kind, one graph, no data parallelism.
+    ONE replayed graph per step: one pass kind, one graph.  Data parallel (a model prepared by
+    ``pretrain.lxmert_pretrain.enable_data_parallel``: one process per GPU, the reference's ``--multiGPU``,
+    src/pretrain/lxmert_pretrain.py:255-256) the training step is TWO graphs with the gradient exchange between them:
+    graph F = swap, masking, forward, backward; ``_sync_grads`` live on the communicator, never inside a capture; graph U =
+    ``clip_and_step(..., advance=True)`` and the log appends -- captured with ``capture_error_mode="thread_local"``
+    (``CapturedTrainer`` says why).  The eager path makes the same calls in the same order: the same bits.  ``step()``
+    and ``check()`` are then COLLECTIVE calls (every rank makes them, equally often); ``valid_step()`` exchanges nothing and
+    stays one graph, so ranks may validate on different numbers of batches.  Every rank logs its OWN losses;
+    ``TrainLog.fold`` averages the logs over the ranks at read-back time.  The constructor is collective too (its warm-up
+    steps exchange) and restores the state every rank started from, so equal replicas stay equal.  Without
+    ``enable_data_parallel`` nothing of this exists: one graph, the same launches.
 
         feats = DeviceFeatures.from_args(args, swap=True, vocab_size=..., max_labels=K)
         tr = CapturedPretrainer(model, optim, batch, feats, train_log=TrainLog(n, dev), answer_log=AnswerLog(n * B, dev, False))
@@ -824,6 +876,11 @@ class CapturedPretrainer:
         self.columns = cols  # column of the i-th entry of the ``losses`` the model returns
         self.use_graph = use_graph
         self.graphs, self.outputs = {}, {}
+        # data parallelism (pretrain.lxmert_pretrain.enable_data_parallel): the training step is two graphs with the live
+        # gradient exchange between them; a capture beside a process group polices its own thread only (CapturedTrainer)
+        self.split = getattr(model, "_grad_sync", None) is not None
+        self.capture_mode = "thread_local" if self.split else "global"
+        self._emb_ids = None  # the ids the captured forward looks up (the sparse exchange of the word table reads them)
         self._flags = torch.zeros(1, dtype=torch.int64, device=self.static["input_ids"].device)
         self._flags_host = torch.zeros(1, dtype=torch.int64).pin_memory()
         if use_graph:
@@ -853,13 +910,28 @@ class CapturedPretrainer:
         if self.answer_log is not None:
             ops.answer_pick(ans if ans.dtype == torch.float32 else ans.float(), self.answer_log)
 
-    def _train_pass(self, s):
+    def _fwd_bwd(self, s):
+        """graph F of a data-parallel step: swap, masking, forward, backward"""
         self.model.train()
+        if self.split:
+            # the gradients are zero here (the previous update cleared them) and a validation forward in between adds to
+            # none: the look-up of this forward is the ONE the sparse exchange of the word table has to cover
+            self.rt.arena.emb_uses = 0
         total, losses, ans = self.model(*self._corrupt(s))
         self.rt.backward(total)
+        return total.detach(), losses, ans
+
+    def _update(self, loss, losses, ans):
+        """graph U of a data-parallel step: clip, update, the rng advance, the log appends"""
         norm = clip_and_step(self.model, self.optim, self.clip, advance=True)
-        loss = total.detach()
         self._observe(self.train_log, loss, losses, norm, ans)
+        return norm
+
+    def _train_pass(self, s):
+        loss, losses, ans = self._fwd_bwd(s)
+        if self.split:
+            _sync_grads(self.model)  # live, never inside a capture: the ranks' gradients are averaged where they lie
+        norm = self._update(loss, losses, ans)
         return loss, losses, ans, norm
 
     def _valid_pass(self, s):
@@ -911,10 +983,32 @@ class CapturedPretrainer:
                     run(self.static)
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
+        mode = {}
+        if self.split:
+            mode = dict(capture_error_mode=self.capture_mode)
+        if self.split and self.optim is not None:
+            # nothing of the eager warm-up exchanges may still be in flight (or polled) while graphs are captured; every
+            # rank is here: the warm-up is the same number of steps everywhere.  (A validation-only engine exchanged nothing
+            # and may be built on one rank alone -- a ragged validation slice -- so it must not wait for the others.)
+            import torch.distributed as dist
+            dist.barrier()
+            torch.cuda.synchronize()
         with _quiet_gc():
             for kind, run in self._passes():
                 g = torch.cuda.CUDAGraph()  # a memory pool per graph: the outputs of one are not the other's scratch
-                with torch.cuda.graph(g):
+                if kind == "train" and self.split:
+                    # forward + backward | live exchange | clip + update + logs.  The two graphs share a pool: U reads what
+                    # F left (loss, terms, answer scores), which stays referenced here and is therefore never handed out
+                    from .dist import active_ranges
+                    with torch.cuda.graph(g, **mode):
+                        loss, losses, ans = self._fwd_bwd(self.static)
+                    ranges, self._emb_ids = active_ranges(self.rt.arena), getattr(self.rt, "emb_ids", None)
+                    gu = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(gu, pool=g.pool(), **mode):
+                        norm = self._update(loss, losses, ans)
+                    self.graphs[kind], self.outputs[kind] = (g, gu, ranges), (loss, losses, ans, norm)
+                    continue
+                with torch.cuda.graph(g, **mode):
                     out = run(self.static)
                 self.graphs[kind], self.outputs[kind] = g, out
         torch.cuda.synchronize()
@@ -960,21 +1054,57 @@ class CapturedPretrainer:
         if not self.use_graph:
             return run(self.static)
         runtime_of(self.model)  # weights loaded since the last step (load_state_dict): the bf16 shadows are refreshed here
-        self.graphs[kind].replay()
+        g = self.graphs[kind]
+        if isinstance(g, tuple):  # data parallel: the exchange runs live between the two graphs
+            # host-side bookkeeping a replay never runs (CapturedTrainer.run_pass): the sparse exchange of the word table
+            # gathers the rows of the ids THIS step's forward looks up, once
+            self.rt.emb_ids = self._emb_ids
+            self.rt.arena.emb_uses = 1
+            g[0].replay()
+            self.model._grad_sync.sync(g[2])
+            g[1].replay()
+        else:
+            g.replay()
         return self.outputs[kind]
 
     def step(self, batch=None):
         """one training step -> (loss, losses [1, n], answer scores, pre-clip norm): device tensors, views of static
         buffers under a graph (consume them before the next step).  ``batch``: loaded first; another batch size than the
-        static one runs eagerly"""
-        return self._run("train", batch)
+        static one runs eagerly.  Under data parallelism a COLLECTIVE call (every rank steps, on a batch of its own), and
+        the replica guard, when there is one, counts the step"""
+        out = self._run("train", batch)
+        if self.split:
+            guard = getattr(self.model, "_replica_guard", None)
+            if guard is not None:
+                guard.tick()  # eager work between two replays, never part of a graph (the check is a collective)
+        return out
 
     def valid_step(self, batch=None):
         """the forward-only step -> (loss, losses, answer scores, None); it changes no parameter and no optimiser state"""
         return self._run("valid", batch)
 
-    def check(self):
-        """ONE synchronisation per read-back: the masked-LM overflow flag ``model.mlm_overflow`` (more labelled rows than
+    def _agree_on_overflow(self):
+        """data parallel: MAX of the ranks' overflow flags into ``_flags_host``, so that either every rank raises or none
+        does -- a rank that raised alone would leave the others hung in the next exchange.  The ranks first meet on the
+        host with a timeout (``dist._meet``): a lone caller gets a RuntimeError, not a hung group."""
+        import torch.distributed as dist
+        from .dist import _meet
+        gs = self.model._grad_sync
+        if not dist.is_initialized() or gs.world == 1:
+            return
+        _meet(gs, "pretrain_check", None,
+              "CapturedPretrainer.check: only %d of %d ranks reached %s (call %d) within %.0f s.  Under data parallelism "
+              "check() is a COLLECTIVE call: make it on every rank, not inside `if rank == 0:`")
+        t = self._flags_host.clone() if gs.backend != "nccl" else self._flags.clone()
+        dist.all_reduce(t, op=dist.ReduceOp.MAX, group=gs.group)
+        self._flags_host.copy_(t)
+
+    def check(self, collective=None):
+        """``collective`` (default: whether the model is data parallel): the ranks first agree on the flag (MAX), so that
+        either every rank raises or none does -- then a COLLECTIVE call; False: this rank's flag alone (the driver's
+        validation sweep, where the ranks take different numbers of steps, collects what it raises and agrees once, after
+        the sweep).
+        ONE synchronisation per read-back: the masked-LM overflow flag ``model.mlm_overflow`` (more labelled rows than
         ``mlm_capacity`` slots: the masked-LM loss of that step was NaN).  Nothing is raised while it is clear -- a NaN of
         another origin (a batch whose swap left no QA label has a NaN QA loss, as in the reference) is the log's business
         (``first_bad``), not an error here.  When it is set, the attached logs are read (the failing path alone pays that
@@ -989,6 +1119,8 @@ class CapturedPretrainer:
         self._flags[0:1].copy_(flag)
         self._flags_host.copy_(self._flags, non_blocking=True)
         torch.cuda.current_stream(self._flags.device).synchronize()
+        if self.split if collective is None else collective:
+            self._agree_on_overflow()
         if not int(self._flags_host[0]):
             return
         flag.zero_()
@@ -1003,5 +1135,7 @@ class CapturedPretrainer:
                 number = int(rec["cursor"]) - m + row
                 where.append("the first %s record with a NaN Mask_LM is number %d since the log's reset (step %d of this "
                              "window, optimiser step %d)" % (name, number, number + 1, int(rec["steps"][row])))
+        none = "no attached log of this rank retains the step (it overflowed on another rank)" if self.split \
+            else "no attached log retains the step"
         raise RuntimeError("masked-LM overflow: a batch had more labelled tokens than mlm_capacity=%r slots; %s"
-                           % (self.model.mlm_capacity, "; ".join(where) or "no attached log retains the step"))
+                           % (self.model.mlm_capacity, "; ".join(where) or none))

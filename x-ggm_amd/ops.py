@@ -1887,6 +1887,51 @@ def train_log_append(log, kind, cols, mul=None, step=None):
          int(kind), ptr(step), _ct.addressof(d), stream())
 
 
+def train_log_fold(log, vals, kinds, world, n, flag, steps=None, cursors=None, strides=None):
+    """the mean of the data-parallel ranks' copies of the ``n`` records of ``log`` (all of them since its reset: record i in
+    row i), folded into ``log``; ONE launch, contract: xggm_train_log_fold in xggm.h.  ``vals`` fp32, ``kinds`` int32 (the
+    packed kind words), ``steps`` / ``cursors`` int64 or None: DEVICE buffers that hold every rank's copy, rank r's at
+    ``r * strides[j]`` elements -- ``strides`` = (values, kinds, steps, cursors), default: dense [world, n, 8], [world, n],
+    [world, n], [world].  ``flag``: int64 [1] on the device; the launch leaves -1 there, or the first record the ranks
+    disagree on (n: a cursor is not n) -- the caller reads it with the log."""
+    world, n = int(world), int(n)
+    if world < 1:
+        raise ValueError("train_log_fold: world = %d" % world)
+    cap = int(log.capacity)
+    if not 1 <= n <= cap:
+        raise ValueError("train_log_fold: %d records, the log holds 1 .. %d" % (n, cap))
+    if strides is None:
+        strides = (n * TRAINLOG_COLS, n, n, 1)
+    sv, sk, ss, sc = (int(s) for s in strides)
+    _chk(vals, F32, "vals"), _chk(kinds, torch.int32, "kinds"), _chk(flag, torch.int64, "flag")
+    _c(log.values, F32, "log.values"), _c(log.kinds, torch.int32, "log.kinds"), _c(log.cursor, torch.int64, "log.cursor")
+    _c(log.sums, torch.float64, "log.sums"), _c(log.counts, torch.int64, "log.counts")
+    _c(log.first_bad_word, torch.int64, "log.first_bad_word")
+    if log.values.numel() < cap * TRAINLOG_COLS or log.kinds.numel() < cap or log.sums.numel() < TRAINLOG_KINDS * TRAINLOG_COLS \
+            or log.counts.numel() < TRAINLOG_KINDS or log.cursor.numel() < 1 or log.first_bad_word.numel() < 1:
+        raise ValueError("train_log_fold: the log's buffers are smaller than its capacity %d says" % cap)
+    if flag.numel() < 1:
+        raise ValueError("train_log_fold: flag holds no word")
+    # the last element any rank's copy is read at must lie inside its buffer
+    need = [("vals", vals, sv, n * TRAINLOG_COLS), ("kinds", kinds, sk, n)]
+    for name, t, s, dt in (("steps", steps, ss, n), ("cursors", cursors, sc, 1)):
+        if t is not None:
+            _chk(t, torch.int64, name)
+            need.append((name, t, s, dt))
+    for name, t, s, per in need:
+        if (world > 1 and s < per) or (world - 1) * s + per > t.numel():
+            raise ValueError("train_log_fold: %s holds %d elements, %d ranks at stride %d need %d"
+                             % (name, t.numel(), world, s, (world - 1) * s + per))
+    dev = log.cursor.device
+    for t in (vals, kinds, steps, cursors, flag, log.values, log.kinds, log.sums, log.counts, log.first_bad_word):
+        if t is not None and t.device != dev:
+            raise RuntimeError("train_log_fold: the log and the gathered buffers must live on one device")
+    d = TrainLogDesc(ptr(log.values), ptr(log.steps), ptr(log.kinds), ptr(log.cursor), ptr(log.sums), ptr(log.counts),
+                     ptr(log.first_bad_word), cap)
+    call("xggm_train_log_fold", ptr(vals), ptr(kinds), ptr(steps), ptr(cursors), sv, sk, ss, sc, world, n, _ct.addressof(d),
+         ptr(flag), stream())
+
+
 class _PassTail(_ct.Structure):
     _fields_ = [("steps", _ct.c_void_p), ("lr_scale", _ct.c_void_p), ("index", _ct.c_void_p), ("t_total", _ct.c_void_p),
                 ("warmup", _ct.c_void_p), ("n", _ct.c_int), ("rng", _ct.c_void_p), ("rng_by", _ct.c_uint64)]

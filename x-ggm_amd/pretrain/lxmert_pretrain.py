@@ -31,8 +31,12 @@ place of ``collate_examples`` and thirteen copies; ``LXMERT(resident=True)`` tak
 
 Out of scope here: the data-set readers and the evaluator of src/pretrain/lxmert_data.py (``LXMERTDataset``,
 ``LXMERTTorchDataset``, ``LXMERTEvaluator``: the data files are absent offline; any ``(dataset, loader, evaluator)`` whose
-loader yields lists of ``InputExample`` or is a ``ResidentPretrainSet`` serves), data-parallel pre-training, the packed
-loader ring of the fine-tuning side, and fusing the masking into the visual-embedding product's input read."""
+loader yields lists of ``InputExample`` or is a ``ResidentPretrainSet`` serves), the packed loader ring of the fine-tuning
+side, and fusing the masking into the visual-embedding product's input read.
+
+Data parallel (the reference's ``--multiGPU``, :255-256): ``enable_data_parallel`` prepares the model, the captured step
+exchanges the gradients between its two graphs (``engine.CapturedPretrainer``) and ``LXMERT`` shards a resident store over
+the ranks; the sharded update, the staged exchange and sharding a host loader are out of scope."""
 import os
 
 import numpy as np
@@ -147,6 +151,102 @@ class DeviceFeatures:
                 is_matched, out["ans"])
 
 
+# ----------------------------------------------------------------------------------------------- data parallelism
+
+
+def enable_data_parallel(model, group=None, wire_dtype=None, check_every=None, check_level="weights", overlap=False,
+                         zero1=False):
+    """one process per GPU for an ``LXRTPretraining`` (the reference's ``--multiGPU``, src/pretrain/lxmert_pretrain.py:255-256):
+    what ``vqa.vqacpv2.enable_data_parallel`` does for a ``VQAModel``.  Rank 0's parameters go to everyone; the rank is
+    folded into the Philox seed (same constant), so every rank draws its OWN masks, swaps, dropout and noise; a
+    ``dist.GradSync`` averages the flat gradient arena between the backward and the fused clip + update of every step
+    (``engine.CapturedPretrainer``: two graphs with the exchange between them) -- over ``rt.arena.grads``, or IN PLACE on the
+    bf16 wire arena when the storage is bf16 and ``wire_dtype=torch.bfloat16``; the clip norm is read after the exchange
+    (``arena.sq_enabled = False``, ``row_list_enabled = False``).  ``check_every`` / ``check_level``: a
+    ``dist.ReplicaGuard`` that ``CapturedPretrainer.step`` ticks.
+
+    The word table: the tied decoder of the masked-LM head gives EVERY row of the vocab x H table a gradient, so with
+    ``task_mask_lm`` the table is exchanged densely; only with the masked-LM task off are the rows of the step's tokens all
+    there is, and ``GradSync.set_sparse_table`` is used (wire arena only, as in fine-tuning).
+
+    Scope: the replicated update with a plain exchange.  ``zero1=True`` (the sharded update) and ``overlap=True`` (the
+    exchange staged under the backward) raise ``NotImplementedError`` before anything is touched; ``rt.cut_enabled`` is
+    False."""
+    if zero1:
+        raise NotImplementedError("pretrain.lxmert_pretrain.enable_data_parallel: the sharded update (zero1=True) is not "
+                                  "built for pre-training; the update is replicated")
+    if overlap:
+        raise NotImplementedError("pretrain.lxmert_pretrain.enable_data_parallel: the overlapped, staged exchange "
+                                  "(overlap=True) is not built for pre-training; the exchange runs between the two graphs")
+    import torch.distributed as dist
+    from ..dist import GradSync, broadcast_params
+    from ..runtime import runtime_of
+    rt = runtime_of(model)
+    broadcast_params(rt.arena, group)
+    rank = dist.get_rank(group) if dist.is_initialized() else 0
+    if rank:
+        # seed word of the device-resident {seed, offset} pair; saved / restored with the training state
+        rt.rng[0] = (int(rt.rng[0].item()) + rank * 0x9E3779B97F4A7C15) & 0x7FFFFFFFFFFFFFFF
+    inplace = wire_dtype == torch.bfloat16 and rt.arena.shadow is not None and os.environ.get("XGGM_DP_WIRE_ARENA", "1") != "0"
+    if inplace:
+        rt.arena.enable_wire()  # matrix gradients are born in the wire arena, reduced in place and read by the update
+    gs = GradSync(rt.arena.grads, group, wire_dtype, arena=rt.arena if inplace else None)
+    if inplace and not model.task_mask_lm and os.environ.get("XGGM_DP_SPARSE_EMB", "1") != "0":
+        wt = model.bert.embeddings.word_embeddings.weight
+        xg = getattr(wt, "_xg", None)
+        if xg is not None and xg[0] is rt.arena:
+            gs.set_sparse_table(xg[1], wt.shape[0], wt.shape[1], lambda: rt.emb_ids)
+    object.__setattr__(model, "_grad_sync", gs)
+    rt.arena.sq_enabled = False  # the clip norm is that of the AVERAGED gradients: read them after the exchange
+    rt.arena.row_list_enabled = False  # ... and the word table's gradient holds the OTHER ranks' rows too
+    rt.cut_enabled = False
+    if check_every is not None:
+        from ..dist import ReplicaGuard
+        object.__setattr__(model, "_replica_guard", ReplicaGuard(rt.arena, group, every=check_every, level=check_level))
+    return model
+
+
+def shard_range(n, rank, world):
+    """this rank's contiguous slice ``range(lo, hi)`` of ``n`` samples: the slices of ranks 0 .. world - 1 are disjoint, in
+    rank order, cover every sample exactly once and differ in length by at most one (the first ``n % world`` ranks hold one
+    more); a slice may be empty.  Pure: how the data-parallel validation sweep is divided."""
+    n, rank, world = int(n), int(rank), int(world)
+    if n < 0 or world < 1 or not 0 <= rank < world:
+        raise ValueError("shard_range: n=%d, rank %d of %d" % (n, rank, world))
+    q, r = divmod(n, world)
+    lo = rank * q + min(rank, r)
+    return range(lo, lo + q + (1 if rank < r else 0))
+
+
+def combine_sums(sums, steps, group=None):
+    """the data-parallel validation sweep's loss sums, combined once after the sweep: every rank hands in its fp64 host
+    sums ``sums`` (any number of values, the same number on every rank) and its step count; they are all-gathered and
+    added in RANK ORDER in fp64 -> (numpy fp64 array of the totals, total steps): the same bits on every rank.  The sums
+    are sums of per-step means, so total / steps is the mean of the per-step means the reference prints.  Without a
+    process group (or on one rank): the input."""
+    import torch.distributed as dist
+    mine = np.asarray(list(sums) + [float(steps)], dtype=np.float64)
+    if not dist.is_initialized() or dist.get_world_size(group) == 1:
+        return mine[:-1].copy(), int(steps)
+    world = dist.get_world_size(group)
+    t = torch.from_numpy(mine)
+    if dist.get_backend(group) == "nccl":
+        t = t.cuda()
+    parts = [torch.empty_like(t) for _ in range(world)]
+    dist.all_gather(parts, t, group=group)
+    return combine_sums_host([p.cpu().numpy()[:-1] for p in parts], [p.cpu().numpy()[-1] for p in parts])
+
+
+def combine_sums_host(per_rank_sums, per_rank_steps):
+    """``combine_sums`` restated without a process group: lists over the ranks -> (totals, steps), added in rank order"""
+    total = np.zeros(len(per_rank_sums[0]), dtype=np.float64)
+    steps = 0
+    for s, k in zip(per_rank_sums, per_rank_steps):
+        total = total + np.asarray(s, dtype=np.float64)
+        steps += int(k)
+    return total, steps
+
+
 # ----------------------------------------------------------------------------------------------- the driver loop
 
 
@@ -230,6 +330,16 @@ class LXMERT:
     ``train_batch(optim, (store, start[, rows]))`` / ``valid_batch((store, start[, rows]))`` take rows of the order the store
     currently holds.
 
+    Data parallel (``enable_data_parallel(model)`` before the driver is built, one process per GPU; the reference's
+    ``--multiGPU``, :255-256, with its ``loss.mean()`` over the replicas, :311-313): the loader must be a store.  ``train`` and
+    ``evaluate_epoch`` are then COLLECTIVE calls, made on every rank.  Training: every rank takes its ``B`` rows of each
+    global step of ``world x B`` (``store.order(..., rank=, world=)``), ``t_total`` counts global steps, and the printed losses
+    come from the logs FOLDED over the ranks (``TrainLog.fold``: the mean of the ranks' values per step).  Validation: rank r
+    walks the slice ``shard_range(n, r, world)`` of the sweep with no collective inside, so ranks may take different numbers
+    of steps (none included); after the sweep the fp64 sums are combined in rank order (``combine_sums``: weighted by steps,
+    the printed mean is that of the per-step means) and the ``uid2ans`` dicts merged in rank order.  Rank 0 alone prints,
+    calls the evaluator and writes snapshots (``save`` is a no-op elsewhere); every rank returns the same numbers.
+
     The printed per-term line names the terms that are on; the reference zips LOSSES_NAME with however many terms there
     are, which mislabels them as soon as a task is off (:366, :402) -- with all tasks on the lines are the same."""
 
@@ -266,14 +376,36 @@ class LXMERT:
         train = kind == "train"
         if store.batch_size is None:
             raise ValueError("LXMERT: a ResidentPretrainSet loader needs its batch_size")
+        dp = self._dp()
+        if dp is not None and train:
+            # global step s covers perm[s B world : (s + 1) B world], this rank takes its B of it: B is per rank
+            return store.order(epoch, shuffle=True, seed=int(getattr(self.args, "seed", 0) or 0), rank=dp[0], world=dp[1],
+                               drop_last=True, batch_size=store.batch_size)
         return store.order(epoch, shuffle=train, seed=int(getattr(self.args, "seed", 0) or 0), drop_last=train,
                            batch_size=store.batch_size)
 
+    def _dp(self):
+        """(rank, world, group) when the model was prepared by ``enable_data_parallel`` and the group has several ranks, else
+        None: everything below then runs as it always did"""
+        gs = getattr(self.model, "_grad_sync", None)
+        if gs is None or gs.world <= 1:
+            return None
+        import torch.distributed as dist
+        return dist.get_rank(gs.group), gs.world, gs.group
+
     def _n_batches(self, loader, kind):
+        """steps of one sweep: GLOBAL steps of a training epoch, THIS rank's steps of a validation sweep"""
+        dp = self._dp()
         if not self._is_store(loader):
+            if dp is not None:
+                raise ValueError("LXMERT: under data parallelism the loader must be a ResidentPretrainSet (its order is "
+                                 "sharded over the ranks); a host loader would have to be sharded by the caller")
             return len(loader)
         B = loader.batch_size
-        return len(loader) // B if kind == "train" else -(-len(loader) // B)
+        if kind == "train":
+            return len(loader) // (B * (dp[1] if dp is not None else 1))
+        n = len(loader) if dp is None else len(shard_range(len(loader), dp[0], dp[1]))
+        return -(-n // B)
 
     def _resident_batch(self, store, start, rows, like=None):
         """buffers of ``rows`` rows filled from the store, swap included: the first batch an engine is built on (``like`` None:
@@ -382,13 +514,23 @@ class LXMERT:
     # ------------------------------------------------------------------ epochs
     def _steps(self, loader, kind, epoch):
         """one sweep as (feed, rows, uids) per step; feed: the device batch of a list loader, or (store, start) of a store"""
+        dp = self._dp()
         if not self._is_store(loader):
+            if dp is not None:
+                raise ValueError("LXMERT: under data parallelism the loader must be a ResidentPretrainSet (its order is "
+                                 "sharded over the ranks); a host loader would have to be sharded by the caller")
             for batch in loader:
                 yield self._device_batch(batch), len(batch), [datum.uid for datum in batch]
             return
         order, B = self.resident_order(loader, kind, epoch), loader.batch_size
-        for start in range(0, len(order), B):
-            rows = min(B, len(order) - start)
+        lo, hi = 0, len(order)
+        if dp is not None and kind != "train":
+            # validation: a contiguous slice of the sweep per rank, its ragged tail eagerly; no collective in here, so the
+            # ranks may take different numbers of steps (none at all included)
+            mine = shard_range(len(order), dp[0], dp[1])
+            lo, hi = mine.start, mine.stop
+        for start in range(lo, hi, B):
+            rows = min(B, hi - start)
             yield (loader, start), rows, loader.uids(order[start:start + rows])
 
     def _sweep(self, loader, optim, kind, table, iters=-1, epoch=0):
@@ -399,12 +541,26 @@ class LXMERT:
         window = max(1, min(self.log_every or n_batches, n_batches))
         total, terms, steps, uids, uid2ans = 0.0, {}, 0, [], {}
         e = None
+        dp = self._dp()
+        self._deferred = None  # data-parallel validation: an overflow of THIS rank, raised on every rank after the sweep
 
         def read_back():
             nonlocal total, steps, uids
-            e.check()
             log = e.train_log if kind == "train" else e.valid_log
-            rec = log.read()
+            if dp is not None and kind == "train":
+                # every rank is here after the same number of steps: the overflow flag is agreed on (all raise or none),
+                # then the ranks' logs are folded into their mean -- one collective each per read-back, none per step
+                e.check()
+                rec = log.fold(pending, dp[2])
+            elif dp is not None:
+                try:
+                    e.check(collective=False)
+                except RuntimeError as err:
+                    self._deferred = self._deferred or err
+                rec = log.read()
+            else:
+                e.check()
+                rec = log.read()
             mean, named, n = T.pretrain_means(rec)
             total, steps = total + mean * n, steps + n
             for name, v in named:
@@ -447,6 +603,26 @@ class LXMERT:
             read_back()
         return total, terms, steps, uid2ans
 
+    def _merge_ranks(self, uid2ans):
+        """data parallel, once after a sweep (a COLLECTIVE call): the ranks' ``uid2ans`` merged in rank order with one
+        ``all_gather_object``; an overflow a rank met in its validation slice travels with it and is raised on EVERY rank"""
+        dp = self._dp()
+        err, self._deferred = getattr(self, "_deferred", None), None
+        if dp is None:
+            if err is not None:
+                raise err
+            return uid2ans
+        import torch.distributed as dist
+        parts = [None] * dp[1]
+        dist.all_gather_object(parts, (uid2ans, None if err is None else str(err)), group=dp[2])
+        merged = {}
+        for u, _ in parts:
+            merged.update(u)
+        for r, (_, msg) in enumerate(parts):
+            if msg is not None:
+                raise RuntimeError("rank %d: %s" % (r, msg))
+        return merged
+
     @staticmethod
     def _losses_line(terms, denom):
         s = "The losses are "
@@ -461,7 +637,9 @@ class LXMERT:
         from ..lxrt.optimization import BertAdam
         args = self.args
         dataset, train_ld, evaluator = _tuple(train_tuple)
-        batch_per_epoch = self._n_batches(train_ld, "train")
+        dp = self._dp()
+        print = _printer(dp)  # data parallel: rank 0 alone prints, evaluates and writes
+        batch_per_epoch = self._n_batches(train_ld, "train")  # data parallel: GLOBAL steps of world x B samples
         t_total = int(batch_per_epoch * args.epochs)
         warmup_ratio = 0.05
         warmup_iters = int(t_total * warmup_ratio)
@@ -473,9 +651,10 @@ class LXMERT:
         for epoch in range(args.epochs):
             self.model.train()
             total_loss, terms, _, uid2ans = self._sweep(train_ld, optim, "train", dataset.answer_table, epoch=epoch)
+            uid2ans = self._merge_ranks(uid2ans)
             print("The training loss for Epoch %d is %0.4f" % (epoch, total_loss / batch_per_epoch))
             print(self._losses_line(terms, batch_per_epoch))
-            if self.model.task_qa:
+            if self.model.task_qa and (dp is None or dp[0] == 0):
                 evaluator.evaluate(uid2ans, pprint=True)
             avg_eval_loss = self.evaluate_epoch(eval_tuple, iters=-1)
             if avg_eval_loss < best_eval_loss:
@@ -488,17 +667,34 @@ class LXMERT:
         dataset, eval_ld, evaluator = _tuple(eval_tuple)
         was_training = self.model.training
         self.model.eval()
-        total_loss, terms, _, uid2ans = self._sweep(eval_ld, None, "valid", dataset.answer_table, iters)
+        total_loss, terms, steps, uid2ans = self._sweep(eval_ld, None, "valid", dataset.answer_table, iters)
         self.model.train(was_training)
         n_eval = self._n_batches(eval_ld, "valid")
+        dp = self._dp()
+        print = _printer(dp)  # data parallel: rank 0 alone prints and evaluates
+        if dp is not None:
+            # the ranks' sums of per-step means, combined once: fp64, rank order, weighted by steps -- the printed mean is
+            # that of the per-step means of the whole sweep, the same bits on every rank
+            uid2ans = self._merge_ranks(uid2ans)
+            named = list(LOSSES_NAME)
+            sums = [total_loss] + [terms.get(n, 0.0) for n in named] + [float(n in terms) for n in named]
+            tot, n_eval = combine_sums(sums, steps, dp[2])
+            if n_eval == 0:
+                raise ValueError("LXMERT.evaluate_epoch: no rank took a validation step")
+            total_loss = float(tot[0])
+            terms = {n: float(tot[1 + i]) for i, n in enumerate(named) if tot[1 + len(named) + i] > 0}
         print("The valid loss is %0.4f" % (total_loss / n_eval))
         print(self._losses_line(terms, n_eval))
-        if self.model.task_qa:
+        if self.model.task_qa and (dp is None or dp[0] == 0):
             evaluator.evaluate(uid2ans, pprint=True)
         return total_loss / n_eval
 
     # ------------------------------------------------------------------ snapshots, the reference's file names
     def save(self, name):
+        """data parallel: rank 0 writes (the replicas are equal), on the other ranks a no-op"""
+        dp = self._dp()
+        if dp is not None and dp[0] != 0:
+            return
         os.makedirs(self.args.output, exist_ok=True)
         torch.save(self.model.state_dict(), os.path.join(self.args.output, "%s_LXRT.pth" % name))
 
@@ -523,6 +719,12 @@ class LXMERT:
             print(key)
         print()
         self.model.load_state_dict(sd, strict=False)
+
+
+def _printer(dp):
+    """``print`` on rank 0 (and without data parallelism), a no-op on the other ranks"""
+    import builtins
+    return builtins.print if dp is None or dp[0] == 0 else (lambda *a, **k: None)
 
 
 def _tuple(t):

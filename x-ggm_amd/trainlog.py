@@ -77,3 +77,44 @@ def pretrain_means(rec):
     sums = rec["sums"][PRETRAIN]
     terms = [(name, float(sums[c]) / n) for name, c in zip(LOSSES_NAME, range(PT_MASK_LM, PT_QA + 1)) if bool(present[c])]
     return float(sums[LOSS]) / n, terms, n
+
+
+def fold_host(values, kinds, present, steps=None, cursors=None, cursor=None):
+    """xggm_train_log_fold restated in numpy: the data-parallel ranks' copies of the n records of a log -> what the launch
+    leaves in a rank's ring.  ``values`` [world, n, COLS] fp32, ``kinds`` [world, n] (the kind alone), ``present`` [world, n,
+    COLS] bool, ``steps`` [world, n] int64 or None, ``cursors`` [world] or None, ``cursor``: this rank's (default n).
+    -> dict of numpy arrays / numbers: values [n, COLS] fp32 -- per record and column the sum in rank order times the fp32
+    1 / world; an absent column 0; ``world == 1``: unchanged --, kinds [n] (rank 0's), present [n, COLS] (on EVERY rank),
+    sums [KINDS, COLS] fp64 and counts [KINDS] over the folded records in record order, first_bad, and ``flag``: -1, the
+    first record whose kind, present columns or step differ between ranks, or n when only a cursor is not n.  The
+    CPU-testable reference of the kernel (tested against it bit for bit); no fallback."""
+    import numpy as np
+    values = np.asarray(values, dtype=np.float32)
+    kinds, present = np.asarray(kinds).astype(np.int64), np.asarray(present).astype(bool)
+    world, n = kinds.shape
+    if world < 1 or n < 1 or values.shape != (world, n, COLS) or present.shape != (world, n, COLS):
+        raise ValueError("fold_host: values %s, kinds %s, present %s" % (values.shape, kinds.shape, present.shape))
+    both = present.all(axis=0)
+    with np.errstate(invalid="ignore", over="ignore"):
+        acc = values[0].copy()
+        for r in range(1, world):
+            acc = acc + values[r]  # rank order, fp32
+        out = acc if world == 1 else np.where(both, acc * (np.float32(1.0) / np.float32(world)), np.float32(0.0))
+    out = out.astype(np.float32)
+    differ = (kinds != kinds[0]).any(axis=0) | (present != present[0]).any(axis=(0, 2))
+    if steps is not None:
+        steps = np.asarray(steps).astype(np.int64)
+        differ |= (steps != steps[0]).any(axis=0)
+    flag = int(np.argmax(differ)) if differ.any() else -1
+    if flag < 0 and cursors is not None and any(int(c) != n for c in np.asarray(cursors).reshape(-1)):
+        flag = n
+    sums, counts = np.zeros((KINDS, COLS), dtype=np.float64), np.zeros(KINDS, dtype=np.int64)
+    for i in range(n):  # record order, fp64: what the appends would have accumulated
+        k = int(kinds[0, i])
+        counts[k] += 1
+        for c in range(COLS):
+            if both[i, c]:
+                sums[k, c] = sums[k, c] + np.float64(out[i, c])
+    bad = (~np.isfinite(out) & both).any(axis=1)
+    first_bad = (n if cursor is None else int(cursor)) - n + int(np.argmax(bad)) if bad.any() else -1
+    return dict(values=out, kinds=kinds[0].copy(), present=both, sums=sums, counts=counts, first_bad=first_bad, flag=flag)
