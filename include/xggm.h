@@ -1356,6 +1356,40 @@ typedef struct xggm_answer_log {
 int xggm_answer_pick_f32(const float* logits, int64_t row_stride, const float* target, int64_t target_stride, int B, int A,
                          const int* rows, xggm_answer_log* log, float* ws, xggm_stream_t stream);
 
+/* xggm_answer_log_fold: the data-parallel ranks' answer logs merged into ONE log in sweep order.  The reference's
+ * --multiGPU runs hand every replica a slice of the batch and collect the answers on the host: `logit.max(1)[1].cpu()` in
+ * the training loop (src/vqa/vqacpv2.py:180-181, the train score of :285) and in the validation sweep (:333-334), over
+ * the replicas of nn.DataParallel (src/lxrt/entry.py:183-184).  Here every rank appends to a log of its own; after a sweep
+ * or an epoch the packed logs are all-gathered -- one collective per sweep, never per step -- and ONE launch merges them.
+ *
+ * logs: DEVICE int64; rank r's packed log starts at logs + r * log_stride (int64 words) and is laid out as
+ *     [cursor, score_sum (fp64 bits), flags, labels[src_capacity], scores (fp32, two per word; with_scores only)]
+ * with the same src_capacity on every rank.  expect: HOST array of `world` counts (copied into the kernel arguments): how
+ * many answers rank r must hold; total = sum(expect).  Position p in [0, expect[r]) of rank r goes to destination d:
+ *     XGGM_FOLD_CONCAT      d = expect[0] + .. + expect[r-1] + p               (a validation sweep cut into contiguous
+ *                                                                              slices; counts may differ, 0 is allowed)
+ *     XGGM_FOLD_INTERLEAVE  d = ((p / block) * world + r) * block + p % block  (a training epoch whose global step holds
+ *                           `world` blocks of `block` samples, rank r's the r-th; every expect[r] equal, a multiple of block)
+ * Written: dst->labels[d]; dst->scores[d] (with_scores); *dst->cursor = total; *dst->score_sum = ((+0.0 + s_0) + s_1) + ..
+ * over the ranks' fp64 sums in rank order (when dst->score_sum is given); *dst->flags = 0; and *flag: 0 when every rank's
+ * cursor equals its expect[r] and every rank's flags word (all 64 bits) is 0, else
+ *     bit 0: a cursor differs;  bit 1: a rank carries refused appends;  bits 8..: the lowest offending rank.
+ * The copy is carried out either way.  Every address is decided by HOST values: the kernel copies expect[r] positions
+ * whatever the device cursors say, and no store leaves labels[0, total), scores[0, total), the three header words and
+ * *flag under any device contents.  No atomics: the header words are written by one lane; labels move as 8-byte and scores
+ * as 4-byte elements (with an odd capacity in front of it a scores region is only 4-byte aligned).  The gathered logs are
+ * only read.  One launch, no allocation, no host synchronisation: legal inside a stream capture.
+ * Refused before any launch: a null logs / expect / dst / flag / dst->labels / cursor / flags; world outside [1,
+ * XGGM_FOLD_MAX_RANKS]; expect[r] < 0 or > src_capacity; total < 1 or > dst->capacity; an unknown layout; INTERLEAVE with
+ * unequal counts, block < 1 or a count that is no multiple of block; with_scores without dst->scores; log_stride shorter
+ * than one packed log; dst buffers or the flag overlapping the gathered logs; logs, labels, cursor, score_sum, flag not
+ * 8-byte or scores, flags not 4-byte aligned. */
+#define XGGM_FOLD_MAX_RANKS 64
+#define XGGM_FOLD_CONCAT 0
+#define XGGM_FOLD_INTERLEAVE 1
+int xggm_answer_log_fold(const int64_t* logs, int64_t log_stride, int64_t src_capacity, int with_scores, int world, int layout,
+                         int64_t block, const int64_t* expect, xggm_answer_log* dst, int64_t* flag, xggm_stream_t stream);
+
 /* ---- sweep score --------------------------------------------------------------------------
  * The reference scores a sweep on the host: `evaluator.evaluate(quesid2ans)` walks a {question_id: answer string} dict
  * through id2datum / ans2label (src/vqa/vqacpv2_data.py:134-142, src/gqa/gqa_ood_data.py:160-167), four times per epoch

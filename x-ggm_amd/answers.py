@@ -30,6 +30,83 @@ def decode_packed(words, capacity, with_scores=True):
     return labels, scores, score_sum, n
 
 
+FOLD_MAX_RANKS = 64               # XGGM_FOLD_MAX_RANKS (include/xggm.h)
+FOLD_CONCAT, FOLD_INTERLEAVE = 0, 1   # XGGM_FOLD_CONCAT, XGGM_FOLD_INTERLEAVE
+FOLD_FLAG_CURSOR = 1              # bit 0 of a fold's flag: a rank's cursor is not its expected count
+FOLD_FLAG_REFUSED = 2             # bit 1: a rank's log carries refused appends; bits 8..: the lowest offending rank
+
+
+def packed_words(capacity, with_scores=True):
+    """int64 words of a packed answer log: [cursor, score_sum, flags, labels[capacity], scores fp32 two per word]"""
+    capacity = int(capacity)
+    return 3 + capacity + ((capacity + 1) // 2 if with_scores else 0)
+
+
+def fold_destinations(layout, expect, block=None):
+    """where xggm_answer_log_fold puts the answers: a list over the ranks of int64 arrays, entry p of rank r's = the
+    destination index of its position p.  ``FOLD_CONCAT``: rank r's ``expect[r]`` answers behind those of the ranks below it
+    (a sweep cut into contiguous slices, ``dist.shard_range``); ``FOLD_INTERLEAVE``: global step s holds ``world`` blocks of
+    ``block`` answers, rank r's the r-th -- the inverse of ``perm.reshape(steps, world, B)[:, rank]`` (``ResidentDataset.order``).
+    ValueError for what the entry refuses."""
+    import numpy as np
+    expect = [int(e) for e in expect]
+    world = len(expect)
+    if not 1 <= world <= FOLD_MAX_RANKS or any(e < 0 for e in expect) or sum(expect) < 1:
+        raise ValueError("fold: expect = %s (1 .. %d ranks, counts >= 0, at least one answer)" % (expect, FOLD_MAX_RANKS))
+    if layout == FOLD_CONCAT:
+        first = np.concatenate([[0], np.cumsum(expect)[:-1]]).astype(np.int64)
+        return [first[r] + np.arange(expect[r], dtype=np.int64) for r in range(world)]
+    if layout != FOLD_INTERLEAVE:
+        raise ValueError("fold: unknown layout %r" % (layout,))
+    if block is None or int(block) < 1 or any(e != expect[0] or e % int(block) for e in expect):
+        raise ValueError("fold: interleave needs equal counts that are multiples of the block (expect = %s, block = %s)" % (expect, block))
+    block = int(block)
+    p = np.arange(expect[0], dtype=np.int64)
+    return [((p // block) * world + r) * block + p % block for r in range(world)]
+
+
+def fold_logs_host(bufs, capacity, with_scores, layout, block, expect):
+    """xggm_answer_log_fold restated in numpy: ``bufs`` = [world, >= packed_words] int64 (the gathered packed logs, one row
+    per rank, ``capacity`` entries each) -> dict: ``labels`` [total] int64, ``scores`` [total] fp32 or None, ``cursor`` = total,
+    ``score_sum`` (the ranks' fp64 sums added in rank order to +0.0), ``flags`` = 0, ``flag`` (0, or FOLD_FLAG_* with the lowest
+    offending rank from bit 8 on) and ``dest`` (``fold_destinations``).  As the kernel does, it copies ``expect[r]`` positions
+    whatever the cursors say.  The CPU-testable reference of the kernel (tested against it bit for bit); no fallback."""
+    import numpy as np
+    bufs = np.asarray(bufs, dtype=np.int64)
+    capacity = int(capacity)
+    dest = fold_destinations(layout, expect, block)
+    world, total = len(dest), sum(len(d) for d in dest)
+    if bufs.ndim != 2 or bufs.shape[0] != world or bufs.shape[1] < packed_words(capacity, with_scores):
+        raise ValueError("fold_logs_host: bufs %s for %d ranks of capacity %d" % (bufs.shape, world, capacity))
+    if any(len(d) > capacity for d in dest):
+        raise ValueError("fold_logs_host: expect = %s exceeds the capacity %d" % ([len(d) for d in dest], capacity))
+    labels = np.zeros(total, dtype=np.int64)
+    scores = np.zeros(total, dtype=np.float32) if with_scores else None
+    score_sum, bits, bad = np.float64(0.0), 0, -1
+    for r in range(world):
+        row = np.ascontiguousarray(bufs[r])
+        n = len(dest[r])
+        labels[dest[r]] = row[3:3 + n]
+        if with_scores:
+            scores[dest[r]] = row[3 + capacity:3 + capacity + (capacity + 1) // 2].view(np.float32)[:n]
+        with np.errstate(invalid="ignore", over="ignore"):
+            score_sum = score_sum + row[1:2].view(np.float64)[0]
+        off = (FOLD_FLAG_CURSOR if int(row[0]) != n else 0) | (FOLD_FLAG_REFUSED if int(row[2]) != 0 else 0)
+        bits |= off
+        if off and bad < 0:
+            bad = r
+    return dict(labels=labels, scores=scores, cursor=total, score_sum=float(score_sum), flags=0,
+                flag=(bits | (bad << 8)) if bits else 0, dest=dest)
+
+
+def fold_flag_message(flag):
+    """what a non-zero flag of a fold says"""
+    flag = int(flag)
+    what = [s for bit, s in ((FOLD_FLAG_CURSOR, "a rank has not logged the answers expected of it"),
+                             (FOLD_FLAG_REFUSED, "a rank's log refused appends (overflow)")) if flag & bit]
+    return "answer log fold: %s; the lowest such rank is %d -- the merged sweep is incomplete" % (" and ".join(what), flag >> 8)
+
+
 SCORE_CHUNK = 1024       # XGGM_SCORE_CHUNK (include/xggm.h)
 SCORE_MAX_GROUPS = 16    # XGGM_SCORE_MAX_GROUPS
 SCORE_FLAG_CURSOR = 1    # bit 0 of a score's flag word: the log's cursor was not the n the launch was given

@@ -669,6 +669,45 @@ def sync_branch(branch_is_rel, device, group=None):
     return bool(t.item())
 
 
+def rank0_printer(dp):
+    """``print`` on rank 0 (and without data parallelism: ``dp`` None), a no-op on the other ranks; ``dp`` = (rank, ...)"""
+    import builtins
+    return builtins.print if dp is None or dp[0] == 0 else (lambda *a, **k: None)
+
+
+def sync_branches(draws, device, group=None, delta=5):
+    """the branch decisions of a whole epoch at once: rank 0 draws ``draws`` values ``random.randint(1, 10) <= delta`` up
+    front -- the same sequence as ``pick_branch``'s one draw per iteration -- and ONE broadcast hands them to every rank,
+    instead of ``sync_branch``'s broadcast and read-back per iteration.  -> list of ``draws`` bools (True: relation
+    generation).  The other ranks draw nothing: their generators stay where they were.  Without a process group (or in a
+    one-rank group): this process's own draws."""
+    import random
+    draws = int(draws)
+    alone = not dist.is_initialized() or dist.get_world_size(group) == 1
+    if alone or dist.get_rank(group) == 0:
+        t = torch.tensor([1 if random.randint(1, 10) <= delta else 0 for _ in range(draws)], dtype=torch.int32)
+    else:
+        t = torch.zeros(draws, dtype=torch.int32)
+    if alone:
+        return [bool(v) for v in t.tolist()]
+    t = t.to(device)
+    src = dist.get_global_rank(group, 0) if group is not None else 0
+    dist.broadcast(t, src=src, group=group)
+    return [bool(v) for v in t.tolist()]
+
+
+def shard_range(n, rank, world):
+    """this rank's contiguous slice ``range(lo, hi)`` of ``n`` samples: the slices of ranks 0 .. world - 1 are disjoint, in
+    rank order, cover every sample exactly once and differ in length by at most one (the first ``n % world`` ranks hold one
+    more); a slice may be empty.  Pure: how a data-parallel validation sweep is divided."""
+    n, rank, world = int(n), int(rank), int(world)
+    if n < 0 or world < 1 or not 0 <= rank < world:
+        raise ValueError("shard_range: n=%d, rank %d of %d" % (n, rank, world))
+    q, r = divmod(n, world)
+    lo = rank * q + min(rank, r)
+    return range(lo, lo + q + (1 if rank < r else 0))
+
+
 def shard_batch(batch, rank, world):
     """equal contiguous shards of every per-sample tensor of a global batch."""
     out = {}

@@ -120,6 +120,51 @@ class AnswerLog:
         torch.cuda.current_stream(self.buf.device).synchronize()
         return decode_packed(self.host, self.capacity, self.with_scores)
 
+    def fold(self, layout, expect, block=None, group=None):
+        """COLLECTIVE merge under data parallelism (every rank of ``group`` calls it with the same arguments): the ranks'
+        packed logs -- the same capacity on every rank -- are all-gathered, ONE collective per sweep or epoch and never per
+        step, and one launch (``ops.answer_log_fold``) merges them in sweep order into a log of capacity >= ``sum(expect)``
+        that is made once and reused.  ``expect[r]``: the answers rank r must hold; ``layout``: ``ops.FOLD_CONCAT`` (a sweep cut
+        into contiguous slices, counts may differ or be 0) or ``ops.FOLD_INTERLEAVE`` (a training epoch: global step s holds
+        the ranks' ``block`` answers in rank order).  -> the merged ``AnswerLog`` with ``count = sum(expect)``: ``read`` and
+        ``score_store`` work on it as on any log, and give the same bits on every rank.  RuntimeError on every rank (the
+        flag is computed from the same gathered words) when a rank's cursor is not its ``expect[r]`` or its log refused an
+        append.  A one-rank group: ``self``, without a launch."""
+        import torch.distributed as dist
+        from .answers import fold_flag_message
+        world = dist.get_world_size(group) if dist.is_initialized() else 1
+        if world == 1:
+            return self
+        expect = [int(e) for e in expect]
+        total = sum(expect)
+        if len(expect) != world or total < 1 or any(not 0 <= e <= self.capacity for e in expect):
+            raise ValueError("AnswerLog.fold: expect = %s for %d ranks of capacity %d" % (expect, world, self.capacity))
+        dev, W = self.buf.device, self.buf.numel()
+        if getattr(self, "_gathered", None) is None or self._gathered.shape[0] != world:
+            self._gathered = torch.zeros((world, W), dtype=torch.int64, device=dev)
+            self._flag = torch.zeros(1, dtype=torch.int64, device=dev)
+            self._flag_host = torch.zeros(1, dtype=torch.int64).pin_memory()
+        if getattr(self, "_merged", None) is None or self._merged.capacity < total:
+            self._merged = AnswerLog(total, dev, with_scores=self.with_scores)  # a sweep's total does not change
+        if dist.get_backend(group) == "nccl":
+            dist.all_gather_into_tensor(self._gathered, self.buf, group=group)
+        else:  # gloo, the test transport: through the host
+            self.host.copy_(self.buf, non_blocking=True)
+            torch.cuda.current_stream(dev).synchronize()
+            parts = [torch.empty(W, dtype=torch.int64) for _ in range(world)]
+            dist.all_gather(parts, self.host.clone(), group=group)
+            self._gathered.copy_(torch.stack(parts))
+        out = self._merged
+        ops.answer_log_fold(self._gathered, out, self._flag, self.capacity, self.with_scores, layout, expect,
+                            block=1 if block is None else block)
+        out.count = total
+        self._flag_host.copy_(self._flag, non_blocking=True)
+        torch.cuda.current_stream(dev).synchronize()
+        flag = int(self._flag_host[0])
+        if flag:
+            raise RuntimeError(fold_flag_message(flag) + " (expected per rank: %s)" % expect)
+        return out
+
     def score(self):
         """mean soft score of the logged samples (the reference's per-epoch train score, src/vqa/vqacpv2.py:285, as a
         fraction; the evaluator's sum, src/vqa/vqacpv2_data.py:134-142, over the count)"""

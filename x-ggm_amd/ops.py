@@ -1770,6 +1770,52 @@ def answer_pick(logits, log, target=None, rows=None):
          ptr(sum_ws(logits.device)), stream())
 
 
+FOLD_MAX_RANKS = 64                   # XGGM_FOLD_MAX_RANKS (include/xggm.h)
+FOLD_CONCAT, FOLD_INTERLEAVE = 0, 1   # XGGM_FOLD_CONCAT, XGGM_FOLD_INTERLEAVE
+
+
+def answer_log_fold(logs, dst, flag, src_capacity, with_scores, layout, expect, block=1, log_stride=None):
+    """merge the data-parallel ranks' packed answer logs into ``dst`` in sweep order; ONE launch, contract:
+    xggm_answer_log_fold in xggm.h.  ``logs``: int64 DEVICE tensor [world, log_stride] (or flat) holding every rank's
+    ``AnswerLog.buf`` of ``src_capacity`` entries; ``dst``: anything with the device tensors of an ``engine.AnswerLog``;
+    ``flag``: int64 [1] on the device -- 0 afterwards, or the bits of ``answers.FOLD_FLAG_*``; ``expect``: host ints, the
+    answers every rank must hold; ``layout``: ``FOLD_CONCAT`` or ``FOLD_INTERLEAVE`` (with ``block``)."""
+    from .answers import packed_words
+    expect = [int(e) for e in expect]
+    world = len(expect)
+    if not 1 <= world <= FOLD_MAX_RANKS:
+        raise ValueError("answer_log_fold: %d ranks (1 .. %d)" % (world, FOLD_MAX_RANKS))
+    _c(logs, torch.int64, "logs"), _c(flag, torch.int64, "flag")
+    src_capacity = int(src_capacity)
+    words = packed_words(src_capacity, with_scores)
+    if log_stride is None:
+        log_stride = logs.shape[-1] if logs.dim() == 2 else words
+    log_stride = int(log_stride)
+    # the last word any rank's log is read at must lie inside the gathered buffer
+    if src_capacity < 1 or log_stride < words or (world - 1) * log_stride + words > logs.numel():
+        raise ValueError("answer_log_fold: logs holds %d words, %d ranks of capacity %d at stride %d need %d"
+                         % (logs.numel(), world, src_capacity, log_stride, (world - 1) * max(log_stride, words) + words))
+    cap = int(dst.capacity)
+    _c(dst.labels, torch.int64, "dst.labels"), _c(dst.cursor, torch.int64, "dst.cursor"), _c(dst.flags, torch.int32, "dst.flags")
+    if dst.labels.numel() < cap or dst.cursor.numel() < 1 or dst.flags.numel() < 1 or flag.numel() < 1:
+        raise ValueError("answer_log_fold: the destination's buffers are smaller than its capacity %d says" % cap)
+    if dst.scores is not None:
+        _c(dst.scores, F32, "dst.scores")
+        if dst.scores.numel() < cap:
+            raise ValueError("answer_log_fold: dst.scores holds %d entries, the capacity is %d" % (dst.scores.numel(), cap))
+    if dst.score_sum is not None:
+        _c(dst.score_sum, torch.float64, "dst.score_sum")
+    if with_scores and dst.scores is None:
+        raise ValueError("answer_log_fold: with_scores needs a destination with scores")
+    for t in (flag, dst.labels, dst.scores, dst.cursor, dst.score_sum, dst.flags):
+        if t is not None and t.device != logs.device:
+            raise RuntimeError("answer_log_fold: the gathered logs, the destination and the flag must live on one device")
+    d = AnswerLogDesc(ptr(dst.labels), ptr(dst.scores), ptr(dst.cursor), ptr(dst.score_sum), ptr(dst.flags), cap)
+    exp = (_ct.c_int64 * world)(*expect)
+    call("xggm_answer_log_fold", ptr(logs), log_stride, src_capacity, 1 if with_scores else 0, world, int(layout), int(block),
+         _ct.cast(exp, _ct.c_void_p), _ct.addressof(d), ptr(flag), stream())
+
+
 SCORE_MAX_GROUPS = 16  # XGGM_SCORE_MAX_GROUPS (include/xggm.h)
 
 

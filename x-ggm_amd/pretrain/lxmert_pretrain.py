@@ -43,6 +43,7 @@ import numpy as np
 import torch
 
 from .. import ops
+from ..dist import rank0_printer as _printer, shard_range  # noqa: F401  (shared with the fine-tuning drivers)
 from ..trainlog import LOSSES_NAME  # src/pretrain/lxmert_pretrain.py:218
 
 SID_BASE = 0x70726500  # far from the module streams (16 * (i + 1) + k) and the graph streams
@@ -204,18 +205,6 @@ def enable_data_parallel(model, group=None, wire_dtype=None, check_every=None, c
         from ..dist import ReplicaGuard
         object.__setattr__(model, "_replica_guard", ReplicaGuard(rt.arena, group, every=check_every, level=check_level))
     return model
-
-
-def shard_range(n, rank, world):
-    """this rank's contiguous slice ``range(lo, hi)`` of ``n`` samples: the slices of ranks 0 .. world - 1 are disjoint, in
-    rank order, cover every sample exactly once and differ in length by at most one (the first ``n % world`` ranks hold one
-    more); a slice may be empty.  Pure: how the data-parallel validation sweep is divided."""
-    n, rank, world = int(n), int(rank), int(world)
-    if n < 0 or world < 1 or not 0 <= rank < world:
-        raise ValueError("shard_range: n=%d, rank %d of %d" % (n, rank, world))
-    q, r = divmod(n, world)
-    lo = rank * q + min(rank, r)
-    return range(lo, lo + q + (1 if rank < r else 0))
 
 
 def combine_sums(sums, steps, group=None):
@@ -719,12 +708,6 @@ class LXMERT:
             print(key)
         print()
         self.model.load_state_dict(sd, strict=False)
-
-
-def _printer(dp):
-    """``print`` on rank 0 (and without data parallelism), a no-op on the other ranks"""
-    import builtins
-    return builtins.print if dp is None or dp[0] == 0 else (lambda *a, **k: None)
 
 
 def _tuple(t):

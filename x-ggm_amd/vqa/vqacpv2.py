@@ -534,6 +534,14 @@ def val_schedule(n_batches):
     return np.linspace(0, n_batches, 5, dtype=int)[1:-1]
 
 
+def global_steps(n, batch_size, world=1):
+    """iterations of a training epoch over ``n`` samples at ``batch_size`` rows PER RANK: whole global steps of ``world x
+    batch_size`` samples (a ragged global step cannot be split into equal ranks and is dropped).  Under data parallelism
+    ``t_total`` (times the epochs) and ``val_schedule`` count these, so a run on ``world`` ranks validates and decays its
+    learning rate where a single-process run at ``world x batch_size`` would."""
+    return int(n) // (int(batch_size) * int(world))
+
+
 def _tuple(t):
     """(dataset, loader, evaluator) of a DataTuple-like object or a plain 3-tuple"""
     if hasattr(t, "dataset"):
@@ -556,7 +564,8 @@ class FineTuner:
     the reference's sequence of scalars.
 
     ``model``: a ``VQAModel`` / ``GQAModel`` on the GPU, snapshots loaded (the reference builds it inside the class; here
-    the caller does, as for ``pretrain.lxmert_pretrain.LXMERT``); a model prepared with ``enable_data_parallel`` is refused.
+    the caller does, as for ``pretrain.lxmert_pretrain.LXMERT``); a model prepared with ``enable_data_parallel`` is refused
+    unless ``data_parallel=True`` is given (below).
     ``train_tuple`` / ``valid_tuple``: ``(dataset, loader, evaluator)``.  A loader is a ``tools.resident.ResidentDataset``
     -- the device path: per-epoch order from ``store.order(epoch, shuffle=True, seed=args.seed, drop_last=True)``, batches
     gathered in HBM, scores computed against the store's own tables with the keep mask that gives a ``quesid2ans`` dict's
@@ -567,31 +576,48 @@ class FineTuner:
     ``writer``: anything with ``add_scalar(tag, value, step)`` (the reference's ``--tf_writer``); None: nothing is written.
 
     The training engine is captured on the first batch of the first epoch; ``CapturedTrainer`` warms up with eager passes
-    on that batch (optimiser steps at the head of the warm-up schedule), as it does for every caller."""
+    on that batch (optimiser steps at the head of the warm-up schedule), as it does for every caller.
+
+    ``data_parallel=True`` (the reference's ``--multiGPU``, src/vqa/vqacpv2.py:106-107) with a model prepared by
+    ``enable_data_parallel`` in a group of several ranks: ``train``, ``evaluate`` and ``predict`` are then COLLECTIVE calls, made
+    on every rank, and both loaders must be resident stores (a host loader is a ValueError).  ``args.batch_size`` is per rank;
+    an epoch has ``n // (B * world)`` GLOBAL steps, which ``t_total`` and ``val_schedule`` count; rank r takes its ``B`` rows of
+    every global step (``store.order(..., rank=, world=)``); rank 0's branch draws for the epoch travel in one broadcast
+    (``dist.sync_branches``); the losses are read through ``TrainLog.fold`` (the mean over the ranks); the epoch's answers are
+    merged with ``AnswerLog.fold`` (interleaved back into the global order) and scored on every rank.  A validation sweep
+    gives rank r the slice ``dist.shard_range(n, r, world)`` of the data set order, with no collective inside, and merges the
+    logs in rank order before ONE ``score_store`` with the global keep mask.  Every rank keeps the same ``history``,
+    ``valid_scores`` and best score; rank 0 alone prints, writes ``log.log`` and ``dump``, calls the ``writer`` and saves.
+    Without the keyword, with a model that was not prepared, or in a one-rank group nothing changes."""
 
     order = "vqa"        # pass order and KL weight of ``CapturedTrainer``
     valid_factor = 1     # validation batch size over the training one (src/gqa/gqa_ood.py:82: 2)
     extra_tags = ()      # writer tags beyond the common ones, written with the value the reference leaves in them
 
     def __init__(self, model, train_tuple, valid_tuple=None, args=None, use_graph=True, valid_batch_size=None, log_every=None,
-                 writer=None):
+                 writer=None, data_parallel=False):
         import os
         from .. import param
-        if getattr(model, "_grad_sync", None) is not None:
+        from ..dist import rank0_printer
+        if getattr(model, "_grad_sync", None) is not None and not data_parallel:
             raise NotImplementedError("%s: a model prepared with enable_data_parallel is not supported by this driver (every "
                                       "rank would need its own epoch order and the ranks' scores would need combining); "
                                       "drive CapturedTrainer directly" % type(self).__name__)
         self.model, self.args = model, (param.args if args is None else args)
+        self.data_parallel = bool(data_parallel)
         self.train_tuple, self.valid_tuple = train_tuple, valid_tuple
         self.use_graph, self.log_every, self.writer = use_graph, log_every, writer
+        dp = self._dp()
+        if dp is not None and dp[0] != 0:
+            self.writer = None  # rank 0 alone calls the writer
         self.device = next(model.parameters()).device
-        self.B = int(self.args.batch_size)
+        self.B = int(self.args.batch_size)  # data parallel: per rank
         self.valid_B = int(valid_batch_size) if valid_batch_size else self.valid_factor * self.B
         self.bce_loss = BCEWithLogitsLoss()
-        batch_per_epoch = self._n_batches(_tuple(train_tuple)[1])
+        batch_per_epoch = self._n_batches(_tuple(train_tuple)[1])  # data parallel: GLOBAL steps of world x B samples
         t_total = int(batch_per_epoch * self.args.epochs)
         if 'bert' in self.args.optim:
-            print(self._total_iters_line(t_total))
+            rank0_printer(dp)(self._total_iters_line(t_total))
         self.optim = make_optimizer(model, self.args.lr, 2 * t_total, optim=self.args.optim)
         self.output = self.args.output
         os.makedirs(self.output, exist_ok=True)
@@ -600,6 +626,7 @@ class FineTuner:
         self.total_loss = 0.0    # the reference's running ``total_loss`` (never reset between epochs)
         self.history = []        # per epoch of ``train``: the unrounded numbers behind the lines of log.log
         self.valid_scores = []   # every validation score of ``train``, in the order the sweeps ran
+        self.best_valid = 0.     # the best of them in the last ``train`` call
 
     # ------------------------------------------------------------------ what the two classes differ in
     def _total_iters_line(self, t_total):
@@ -619,8 +646,27 @@ class FineTuner:
         print(f"lr: {self.optim.state_dict()['param_groups'][0]['lr']}")  # src/vqa/vqacpv2.py:289
 
     # ------------------------------------------------------------------ engines
+    def _dp(self):
+        """(rank, world, group) when the driver was built with ``data_parallel=True`` on a model prepared by
+        ``enable_data_parallel`` and the group has several ranks, else None: everything then runs as it always did"""
+        gs = getattr(self.model, "_grad_sync", None)
+        if not self.data_parallel or gs is None or gs.world <= 1:
+            return None
+        import torch.distributed as dist
+        return dist.get_rank(gs.group), gs.world, gs.group
+
     def _n_batches(self, loader):
+        """iterations of a training epoch; data parallel: GLOBAL steps of world x B samples"""
+        dp = self._dp()
+        if dp is not None:
+            self._need_store(loader)
+            return global_steps(len(loader), self.B, dp[1])
         return len(loader) // self.B if _is_store(loader) else len(loader)
+
+    def _need_store(self, loader):
+        if not _is_store(loader):
+            raise ValueError("%s: under data parallelism the loader must be a ResidentDataset (its order is sharded over the "
+                             "ranks); a host loader would have to be sharded by the caller" % type(self).__name__)
 
     def _engine(self, make_batch, B, n_batches):
         """the captured iteration at ``B`` rows with an answer log for a whole epoch and a training log for ``log_every``
@@ -671,9 +717,11 @@ class FineTuner:
         if tr is None or state["pending"] == 0:
             return
         from ..engine import TrainLog
-        rec = tr.train_log.read()
-        tr.train_log.reset()
+        dp = self._dp()
         m = 2 * state["pending"]
+        # data parallel (a COLLECTIVE read: every rank flushes after the same iterations): the mean of the ranks' records
+        rec = tr.train_log.read() if dp is None else tr.train_log.fold(m, dp[2])
+        tr.train_log.reset()
         values, kinds = rec["values"][-m:], rec["kinds"][-m:]
         if int(rec["cursor"]) != m or values.shape[0] != m:
             raise RuntimeError("%s: the training log holds %d records, %d were expected" % (type(self).__name__, int(rec["cursor"]), m))
@@ -700,6 +748,9 @@ class FineTuner:
         from ..answers import to_quesid2ans
         dset, loader, evaluator = _tuple(train_tuple)
         resident = _is_store(loader)
+        from ..dist import rank0_printer
+        dp = self._dp()
+        print = rank0_printer(dp)  # data parallel: rank 0 alone prints, writes log.log, calls the writer and saves
         n_batches = self._n_batches(loader)
         val_in_epoch = set(int(v) for v in val_schedule(n_batches))
         seed = int(getattr(self.args, "seed", 0) or 0)
@@ -714,10 +765,21 @@ class FineTuner:
             if valid_score > best_valid:
                 best_valid = valid_score
                 self.save("BEST")
+            self.best_valid = best_valid
             return valid_score
 
         for epoch in range(self.args.epochs):
-            if resident:
+            branches = None
+            if dp is not None:
+                from ..dist import sync_branches
+                # the epoch's samples in GLOBAL order, perm[:steps * B * world] (the train score is taken over it), then this
+                # rank's B rows of every global step: the second call leaves ITS order in the store's device buffer
+                global_order = loader.order(epoch, shuffle=True, seed=seed, drop_last=True, batch_size=self.B * dp[1])
+                order = loader.order(epoch, shuffle=True, seed=seed, rank=dp[0], world=dp[1], drop_last=True, batch_size=self.B)
+                batches = range(n_batches)
+                # rank 0's draws for the whole epoch, ONE broadcast: ranks on different branches would exchange different ranges
+                branches = sync_branches(n_batches, self.device, dp[2], delta=self.args.delta)
+            elif resident:
                 order = loader.order(epoch, shuffle=True, seed=seed, drop_last=True, batch_size=self.B)
                 batches = range(n_batches)
             else:
@@ -733,7 +795,8 @@ class FineTuner:
                     ques_ids.extend(item[0].tolist() if torch.is_tensor(item[0]) else item[0])
                 if i == 0:
                     tr.answer_log.reset()  # nothing has been logged in this epoch: the plain pass below is its first append
-                tr.iteration(pick_branch(self.args.delta, model=self.model))
+                tr.iteration(pick_branch(self.args.delta, model=self.model) if branches is None else
+                             ("rel" if branches[i] else "node"))
                 state["pending"] += 1
                 if state["pending"] == self.window:
                     self._flush_losses(state)
@@ -748,7 +811,12 @@ class FineTuner:
             self._flush_losses(state)
             # *compute train score*
             log = self.trainer.answer_log
-            if resident:
+            if dp is not None:
+                # a COLLECTIVE merge: the ranks' logs interleaved back into the global order, scored on EVERY rank -- same bits
+                from ..ops import FOLD_INTERLEAVE
+                merged = log.fold(FOLD_INTERLEAVE, [n_batches * self.B] * dp[1], block=self.B, group=dp[2])
+                train_score = merged.score_store(loader, order=global_order, keep=loader.keep_mask(global_order))["score"] * 100.
+            elif resident:
                 train_score = log.score_store(loader, order=loader._order, keep=loader.keep_mask(order))["score"] * 100.
             else:
                 train_score = evaluator.evaluate(to_quesid2ans(ques_ids, log.read()[0], dset.label2ans)) * 100.
@@ -765,9 +833,10 @@ class FineTuner:
             self.history.append(dict(epoch=epoch, train=train_score, valid=valid_score, best=best_valid))
             log_str = self._epoch_lines(epoch, train_score, valid_score, best_valid)
             print(log_str, end='')
-            with open(self.output + "/log.log", 'a') as f:
-                f.write(log_str)
-                f.flush()
+            if dp is None or dp[0] == 0:
+                with open(self.output + "/log.log", 'a') as f:
+                    f.write(log_str)
+                    f.flush()
         if self.writer is not None and hasattr(self.writer, "close"):
             self.writer.close()
 
@@ -776,8 +845,35 @@ class FineTuner:
         one captured predictor and its answer log"""
         dset, loader, evaluator = _tuple(eval_tuple)
         self.sweeps += 1
+        dp = self._dp()
+        if dp is not None:
+            # a COLLECTIVE call: the dict is built from the merged log, the same on every rank; rank 0 alone writes ``dump``
+            from ..answers import to_quesid2ans
+            labels = self._sweep_ranks(loader, dp).read()[0]
+            quesid2ans = to_quesid2ans(loader.ques_ids(range(len(loader))), labels, dset.label2ans)
+            if dump is not None and dp[0] == 0:
+                evaluator.dump_result(quesid2ans, dump)
+            return quesid2ans
         return predict(self.model, (dset, loader, evaluator), dump, predictor=self._predictor(loader),
                        resident=loader if _is_store(loader) else None)
+
+    def _sweep_ranks(self, loader, dp):
+        """the data-parallel validation sweep (a COLLECTIVE call): rank r pushes the positions ``shard_range(n, r, world)`` of
+        the data set order through its own predictor -- no collective inside the sweep, so the slices may be uneven; a rank
+        with an empty slice pushes nothing -- and the ranks' logs are then concatenated in rank order (``AnswerLog.fold``)
+        -> the merged log of all ``n`` answers in data set order, on every rank"""
+        from ..dist import shard_range
+        from ..ops import FOLD_CONCAT
+        self._need_store(loader)
+        rank, world, group = dp
+        pred = self._predictor(loader)
+        n = len(loader)
+        mine = shard_range(n, rank, world)
+        loader.order(0, shuffle=False, drop_last=False)
+        pred.log.reset()
+        for start in range(mine.start, mine.stop, pred.B):
+            pred.push_resident(loader, start, min(pred.B, mine.stop - start))
+        return pred.log.fold(FOLD_CONCAT, [len(shard_range(n, r, world)) for r in range(world)], group=group)
 
     def evaluate(self, eval_tuple, dump=None, by_group=False):
         """the evaluator's score of a split as a float (src/vqa/vqacpv2.py:341-344).  With a resident store and no ``dump``
@@ -789,14 +885,21 @@ class FineTuner:
             if by_group:
                 raise ValueError("%s.evaluate: by_group needs a resident store with groups and no dump" % type(self).__name__)
             return evaluator.evaluate(self.predict(eval_tuple, dump))
-        pred = self._predictor(loader)
+        dp = self._dp()
         self.sweeps += 1
-        n = len(loader)
-        loader.order(0, shuffle=False, drop_last=False)
-        pred.log.reset()
-        for start in range(0, n, pred.B):
-            pred.push_resident(loader, start, min(pred.B, n - start))
-        res = pred.log.score_store(loader, keep=loader.keep_mask(), by_group=by_group)
+        if dp is not None:
+            # every rank scores the merged log with the GLOBAL keep mask: a question id on both sides of a rank boundary
+            # counts once, with its last answer, and every rank holds the same bits
+            log = self._sweep_ranks(loader, dp)
+        else:
+            pred = self._predictor(loader)
+            n = len(loader)
+            loader.order(0, shuffle=False, drop_last=False)
+            pred.log.reset()
+            for start in range(0, n, pred.B):
+                pred.push_resident(loader, start, min(pred.B, n - start))
+            log = pred.log
+        res = log.score_store(loader, keep=loader.keep_mask(), by_group=by_group)
         return dict(res["by_group"], all=res["score"]) if by_group else res["score"]
 
     def oracle_score(self, data_tuple):
@@ -828,8 +931,13 @@ class FineTuner:
         return evaluator.evaluate(to_quesid2ans(ques_ids, log.read()[0], dset.label2ans))
 
     def save(self, name):
+        """data parallel: rank 0 writes (the replicas are equal), the other ranks write nothing"""
         import os
-        torch.save(self.model.state_dict(), os.path.join(self.output, "%s.pth" % name))
+        dp = self._dp()
+        state = self.model.state_dict()  # under the sharded update a collective (the masters are gathered): on every rank
+        if dp is not None and dp[0] != 0:
+            return
+        torch.save(state, os.path.join(self.output, "%s.pth" % name))
 
     def load(self, path):
         print("Load model from %s" % path)
