@@ -1577,6 +1577,66 @@ typedef struct xggm_tokenize_args {
 int xggm_tokenize_wordpiece(const xggm_tokenize_args* args, xggm_stream_t stream);
 size_t xggm_tokenize_workspace_bytes(int64_t n, int T);
 
+/* xggm_tsv_decode: the six base64 fields of n lines of a bottom-up feature TSV (train2014_obj36.tsv, vg_gqa_obj36.tsv ...)
+ * -> rows [row0, row0 + n) of the stores' image tables in ONE launch: what the host does per line with base64.b64decode +
+ * np.frombuffer + reshape (src/utils.py:41-52) and, with normalize != 0, per item with the box normalisation and its range
+ * check (src/pretrain/lxmert_data.py:165-171, src/vqa/vqacpv2_data.py:108-117).  Integer and bit work, one correctly rounded
+ * division: every output is exact.  O objects and F features per object are fixed per table.
+ *   text [alloc_bytes] uint8 (device): a chunk of the file as it is, of which [0, n_bytes) is text.  Field starts have no
+ *   alignment and the kernel fetches whole aligned 16-byte words around a field, so text must be 16-byte aligned and
+ *   alloc_bytes, the size of its allocation, a multiple of 16 (>= n_bytes): every read stays inside [0, alloc_bytes).
+ *   desc [n, XGGM_TSV_DESC] int64 (device): per line XGGM_TSV_FIELDS (offset, length) pairs into text -- objects_id,
+ *   objects_conf, attrs_id, attrs_conf, boxes, features, the file's order -- then img_w, img_h.  The host finds them
+ *   (xggm_amd.tools.tsv.scan_chunk).  host_desc: the same values in HOST memory, read here before the launch (they are
+ *   what is refused below); the kernel holds every read inside the buffer whatever the device copy says.
+ * Outputs, each may be NULL (not all; flags and counts are the same whichever tables are asked for: every field is
+ * decoded); of rows [row0, row0 + n) every element is written, no store ever leaves them:
+ *   feats [capacity, O, F] fp32 (bit copies of the O F little-endian fp32) or, feats_bf16 != 0, bf16 rounded to nearest
+ *     even: bit for bit torch.Tensor.to(torch.bfloat16) on every non-NaN input (0x7F7FFFFF becomes inf); a NaN becomes 0x7FC0;
+ *   boxes [capacity, O, 4] fp32; normalize != 0: columns 0, 2 divided by (float)img_w, columns 1, 3 by (float)img_h,
+ *     correctly rounded (numpy's b[:, (0, 2)] /= img_w on float32), then checked in double: b < 1 + 1e-5 and -b < 1e-5
+ *     (a NaN fails);
+ *   obj_labels, attr_labels [capacity, O] int32 from the O little-endian int64 of objects_id / attrs_id; a value outside
+ *     int32 is flagged and stored as 0;  obj_confs, attr_confs [capacity, O] fp32 bit copies;
+ *   flags [n] uint32, one per LINE (not per table row): bit 0 a character outside the base64 alphabet, or '=' anywhere but
+ *     the last one or two places that bytes % 3 calls for (or something else there); bit 1 a field whose length is not
+ *     4 ceil(bytes / 3) for this O, F; bit 2 an id outside int32; bit 3 a box outside the range check; bit 4 a non-finite
+ *     feature (informational); bits 8 .. 13 which of the six fields raised bits 0-1;
+ *   counts [2] int32 (the caller zeroes them): += the lines with any of bits 0-2, += the lines with bit 3 (one integer
+ *     atomic add per such line; there are no other atomics).
+ * A line with bit 0 or 1 still writes its whole rows: a field of the wrong length decodes to zeros, a wrong character to
+ * six zero bits.  Lines with bits 0-2 are for the host path to redo (utils.load_obj_tsv): base64.b64decode skips what
+ * this kernel flags.
+ * One launch, one workgroup of 256 threads per line; text is staged through LDS (37 KB), nothing is allocated, there is
+ * no workspace and no host synchronisation.
+ * Refused before any launch: a null struct / text / desc / host_desc, every output null, n < 1, O outside [1,
+ * XGGM_TSV_MAX_OBJECTS], F < 1, F % 8 != 0 (feature rows move 16 bytes per lane), O F >= 2^28, row0 < 0 or row0 + n beyond
+ * capacity, an offset or length that is negative or ends past n_bytes, (normalize) img_w or img_h outside [1, 2^24), text
+ * not 16-byte aligned or alloc_bytes no multiple of 16 or below n_bytes, feats not 16-byte aligned, another table not 4-byte
+ * aligned. */
+#define XGGM_TSV_FIELDS 6
+#define XGGM_TSV_DESC 14
+#define XGGM_TSV_MAX_OBJECTS 128
+typedef struct xggm_tsv_decode_args {
+    const uint8_t* text;          /* [alloc_bytes] */
+    int64_t n_bytes, alloc_bytes;
+    const int64_t* desc;          /* [n, XGGM_TSV_DESC] device */
+    const int64_t* host_desc;     /* [n, XGGM_TSV_DESC] host */
+    int64_t n;
+    int O, F;
+    int feats_bf16, normalize;
+    int64_t row0, capacity;
+    void* feats;                  /* [capacity, O, F] out or NULL */
+    float* boxes;                 /* [capacity, O, 4] out or NULL */
+    int32_t* obj_labels;          /* [capacity, O] out or NULL */
+    int32_t* attr_labels;
+    float* obj_confs;
+    float* attr_confs;
+    uint32_t* flags;              /* [n] out or NULL */
+    int32_t* counts;              /* [2] in/out or NULL */
+} xggm_tsv_decode_args;
+int xggm_tsv_decode(const xggm_tsv_decode_args* args, xggm_stream_t stream);
+
 /* ---- utilities ---------------------------------------------------------------------------*/
 int xggm_rng_advance(uint64_t* rng, uint64_t by, xggm_stream_t stream);
 int xggm_cast_f32_to_bf16(const float* x, void* out, int64_t n, xggm_stream_t stream);

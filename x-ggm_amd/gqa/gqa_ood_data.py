@@ -6,7 +6,7 @@ import os
 import numpy as np
 import torch
 
-from ..vqa.vqacpv2_data import VQADataset, VQATorchDataset, VQAEvaluator, load_json, ShardReader
+from ..vqa.vqacpv2_data import VQADataset, VQATorchDataset, VQAEvaluator, load_json, ShardReader, ObjTable
 
 GQA_DATA_ROOT = 'data/gqa_ood/'
 VG_GQA_IMGFEAT_ROOT = 'data/vg_gqa_imgfeat/'
@@ -35,7 +35,7 @@ class GQATorchDataset(VQATorchDataset):
         self.raw_dataset = dataset
         if shard is None:
             shard = os.path.join(imgfeat_root, '%s_obj36.xgs' % dataset.splits[0])
-        self.shard = shard if isinstance(shard, ShardReader) else ShardReader(shard)
+        self.shard = shard if isinstance(shard, (ShardReader, ObjTable)) else ShardReader(shard)
         self.data = []
         for datum in dataset.data:  # ref :88-93: once per label that is in the answer table
             for ans, score in datum['label'].items():

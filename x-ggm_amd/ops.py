@@ -2813,6 +2813,66 @@ def tokenize_wordpiece(data, offsets, host_offsets, T, tables, outputs=("ids", "
     return res
 
 
+# ----------------------------------------------------------------------------- feature files
+class TsvDecodeArgs(_ct.Structure):
+    """mirror of ``xggm_tsv_decode_args`` (include/xggm.h)"""
+    _fields_ = [("text", _ct.c_void_p), ("n_bytes", _ct.c_int64), ("alloc_bytes", _ct.c_int64), ("desc", _ct.c_void_p),
+                ("host_desc", _ct.c_void_p), ("n", _ct.c_int64), ("O", _ct.c_int), ("F", _ct.c_int), ("feats_bf16", _ct.c_int),
+                ("normalize", _ct.c_int), ("row0", _ct.c_int64), ("capacity", _ct.c_int64), ("feats", _ct.c_void_p),
+                ("boxes", _ct.c_void_p), ("obj_labels", _ct.c_void_p), ("attr_labels", _ct.c_void_p), ("obj_confs", _ct.c_void_p),
+                ("attr_confs", _ct.c_void_p), ("flags", _ct.c_void_p), ("counts", _ct.c_void_p)]
+
+
+TSV_TABLES = ("feats", "boxes", "obj_labels", "attr_labels", "obj_confs", "attr_confs")
+TSV_DESC = 14  # XGGM_TSV_DESC
+
+
+def tsv_decode(text, n_bytes, desc, host_desc, O, F, tables, row0, flags=None, counts=None, normalize=True):
+    """the six base64 fields of n TSV lines -> rows [row0, row0 + n) of ``tables`` in ONE launch; contract: xggm_tsv_decode
+    in xggm.h.  ``text`` uint8 [allocation, a multiple of 16] of which the first ``n_bytes`` are text; ``desc`` int64
+    [n, 14] on the device and ``host_desc``, the same values as a numpy int64 array (checked on the host before the
+    launch): what ``tools.tsv.scan_chunk`` returns.  ``tables``: dict with some of ``TSV_TABLES`` -- feats [cap, O, F] bf16
+    or fp32, boxes [cap, O, 4] fp32, obj_labels / attr_labels [cap, O] int32, obj_confs / attr_confs [cap, O] fp32, one
+    capacity.  ``flags`` int32 [n] (the kernel's uint32 bit patterns), ``counts`` int32 [2] (added to).  -> tables"""
+    import numpy as np
+    who = "tsv_decode"
+    _c(text, torch.uint8, "text"), _c(desc, torch.int64, "desc")
+    dev, O, F = text.device, int(O), int(F)
+    host_desc = np.ascontiguousarray(host_desc, dtype=np.int64)
+    n = desc.shape[0] if desc.dim() == 2 else -1
+    if n < 1 or desc.shape[1] != TSV_DESC or host_desc.shape != (n, TSV_DESC):
+        raise ValueError("%s: desc is %s, host_desc %s, [n >= 1, %d] expected of both" % (who, tuple(desc.shape), host_desc.shape, TSV_DESC))
+    if set(tables) - set(TSV_TABLES):
+        raise ValueError("%s: tables %r, some of %r expected" % (who, sorted(tables), TSV_TABLES))
+    a = TsvDecodeArgs()
+    cap = None
+    want = dict(feats=((O, F), None), boxes=((O, 4), F32), obj_labels=((O,), torch.int32), attr_labels=((O,), torch.int32),
+                obj_confs=((O,), F32), attr_confs=((O,), F32))
+    for k, t in tables.items():
+        shape, dt = want[k]
+        _c(t, dt, k)
+        if k == "feats" and t.dtype not in (F32, BF16):
+            raise TypeError("%s: feats are %s, bfloat16 or float32 expected" % (who, t.dtype))
+        if tuple(t.shape[1:]) != shape or t.dim() != len(shape) + 1 or (cap is not None and t.shape[0] != cap):
+            raise ValueError("%s: table %s is %s, [%s, %s] expected" % (who, k, tuple(t.shape), cap if cap is not None else "capacity",
+                                                                      ", ".join(map(str, shape))))
+        cap = t.shape[0]
+        setattr(a, k, ptr(t))
+    if flags is not None and _c(flags, torch.int32, "flags").shape != (n,):
+        raise ValueError("%s: flags hold %s, [%d] expected" % (who, tuple(flags.shape), n))
+    if counts is not None and _c(counts, torch.int32, "counts").numel() != 2:
+        raise ValueError("%s: counts int32 [2] expected" % who)
+    for t in [desc] + list(tables.values()) + [flags, counts]:
+        if t is not None and t.device != dev:
+            raise RuntimeError("%s: all operands must live on one device" % who)
+    a.text, a.n_bytes, a.alloc_bytes, a.desc, a.host_desc = ptr(text), int(n_bytes), text.numel(), ptr(desc), host_desc.ctypes.data
+    a.n, a.O, a.F, a.normalize, a.row0, a.capacity = n, O, F, int(bool(normalize)), int(row0), int(row0) + n if cap is None else cap  # no table: flags / counts alone
+    a.feats_bf16 = int("feats" in tables and tables["feats"].dtype == BF16)
+    a.flags, a.counts = ptr(flags), ptr(counts)
+    call("xggm_tsv_decode", _ct.addressof(a), stream())
+    return tables
+
+
 # ----------------------------------------------------------------------------- graph attention
 def gat_att_fwd(s, adj, alpha, long=False):
     _c(s, F32, "s"), _c(adj, F32, "adj")

@@ -29,10 +29,12 @@ The batch itself can come from the device: ``pretrain.resident.ResidentPretrainS
 HBM and one launch gathers a clean batch with the swap fused in -- drawn from EVERY sample, as the reference draws -- in
 place of ``collate_examples`` and thirteen copies; ``LXMERT(resident=True)`` takes such a store as the loader of a tuple.
 
-Out of scope here: the data-set readers and the evaluator of src/pretrain/lxmert_data.py (``LXMERTDataset``,
-``LXMERTTorchDataset``, ``LXMERTEvaluator``: the data files are absent offline; any ``(dataset, loader, evaluator)`` whose
-loader yields lists of ``InputExample`` or is a ``ResidentPretrainSet`` serves), the packed loader ring of the fine-tuning
-side, and fusing the masking into the visual-embedding product's input read.
+The feature files have a reader of their own: ``tools.tsv.load_obj_tsv_device`` decodes a bottom-up TSV on the device into
+an ``ObjTable``, which ``pretrain.resident.pretrain_tables(..., images=table)`` hands to the store without a copy
+(``utils.load_obj_tsv`` is the host path).  Out of scope here: the json annotation readers and the evaluator of
+src/pretrain/lxmert_data.py (``LXMERTDataset``, ``LXMERTTorchDataset``, ``LXMERTEvaluator``; any ``(dataset, loader,
+evaluator)`` whose loader yields lists of ``InputExample`` or is a ``ResidentPretrainSet`` serves), the packed loader ring
+of the fine-tuning side, and fusing the masking into the visual-embedding product's input read.
 
 Data parallel (the reference's ``--multiGPU``, :255-256): ``enable_data_parallel`` prepares the model, the captured step
 exchanges the gradients between its two graphs (``engine.CapturedPretrainer``) and ``LXMERT`` shards a resident store over
@@ -248,17 +250,22 @@ class InputExample(object):
         self.obj_labels, self.attr_labels, self.is_matched, self.label = obj_labels, attr_labels, is_matched, label
 
 
-def image_key(example):
-    """a stable non-negative integer per distinct image id: the same in every batch and every process, so that a sentence
-    pool may span batches.  The image id is ``example.img_id`` when the example carries one, else the head of the
-    reference's uid ``"<img_id>_<dset>_<idx>"`` (src/pretrain/lxmert_data.py:80-81, which returns it as a 1-tuple)."""
-    import hashlib
+def image_id(example):
+    """the image id of an example as a string: ``example.img_id`` when the example carries one, else the head of the
+    reference's uid ``"<img_id>_<dset>_<idx>"`` (src/pretrain/lxmert_data.py:80-81, which returns it as a 1-tuple)"""
     img = getattr(example, "img_id", None)
     if img is None:
         uid = example.uid[0] if isinstance(example.uid, (tuple, list)) else example.uid
         parts = str(uid).rsplit("_", 2)
         img = parts[0] if len(parts) == 3 else str(uid)
-    return int.from_bytes(hashlib.blake2b(str(img).encode("utf-8"), digest_size=8).digest(), "little") >> 1
+    return str(img)
+
+
+def image_key(example):
+    """a stable non-negative integer per distinct image id (``image_id``): the same in every batch and every process, so
+    that a sentence pool may span batches"""
+    import hashlib
+    return int.from_bytes(hashlib.blake2b(image_id(example).encode("utf-8"), digest_size=8).digest(), "little") >> 1
 
 
 def collate_examples(examples, tokenizer, max_seq_length, max_labels):

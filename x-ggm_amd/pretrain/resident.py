@@ -23,23 +23,27 @@ import torch
 
 from .. import ops
 from ..lxrt.tokenization import DeviceTokenizer
-from ..tools.resident import ResidentDataset, host_feats
+from ..tools.resident import ResidentDataset, adopted_to_host, host_feats, table_dtype
 from ..tools.shards import _bf16_bits
-from .lxmert_pretrain import SID_BASE, image_key
+from .lxmert_pretrain import SID_BASE, image_id, image_key
 
 IMAGE_TABLES = ("feats", "boxes", "obj_labels", "attr_labels", "obj_confs", "attr_confs")
 SAMPLE_TABLES = ("q_row", "q_ids", "q_len", "q_label", "q_score")
 TRIES = ops.PRETRAIN_SWAP_TRIES
 
 
-def pretrain_tables(examples, tokenizer, max_seq_length, max_labels, n_answers=None, vocab_size=None, feats_bf16=False):
+def pretrain_tables(examples, tokenizer, max_seq_length, max_labels, n_answers=None, vocab_size=None, feats_bf16=False, images=None):
     """a list of ``InputExample`` -> the host tables of the store (numpy arrays under the kernel's names, plus ``uids``, the
     examples' uids as a list).  Images are de-duplicated by ``image_key`` in order of first appearance, which fixes the row
     order; sentences are laid out as ``collate_examples`` lays them out.  ``feats_bf16``: store the features as bf16 bit
     patterns (uint16, torch's rounding) instead of the examples' fp32.  Everything the kernel will trust is checked here,
     once, with a ValueError naming the example: rows fit int32, token ids lie in [0, vocab) (``vocab_size``, default: the
     tokenizer's vocabulary when it has one), labels in [0, n_answers) (``n_answers`` None: only negative ids are refused), at
-    most ``max_labels`` keys, one shape for the object and attribute arrays of all images, F % 8 == 0."""
+    most ``max_labels`` keys, one shape for the object and attribute arrays of all images, F % 8 == 0.
+    ``images``: a ``tools.tsv.ObjTable`` (a feature file decoded on the device).  The examples then carry only uid, sent,
+    label and optionally img_id -- their feature members may be None --, the image row of an example is
+    ``images.row_of[<its image id>]`` (``image_id``; a missing image raises ValueError naming the example), and the returned
+    dict carries the table's device tensors as the six image tables, in the table's row order, for the store to adopt."""
     who = "pretrain_tables"
     n_q, T, K = len(examples), int(max_seq_length), int(max_labels)
     if n_q < 1 or T < 2 or K < 1:
@@ -55,8 +59,10 @@ def pretrain_tables(examples, tokenizer, max_seq_length, max_labels, n_answers=N
     if isinstance(tokenizer, DeviceTokenizer):  # every sentence in one launch, one read-back; the checks below stay
         dev_ids, dev_len = (t.cpu().numpy() for t in tokenizer.encode([ex.sent for ex in examples], T))
     for i, ex in enumerate(examples):
-        key = image_key(ex)
-        r = rows.get(key)
+        key = image_key(ex) if images is None else image_id(ex)
+        r = rows.get(key) if images is None else images.row_of.get(key)
+        if r is None and images is not None:
+            raise ValueError("%s: example %r refers to image %r, which the feature table does not hold" % (who, ex.uid, key))
         if r is None:
             arrs = (np.asarray(ex.visual_feats[0], dtype=np.float32), np.asarray(ex.visual_feats[1], dtype=np.float32),
                     np.asarray(ex.obj_labels[0]), np.asarray(ex.attr_labels[0]),
@@ -94,12 +100,15 @@ def pretrain_tables(examples, tokenizer, max_seq_length, max_labels, n_answers=N
             if int(k) < 0 or (n_answers is not None and int(k) >= n_answers) or int(k) >= (1 << 31):
                 raise ValueError("%s: example %r has label %d outside the answer table [0, %s)" % (who, ex.uid, int(k), n_answers))
             q_label[i, j], q_score[i, j] = int(k), v
-    feats = np.stack([a[0] for a in per_image])
-    t = dict(feats=_bf16_bits(feats) if feats_bf16 else feats, boxes=np.stack([a[1] for a in per_image]),
-             obj_labels=np.stack([a[2] for a in per_image]).astype(np.int32),
-             attr_labels=np.stack([a[3] for a in per_image]).astype(np.int32),
-             obj_confs=np.stack([a[4] for a in per_image]), attr_confs=np.stack([a[5] for a in per_image]),
-             q_row=q_row, q_ids=q_ids, q_len=q_len, q_label=q_label, q_score=q_score)
+    t = dict(q_row=q_row, q_ids=q_ids, q_len=q_len, q_label=q_label, q_score=q_score)
+    if images is not None:
+        t.update(images.tables())
+    else:
+        feats = np.stack([a[0] for a in per_image])
+        t.update(feats=_bf16_bits(feats) if feats_bf16 else feats, boxes=np.stack([a[1] for a in per_image]),
+                 obj_labels=np.stack([a[2] for a in per_image]).astype(np.int32),
+                 attr_labels=np.stack([a[3] for a in per_image]).astype(np.int32),
+                 obj_confs=np.stack([a[4] for a in per_image]), attr_confs=np.stack([a[5] for a in per_image]))
     t["uids"] = [ex.uid for ex in examples]
     return t
 
@@ -111,7 +120,8 @@ def check_tables(t):
     if missing:
         raise ValueError("%s: the tables lack %s" % (who, missing))
     f = t["feats"]
-    if f.ndim != 3 or f.dtype not in (np.uint16, np.float32):
+    dtype_of = lambda a: table_dtype(a, feats=a is f)
+    if f.ndim != 3 or dtype_of(f) not in (np.uint16, np.float32):
         raise ValueError("%s: feats %s %s, [n_img, O, F] uint16 (bf16 bits) or float32 expected" % (who, f.shape, f.dtype))
     n_img, O, F = f.shape
     n_q = t["q_row"].shape[0]
@@ -124,8 +134,8 @@ def check_tables(t):
                 obj_confs=((n_img, O), np.float32), attr_confs=((n_img, O), np.float32), q_row=((n_q,), np.int32),
                 q_ids=((n_q, T), np.int32), q_len=((n_q,), np.int32), q_label=((n_q, K), np.int32), q_score=((n_q, K), np.float32))
     for k, (shape, dt) in want.items():
-        if t[k].shape != shape or t[k].dtype != dt:
-            raise ValueError("%s: table %s is %s %s, %s %s expected" % (who, k, t[k].shape, t[k].dtype, shape, np.dtype(dt)))
+        if tuple(t[k].shape) != shape or dtype_of(t[k]) != dt:
+            raise ValueError("%s: table %s is %s %s, %s %s expected" % (who, k, tuple(t[k].shape), t[k].dtype, shape, np.dtype(dt)))
     if min(n_img, n_q, O, F, T, K) < 1:
         raise ValueError("%s: empty tables" % who)
     if t["q_row"].min() < 0 or t["q_row"].max() >= n_img:
@@ -193,7 +203,9 @@ class ResidentPretrainSet:
                  feats_bf16=False, match_rate=None, sid_base=SID_BASE, chunk_bytes=64 << 20, max_bytes=None, batch_size=None):
         """``source``: ready host tables (a dict as ``pretrain_tables`` returns it) or a list of ``InputExample`` (then
         ``tokenizer`` and ``max_seq_length`` are needed and ``max_labels`` / ``n_answers`` / ``vocab_size`` / ``feats_bf16``
-        go to ``pretrain_tables``).  ``match_rate`` (None: no swap): the fused matched-sentence swap of ``fill``, drawn at
+        go to ``pretrain_tables``).  An image table of ``source`` that is a tensor on ``device`` already (``pretrain_tables(...,
+        images=table)``: a feature file decoded on the device) is adopted -- the same storage, no copy, counted in ``nbytes``
+        like an uploaded one; ``host_batch`` reads it back on first use.  ``match_rate`` (None: no swap): the fused matched-sentence swap of ``fill``, drawn at
         Philox streams ``sid_base + 5 / 6``.  The tables are uploaded once through ONE pinned staging buffer of
         ``chunk_bytes``; ``max_bytes``: refuse (ValueError naming the total) a corpus whose tables exceed it, default: the
         device's free memory minus 2 GiB.  ``batch_size``: the default of ``order`` and of the driver loop."""
@@ -207,8 +219,9 @@ class ResidentPretrainSet:
         if self.match_rate is not None and not 0.0 <= self.match_rate <= 1.0:
             raise ValueError("ResidentPretrainSet: match_rate %r outside [0, 1]" % (match_rate,))
         self._uids = source.get("uids")
+        # numpy arrays to upload, or (image tables) tensors that already live on the device: adopted, not copied
         self.host = {k: source[k] for k in IMAGE_TABLES + SAMPLE_TABLES}
-        self.nbytes = sum(int(v.nbytes) for v in self.host.values())
+        self.nbytes = sum(int(v.numel() * v.element_size() if torch.is_tensor(v) else v.nbytes) for v in self.host.values())
         cuda = self.device.type == "cuda"
         if max_bytes is None and cuda:
             max_bytes = torch.cuda.mem_get_info(self.device)[0] - (2 << 30)
@@ -275,6 +288,7 @@ class ResidentPretrainSet:
         """``fill`` restated in numpy from the same tables, for the SAMPLE indices given (not positions of the order); the
         swap only from explicit ``draws``, else a clean batch.  feats in the table's type unless ``out_f32`` says otherwise.
         The CPU-testable reference of the kernel; no fallback."""
+        adopted_to_host(self.host)
         if out_f32 is None:
             out_f32 = self.host["feats"].dtype == np.float32
         return gather_pretrain_host(self.host, indices, draws=draws, match_rate=self.match_rate if draws else None, out_f32=out_f32)

@@ -88,6 +88,25 @@ def host_feats(f, out_f32=False):
     raise TypeError("gather_host: feats are %s, uint16 (bf16 bits) or float32 expected" % f.dtype)
 
 
+def table_dtype(a, feats=False):
+    """the numpy dtype a host table would have: an array's own, a tensor's counterpart (bf16 ``feats``: uint16 bit patterns)"""
+    if not torch.is_tensor(a):
+        return a.dtype
+    if feats and a.dtype == torch.bfloat16:
+        return np.dtype(np.uint16)
+    return torch.empty(0, dtype=a.dtype).numpy().dtype if a.dtype != torch.bfloat16 else None
+
+
+def adopted_to_host(host):
+    """``host_batch`` on a store with adopted tables: read them back ON FIRST USE, into the host dict, as the numpy arrays
+    an uploaded store would have kept (bf16 features as uint16 bit patterns)"""
+    for k, v in host.items():
+        if torch.is_tensor(v):
+            v = v.detach().cpu().contiguous()
+            host[k] = v.view(torch.int16).numpy().view(np.uint16) if v.dtype == torch.bfloat16 else v.numpy()
+    return host
+
+
 def gather_host(tables, indices, A, out_f32=False):
     """``ops.batch_gather`` restated in numpy: the batch of the samples ``indices`` out of host ``tables`` (numpy arrays
     under the kernel's names; ``feats`` uint16 bf16 bit patterns or float32) -> dict of CPU tensors under the trainer's
@@ -130,6 +149,33 @@ def group_ids(data, key):
     return np.asarray([index[v] for v in values], dtype=np.int32), names
 
 
+def staged_upload(arr, device, chunk_bytes=64 << 20, stage=None, bf16_bits=False):
+    """a host table (numpy array, a memory map included) -> (tensor on ``device``, the pinned staging buffer): copied chunk by
+    chunk through ONE pinned buffer of ``chunk_bytes`` (``stage``: the buffer of an earlier call, reused; none is made for a
+    CPU device).  ``bf16_bits``: a uint16 array of bf16 bit patterns becomes a bfloat16 tensor.  How both resident stores
+    upload their tables."""
+    device = torch.device(device)
+    dt = torch.bfloat16 if bf16_bits else torch.from_numpy(np.empty(0, dtype=arr.dtype)).dtype
+    dst = torch.empty(arr.shape, dtype=dt, device=device)
+    flat = dst.view(-1).view(torch.int16) if bf16_bits else dst.view(-1)
+    src = np.asarray(arr).reshape(-1)
+    if bf16_bits:
+        src = src.view(np.int16)
+    if device.type != "cuda":
+        flat.numpy()[:] = src
+        return dst, stage
+    if stage is None:
+        stage = torch.empty(max(int(chunk_bytes), 4096), dtype=torch.uint8).pin_memory()
+    per = stage.numel() // src.itemsize
+    view = stage[:per * src.itemsize].view(flat.dtype)
+    for o in range(0, src.shape[0], per):
+        m = min(per, src.shape[0] - o)
+        view.numpy()[:m] = src[o:o + m]
+        flat[o:o + m].copy_(view[:m], non_blocking=True)
+        torch.cuda.current_stream(device).synchronize()  # the ONE staging buffer is rewritten next
+    return dst, stage
+
+
 class ResidentDataset:
     def __init__(self, ts, batcher, device, bias_index=None, chunk_bytes=64 << 20, max_bytes=None, batch_size=None, groups=None,
                  group_names=None):
@@ -168,12 +214,16 @@ class ResidentDataset:
             host["q_group"] = gi.astype(np.int32)
             self.G, self.group_names = G, list(group_names) if group_names is not None else list(range(G))
         # the shard's own arrays, as mapped: nothing is read before the upload (or host_batch) touches the rows
-        host["feats"] = sh.feats_bits if sh.feats_f is None else sh.feats_f
+        # (a ``tools.tsv.ObjTable`` -- a feature file decoded on the device -- hands over its tensors: adopted, not copied)
+        if hasattr(sh, "feats_bits"):
+            host["feats"] = sh.feats_bits if sh.feats_f is None else sh.feats_f
+        else:
+            host["feats"] = sh.feats
         host["boxes"] = sh.boxes
         host["adj"] = sh.adj
         self.host = host
         self.n, self.K = len(ts.data), host["q_label"].shape[1]
-        self.nbytes = sum(int(v.nbytes) for v in host.values() if v is not None)
+        self.nbytes = sum(int(v.numel() * v.element_size() if torch.is_tensor(v) else v.nbytes) for v in host.values() if v is not None)
         cuda = self.device.type == "cuda"
         if max_bytes is None and cuda:
             max_bytes = torch.cuda.mem_get_info(self.device)[0] - (2 << 30)
@@ -191,25 +241,13 @@ class ResidentDataset:
         return self.n
 
     def _upload(self, name, arr, chunk_bytes):
-        bf16 = name == "feats" and arr.dtype == np.uint16
-        dt = torch.bfloat16 if bf16 else torch.from_numpy(np.empty(0, dtype=arr.dtype)).dtype
-        dst = torch.empty(arr.shape, dtype=dt, device=self.device)
-        flat = dst.view(-1).view(torch.int16) if bf16 else dst.view(-1)
-        src = np.asarray(arr).reshape(-1)
-        if bf16:
-            src = src.view(np.int16)
-        if self.device.type != "cuda":
-            flat.numpy()[:] = src
-            return dst
-        if self._stage is None:
-            self._stage = torch.empty(max(chunk_bytes, 4096), dtype=torch.uint8).pin_memory()
-        per = self._stage.numel() // src.itemsize
-        stage = self._stage[:per * src.itemsize].view(flat.dtype)
-        for o in range(0, src.shape[0], per):
-            m = min(per, src.shape[0] - o)
-            stage.numpy()[:m] = src[o:o + m]
-            flat[o:o + m].copy_(stage[:m], non_blocking=True)
-            torch.cuda.current_stream(self.device).synchronize()  # the ONE staging buffer is rewritten next
+        if torch.is_tensor(arr):  # a table that already lives on the device is adopted: no copy, the same storage
+            same = arr.device.type == self.device.type and self.device.index in (None, arr.device.index)
+            if not same or not arr.is_contiguous():
+                raise ValueError("%s: table %s is a %s tensor on %s; only a contiguous tensor on the store's device %s is adopted"
+                                 % (type(self).__name__, name, "contiguous" if arr.is_contiguous() else "strided", arr.device, self.device))
+            return arr
+        dst, self._stage = staged_upload(arr, self.device, chunk_bytes, self._stage, bf16_bits=name == "feats" and arr.dtype == np.uint16)
         return dst
 
     # ------------------------------------------------------------------ epoch order
@@ -259,7 +297,7 @@ class ResidentDataset:
     def host_batch(self, indices, out_f32=False):
         """``fill`` restated in numpy from the same tables, for the SAMPLE indices given (not positions of the order):
         CPU tensors under the trainer's names plus ``sample``.  The CPU-testable reference of the kernel; no fallback."""
-        return gather_host(self.host, indices, self.A, out_f32)
+        return gather_host(adopted_to_host(self.host), indices, self.A, out_f32)
 
     def ques_ids(self, indices):
         """question ids of the samples ``indices`` (what ``fill`` leaves in ``sample``), for pairing with an ``AnswerLog``"""

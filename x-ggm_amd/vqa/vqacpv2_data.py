@@ -15,6 +15,7 @@ import torch
 from torch.utils.data import Dataset
 
 from ..tools.shards import ShardReader
+from ..tools.tsv import ObjTable
 
 TINY_IMG_NUM = 512
 FAST_IMG_NUM = 5000
@@ -57,14 +58,17 @@ class VQATorchDataset(Dataset):
     ``ShardReader``.  Only data whose image is in the shard are kept (:82-85).
     One difference from the reference's items: the shard stores the features as bf16 (half the bytes per sample; the
     benchmark dtype), so ``__getitem__`` returns the bf16-ROUNDED values as fp32 -- a parity run in fp32 execution
-    that wants the reference's exact fp32 inputs writes its shard with ``ShardWriter(..., feat_dtype="float32")``."""
+    that wants the reference's exact fp32 inputs writes its shard with ``ShardWriter(..., feat_dtype="float32")``.
+    ``shard`` may also be a ``tools.tsv.ObjTable``: a feature file decoded on the device (with ``set_adjacency`` for the
+    adjacency).  ``ResidentDataset`` then adopts its tensors; ``__getitem__`` reads one row back, for inspection; ``collate``
+    is refused: a device table does not feed the host loader."""
 
     def __init__(self, dataset, shard=None, imgfeat_root=MSCOCO_IMGFEAT_ROOT, tiny=False, fast=False):
         super().__init__()
         self.raw_dataset = dataset
         if shard is None:
             shard = os.path.join(imgfeat_root, '%s_obj36.xgs' % dataset.splits[0])
-        self.shard = shard if isinstance(shard, ShardReader) else ShardReader(shard)
+        self.shard = shard if isinstance(shard, (ShardReader, ObjTable)) else ShardReader(shard)
         key = dataset.img_key
         self.data = [d for d in dataset.data if d[key] in self.shard.row_of]
         # as the reference: only ``tiny`` truncates (src/vqa/vqacpv2_data.py:84-85); ``fast`` sets a top-k there that is
@@ -88,10 +92,12 @@ class VQATorchDataset(Dataset):
         datum = self.data[item]
         row = int(self.rows[item])
         feats = self.shard.feats_f32(row)
-        boxes = np.array(self.shard.boxes[row])
+        on_device = isinstance(self.shard, ObjTable)
+        boxes = self.shard.boxes_of(row) if on_device else np.array(self.shard.boxes[row])
         ques_id, ques = datum['question_id'], datum[self.raw_dataset.sent_key]
         if 'label' in datum:
-            return ques_id, feats, boxes, ques, self.target_of(datum), np.array(self.shard.adj[row])
+            adj = self.shard.adj[row].cpu().numpy() if on_device else np.array(self.shard.adj[row])
+            return ques_id, feats, boxes, ques, self.target_of(datum), adj
         return ques_id, feats, boxes, ques
 
     # ---- batch assembly for tools.data_loader.DataLoaderX
@@ -109,6 +115,9 @@ class VQATorchDataset(Dataset):
         """fill the host buffers ``out`` (``alloc``) with the samples ``items``; returns (ques_ids, sents, B).
         numpy on views of the (pinned) buffers only: a torch CPU op here would spin up the intra-op thread pool on the
         producer thread next to a training loop that needs the host for nothing but graph launches."""
+        if isinstance(self.shard, ObjTable):
+            raise RuntimeError("VQATorchDataset.collate: the features are a table on %s, which does not feed the host loader -- "
+                               "build a tools.resident.ResidentDataset from this data set" % self.shard.device)
         B = self.shard.gather(self.rows[np.asarray(items, dtype=np.int64)], out)
         tgt = out["target"].numpy()
         tgt[:B] = 0.0
