@@ -968,6 +968,20 @@ typedef struct xggm_batch_gather_args {
 } xggm_batch_gather_args;
 int xggm_batch_gather(const xggm_batch_gather_args* args, xggm_stream_t stream);
 
+/* xggm_batch_gather_labels: xggm_batch_gather for a store that keeps NO [n_img, N, N] adjacency.  out_adj[b] is made in
+ * the launch from image r's label ids and the class x attribute cosine table, by the per-image code of
+ * xggm_label_adjacency_f32 (below: data/preprocess/vqa/compute_adjacency.py:38-45, :75-90) -- the same bits that entry
+ * writes for the row.  Every other role, output, rule and refusal is xggm_batch_gather's; args->adj must be NULL (a
+ * stored table beside the label tables is refused), N <= 128, the label tables non-null and 4-byte aligned, Vc, Va > 0.
+ * An image with an id outside [0, Vc) / [0, Va) gets an all-NaN out_adj row; nothing is read outside the table. */
+typedef struct xggm_label_adj_args {
+    const float* table;            /* [Vc, Va] of xggm_label_cosine_table_f32 */
+    const int32_t* obj_labels;     /* [n_img, N] */
+    const int32_t* attr_labels;    /* [n_img, N] */
+    int Vc, Va;
+} xggm_label_adj_args;
+int xggm_batch_gather_labels(const xggm_batch_gather_args* args, const xggm_label_adj_args* labels, xggm_stream_t stream);
+
 /* xggm_pretrain_gather: a CLEAN pre-training batch assembled from a corpus that is RESIDENT on the device, with the
  * matched-sentence swap fused in, in ONE launch.  It replaces what LXMERTTorchDataset.__getitem__ does per example on the
  * host (src/pretrain/lxmert_data.py:148-199: look the image up, copy its features, boxes, object / attribute labels and
@@ -1063,6 +1077,26 @@ int xggm_pretrain_gather(const xggm_pretrain_gather_args* args, xggm_stream_t st
  * [n_img][N][N]; N <= 64, D % 4 == 0. */
 int xggm_cosine_adjacency_f32(const float* cls, const float* attr, float* adj, int n_img, int N, int D, float eps,
                               xggm_stream_t stream);
+
+/* adj_true from the detector's label ids.  The reference embeds the 2 N label strings of every image with BERT and calls
+ * torch.cosine_similarity 666 times per image (data/preprocess/vqa/compute_adjacency.py:38-45, :75-90:
+ * compute_cosin_sim_v2 and its caller); but an image's adjacency depends only on its ids, and there are only Vc x Va distinct cosines.
+ * xggm_label_cosine_table_f32: cls fp32 [Vc][D], attr fp32 [Va][D] (pooled embeddings of objects_vocab.txt /
+ *   attributes_vocab.txt) -> table fp32 [Vc][Va],
+ *     table[o][a] = dot(cls_o, attr_a) / (max(sqrt(|cls_o|^2), eps) * max(sqrt(|attr_a|^2), eps)),
+ *   each of the three sums ONE fmaf chain over k ascending from 0.f -- the arithmetic of xggm_cosine_adjacency_f32 and
+ *   xggm_cosine_adjacency_long_f32, so the table holds the bits those compute per image.  No matrix cores, no split sum.
+ *   D % 4 == 0, cls / attr 16-byte aligned, Vc, Va > 0.
+ * xggm_label_adjacency_f32: obj_labels, attr_labels int32 [n][N], 1 <= N <= 128 -> adj fp32 [n][N][N]; per image
+ *   c[i][j] = table[obj_i][attr_j] for j >= i, c + c on the diagonal and c + 0.f off it, the maximum by fmaxf, every
+ *   value divided by it, written to [i][j] and [j][i]: bit-equal to the two cosine entries on the gathered embeddings.
+ *   An image with an id outside [0, Vc) / [0, Va) is all NaN (its neighbours are untouched); nothing is read outside the
+ *   table.  One workgroup per image; no atomics.
+ * Refused before any launch: a null pointer, Vc or Va <= 0, n <= 0, N outside 1..128, D % 4 != 0, misaligned tables. */
+int xggm_label_cosine_table_f32(const float* cls, const float* attr, float* table, int Vc, int Va, int D, float eps,
+                                xggm_stream_t stream);
+int xggm_label_adjacency_f32(const float* table, int Vc, int Va, const int32_t* obj_labels, const int32_t* attr_labels,
+                             float* adj, int n, int N, xggm_stream_t stream);
 
 /* ---- optimiser ---------------------------------------------------------------------------
  * The gradient norm (nn.utils.clip_grad_norm_, src/vqa/vqacpv2.py:175).  Five entries, ONE mechanism -- "sum (the

@@ -8,6 +8,7 @@
 // workgroup, ordered by its barrier); nothing is accumulated, so there are no atomics.
 #include "common.h"
 #include "feat_move.h"
+#include "label_adjacency.h"
 #include "xggm.h"
 
 namespace {
@@ -15,7 +16,10 @@ using feat_move::NT;
 using feat_move::RUNS;
 using feat_move::u4;
 
-__global__ __launch_bounds__(NT) void batch_gather_kernel(const xggm_batch_gather_args a, const int adj_vec) {
+// LABELS: role 1 makes out_adj[b] from the image's label ids and the pair table (label_adjacency.h) instead of copying a
+// stored row; every other role and output is the same code.
+template <bool LABELS>
+__global__ __launch_bounds__(NT) void batch_gather_kernel(const xggm_batch_gather_args a, const int adj_vec, const xggm_label_adj_args l) {
     const int64_t b = blockIdx.y;
     const int64_t s = a.order[a.start + b];
     const int role = blockIdx.x, tid = threadIdx.x;
@@ -33,7 +37,13 @@ __global__ __launch_bounds__(NT) void batch_gather_kernel(const xggm_batch_gathe
         const u4* bs = reinterpret_cast<const u4*>(a.boxes) + row * a.N;
         u4* bd = reinterpret_cast<u4*>(a.out_boxes) + b * a.N;
         for (int i = tid; i < a.N; i += NT) bd[i] = bs[i];
-        if (a.out_adj) {
+        if constexpr (LABELS) {
+            if (a.out_adj) {  // uniform: no lane skips the helper's barriers
+                __shared__ label_adj::Smem sm;
+                label_adj::image<NT>(l.table, l.Vc, l.Va, l.obj_labels + row * a.N, l.attr_labels + row * a.N,
+                                     a.out_adj + b * a.N * a.N, a.N, sm);
+            }
+        } else if (a.out_adj) {
             const int nn = a.N * a.N;
             const float* as = a.adj + row * nn;
             float* ad = a.out_adj + b * nn;
@@ -72,11 +82,10 @@ __global__ __launch_bounds__(NT) void batch_gather_kernel(const xggm_batch_gathe
 }
 
 bool misaligned(const void* p, uintptr_t n) { return ((uintptr_t)p % n) != 0; }
-}  // namespace
 
-extern "C" int xggm_batch_gather(const xggm_batch_gather_args* args, hipStream_t st) {
-    const char* who = "xggm_batch_gather";
+int launch(const char* who, const xggm_batch_gather_args* args, const xggm_label_adj_args* lab, bool labels, hipStream_t st) {
     XGGM_REQUIRE(args, "%s: null argument struct", who);
+    XGGM_REQUIRE(!labels || lab, "%s: null label struct", who);
     const xggm_batch_gather_args& a = *args;
     XGGM_REQUIRE(a.B >= 1, "%s: B=%d, at least one row expected", who, a.B);
     XGGM_REQUIRE(a.T >= 1 && a.K >= 1 && a.A >= 1 && a.N >= 1 && a.F >= 1,
@@ -91,7 +100,16 @@ extern "C" int xggm_batch_gather(const xggm_batch_gather_args* args, hipStream_t
     XGGM_REQUIRE(a.feats && a.boxes && a.q_row && a.q_ids && a.q_len, "%s: null table (feats, boxes, q_row, q_ids, q_len)", who);
     XGGM_REQUIRE(a.out_feats && a.out_boxes && a.input_ids && a.input_mask && a.segment_ids,
                  "%s: null output (feats, boxes, input_ids, input_mask, segment_ids)", who);
-    XGGM_REQUIRE(!a.out_adj || a.adj, "%s: an adjacency output needs the adjacency table", who);
+    if (labels) {
+        XGGM_REQUIRE(!a.adj, "%s: a stored adjacency table beside the label tables (one source of adj_true only)", who);
+        XGGM_REQUIRE(lab->table && lab->obj_labels && lab->attr_labels, "%s: null label table (table, obj_labels, attr_labels)", who);
+        XGGM_REQUIRE(lab->Vc > 0 && lab->Va > 0, "%s: Vc=%d Va=%d labels, at least one of each expected", who, lab->Vc, lab->Va);
+        XGGM_REQUIRE(a.N <= label_adj::N_MAX, "%s: N = %d objects (1..%d with label tables)", who, a.N, label_adj::N_MAX);
+        XGGM_REQUIRE(!misaligned(lab->table, 4) && !misaligned(lab->obj_labels, 4) && !misaligned(lab->attr_labels, 4),
+                     "%s: a 4-byte label field is misaligned", who);
+    } else {
+        XGGM_REQUIRE(!a.out_adj || a.adj, "%s: an adjacency output needs the adjacency table", who);
+    }
     XGGM_REQUIRE(!a.target || (a.q_label && a.q_score), "%s: a target output needs q_label and q_score", who);
     XGGM_REQUIRE(!a.bias_index || a.q_bias_index, "%s: a bias_index output needs q_bias_index", who);
     XGGM_REQUIRE(!misaligned(a.feats, 16) && !misaligned(a.boxes, 16) && !misaligned(a.out_feats, 16) && !misaligned(a.out_boxes, 16),
@@ -109,6 +127,16 @@ extern "C" int xggm_batch_gather(const xggm_batch_gather_args* args, hipStream_t
     const int64_t runs = (int64_t)a.N * a.F / 8;
     const int adj_vec = a.out_adj && ((int64_t)a.N * a.N) % 4 == 0 && !misaligned(a.adj, 16) && !misaligned(a.out_adj, 16);
     const dim3 grid((unsigned)(2 + ceil_div64(runs, NT * RUNS)), (unsigned)a.B);
-    hipLaunchKernelGGL(batch_gather_kernel, grid, dim3(NT), 0, st, a, adj_vec);
+    if (labels) hipLaunchKernelGGL(batch_gather_kernel<true>, grid, dim3(NT), 0, st, a, adj_vec, *lab);
+    else hipLaunchKernelGGL(batch_gather_kernel<false>, grid, dim3(NT), 0, st, a, adj_vec, xggm_label_adj_args{});
     return xggm_check_launch(who);
+}
+}  // namespace
+
+extern "C" int xggm_batch_gather(const xggm_batch_gather_args* args, hipStream_t st) {
+    return launch("xggm_batch_gather", args, nullptr, false, st);
+}
+
+extern "C" int xggm_batch_gather_labels(const xggm_batch_gather_args* args, const xggm_label_adj_args* labels, hipStream_t st) {
+    return launch("xggm_batch_gather_labels", args, labels, true, st);
 }

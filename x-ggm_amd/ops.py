@@ -2539,6 +2539,12 @@ class BatchGatherArgs(_ct.Structure):
                 ("A", _ct.c_int), ("N", _ct.c_int), ("F", _ct.c_int), ("feats_f32", _ct.c_int), ("out_f32", _ct.c_int)]
 
 
+class LabelAdjArgs(_ct.Structure):
+    """mirror of ``xggm_label_adj_args`` (include/xggm.h)"""
+    _fields_ = [("table", _ct.c_void_p), ("obj_labels", _ct.c_void_p), ("attr_labels", _ct.c_void_p), ("Vc", _ct.c_int),
+                ("Va", _ct.c_int)]
+
+
 def _rows_of(t, B, row, name, who="batch_gather"):
     """``t``: at least B rows of shape ``row`` whose insides are contiguous (the row stride is free) -> row stride"""
     if t.dim() != 1 + len(row) or tuple(t.shape[1:]) != tuple(row) or t.shape[0] < B:
@@ -2552,7 +2558,9 @@ def batch_gather(tables, order, start, B, out):
     """rows ``order[start : start + B]`` of a device-resident split into the batch buffers ``out``, one launch; contract:
     xggm_batch_gather in xggm.h.  ``tables``: feats [n_img, N, F] bf16 / fp32, boxes [n_img, N, 4], adj [n_img, N, N] or None,
     q_row [n_q] int32, q_ids [n_q, T] int32, q_len [n_q] int32, q_label [n_q, K] int32, q_score [n_q, K] fp32, q_bias_index
-    [n_q] int64 or None.  ``order``: [n] int64.  ``out``: feats (bf16 / fp32; the row stride is free), boxes, input_ids,
+    [n_q] int64 or None.  Instead of adj a store may hold pair_table [Vc, Va] fp32 with obj_labels / attr_labels [n_img, N]
+    int32 (1 <= N <= 128, ids inside the table: validated by the store): adj_true is then made in the launch
+    (xggm_batch_gather_labels); both at once are refused.  ``order``: [n] int64.  ``out``: feats (bf16 / fp32; the row stride is free), boxes, input_ids,
     input_mask, segment_ids and any of adj_true, target (row stride free), bias_index, sample; each with at least B rows,
     rows past B are not touched.  The indices inside the tables are trusted (``tools.resident.ResidentDataset`` validates
     them once at upload); every shape is checked here."""
@@ -2577,6 +2585,19 @@ def batch_gather(tables, order, start, B, out):
         raise ValueError("batch_gather: adjacency table %s, [%d, %d, %d] expected" % (tuple(adj.shape), n_img, N, N))
     if bias is not None and tuple(_c(bias, torch.int64, "q_bias_index").shape) != (n_q,):
         raise ValueError("batch_gather: q_bias_index %s, [%d] expected" % (tuple(bias.shape), n_q))
+    pair = tb.get("pair_table")
+    if pair is not None:
+        if adj is not None:
+            raise ValueError("batch_gather: the tables hold a stored adjacency AND a pair table (one source of adj_true only)")
+        ol, al = tb.get("obj_labels"), tb.get("attr_labels")
+        if ol is None or al is None:
+            raise ValueError("batch_gather: a pair table needs the tables obj_labels and attr_labels")
+        if _c(pair, F32, "pair_table").dim() != 2 or min(pair.shape) < 1:
+            raise ValueError("batch_gather: pair table %s, [Vc, Va] expected" % (tuple(pair.shape),))
+        if tuple(_c(ol, torch.int32, "obj_labels").shape) != (n_img, N) or tuple(_c(al, torch.int32, "attr_labels").shape) != (n_img, N):
+            raise ValueError("batch_gather: label tables %s and %s, [%d, %d] expected" % (tuple(ol.shape), tuple(al.shape), n_img, N))
+        if N > 128:
+            raise ValueError("batch_gather: N=%d objects, the label adjacency serves 1 .. 128" % N)
     if min(n_img, n_q, N, F, T, K) < 1:
         raise ValueError("batch_gather: empty tables")
     if F % 8:
@@ -2597,7 +2618,7 @@ def batch_gather(tables, order, start, B, out):
         _rows_of(_c(out[k], torch.int64, "out " + k), B, (T,), "out " + k)
     oa, tg, ob, sm = out.get("adj_true"), out.get("target"), out.get("bias_index"), out.get("sample")
     if oa is not None:
-        if adj is None:
+        if adj is None and pair is None:
             raise ValueError("batch_gather: the tables hold no adjacency for out adj_true")
         _rows_of(_c(oa, F32, "out adj_true"), B, (N, N), "out adj_true")
     if tg is not None:
@@ -2624,7 +2645,12 @@ def batch_gather(tables, order, start, B, out):
     a.target, a.bias_index, a.sample = ptr(tg), ptr(ob), ptr(sm)
     a.B, a.T, a.K, a.N, a.F = B, T, K, N, F
     a.feats_f32, a.out_f32 = int(feats.dtype == F32), int(of.dtype == F32)
-    call("xggm_batch_gather", _ct.addressof(a), stream())
+    if pair is not None:
+        l = LabelAdjArgs()
+        l.table, l.obj_labels, l.attr_labels, l.Vc, l.Va = ptr(pair), ptr(tb["obj_labels"]), ptr(tb["attr_labels"]), pair.shape[0], pair.shape[1]
+        call("xggm_batch_gather_labels", _ct.addressof(a), _ct.addressof(l), stream())
+    else:
+        call("xggm_batch_gather", _ct.addressof(a), stream())
     return out
 
 

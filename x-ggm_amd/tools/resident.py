@@ -6,7 +6,9 @@ ship the image again -- and a producer thread tokenises and copies rows beside a
 The features of a split fit in HBM many times over (120 000 images: 17.7 GB of bf16), so ``ResidentDataset`` stores
 
     feats [n_img, N, F]   the shard's own storage type (bf16, or fp32 for a ``float32`` parity shard)
-    boxes [n_img, N, 4], adj [n_img, N, N]
+    boxes [n_img, N, 4], adj [n_img, N, N]       or, in place of adj: pair_table [Vc, Va] with obj_labels / attr_labels
+                                                  [n_img, N] int32 (``ObjTable.set_label_adjacency``): ``adj_true`` is
+                                                  then made in the gather launch and no per-image table exists
     q_row [n_q] int32     the image row of every sample: an image is stored ONCE however many questions refer to it
     q_ids [n_q, T] int32, q_len [n_q] int32       what ``SentenceBatcher`` would produce for the question
     q_label, q_score [n_q, K]                     the (label, score) pairs ``fill_target`` would write, -1 = unused slot
@@ -119,6 +121,9 @@ def gather_host(tables, indices, A, out_f32=False):
     out = dict(feats=feats, boxes=torch.from_numpy(np.array(tables["boxes"][rows], dtype=np.float32)))
     if tables.get("adj") is not None:
         out["adj_true"] = torch.from_numpy(np.array(tables["adj"][rows], dtype=np.float32))
+    elif tables.get("pair_table") is not None:  # a store without an [n_img, N, N] table: the label adjacency, restated
+        from ..preprocess.compute_adjacency import label_adjacency_host
+        out["adj_true"] = torch.from_numpy(label_adjacency_host(tables["pair_table"], tables["obj_labels"][rows], tables["attr_labels"][rows]))
     out["input_ids"] = torch.from_numpy(tables["q_ids"][idx].astype(np.int64))
     out["input_mask"] = torch.from_numpy((np.arange(T)[None, :] < tables["q_len"][idx][:, None]).astype(np.int64))
     out["segment_ids"] = torch.zeros((B, T), dtype=torch.int64)
@@ -221,6 +226,10 @@ class ResidentDataset:
             host["feats"] = sh.feats
         host["boxes"] = sh.boxes
         host["adj"] = sh.adj
+        if getattr(sh, "pair_table", None) is not None:  # ``ObjTable.set_label_adjacency``: adj_true made in the gather
+            if sh.adj is not None:
+                raise ValueError("ResidentDataset: the shard holds a materialised adjacency AND a pair table; one source of adj_true only")
+            host["pair_table"], host["obj_labels"], host["attr_labels"] = sh.pair_table, sh.obj_labels, sh.attr_labels
         self.host = host
         self.n, self.K = len(ts.data), host["q_label"].shape[1]
         self.nbytes = sum(int(v.numel() * v.element_size() if torch.is_tensor(v) else v.nbytes) for v in host.values() if v is not None)
@@ -286,7 +295,7 @@ class ResidentDataset:
                 raise ValueError("ResidentDataset.fill: out[%r] has rows of %s, the store holds N=%d F=%d T=%d A=%d"
                                  % (k, tuple(out[k].shape[1:]), self.N, self.F, self.T, self.A))
         sel = {k: out[k] for k in FIELDS if k in out}
-        if "adj_true" in sel and "adj" not in self.tables:
+        if "adj_true" in sel and "adj" not in self.tables and "pair_table" not in self.tables:
             raise ValueError("ResidentDataset.fill: the shard holds no adjacency")
         if "bias_index" in sel and "q_bias_index" not in self.tables:
             raise ValueError("ResidentDataset.fill: the store was built without bias_index")

@@ -212,7 +212,8 @@ def _torch_feats(bits_or_f32):
 class ObjTable:
     """the images of one feature file as the stores' tables.  Device tensors ``feats`` [n, N, F] (bf16 or fp32), ``boxes``
     [n, N, 4], ``obj_labels`` / ``attr_labels`` [n, N] int32, ``obj_confs`` / ``attr_confs`` [n, N] fp32, ``flags`` int32 [n]
-    (the bit patterns of xggm_tsv_decode's flags, or None) and, after ``set_adjacency``, ``adj`` [n, N, N] fp32.  Host:
+    (the bit patterns of xggm_tsv_decode's flags, or None) and, after ``set_adjacency``, ``adj`` [n, N, N] fp32 -- or, after
+    ``set_label_adjacency``, ``pair_table`` [Vc, Va] fp32 and no ``adj`` at all.  Host:
     ``ids`` (the img_id strings in row order), ``row_of``, ``img_h`` / ``img_w`` int64 [n], ``n``, ``N``, ``F``.  In place of a
     ``ShardReader`` it answers ``len``, ``row_of``, ``N``, ``F``, ``adj``, ``feats_f32(row)`` and ``boxes_of(row)``."""
 
@@ -224,6 +225,7 @@ class ObjTable:
         self.row_of = {i: r for r, i in enumerate(self.ids)}
         self.img_h, self.img_w = np.asarray(img_h, dtype=np.int64), np.asarray(img_w, dtype=np.int64)
         self.flags, self.adj, self.normalized, self.last_host_rows = flags, None, bool(normalized), 0
+        self.pair_table = None  # set_label_adjacency: the adjacency is made from the labels, no [n, N, N] table
         self.device = self.feats.device
         want = dict(feats=(self.n, self.N, self.F), boxes=(self.n, self.N, 4), obj_labels=(self.n, self.N), attr_labels=(self.n, self.N),
                     obj_confs=(self.n, self.N), attr_confs=(self.n, self.N))
@@ -243,7 +245,8 @@ class ObjTable:
 
     @property
     def nbytes(self):
-        return sum(int(t.numel() * t.element_size()) for t in list(self.tables().values()) + ([self.adj] if self.adj is not None else []))
+        extra = [t for t in (self.adj, self.pair_table) if t is not None]  # one of the two at most
+        return sum(int(t.numel() * t.element_size()) for t in list(self.tables().values()) + extra)
 
     def set_adjacency(self, adj):
         """``adj`` [n, N, N] fp32 on the table's device (``preprocess.build_adjacency(class_table, attr_table,
@@ -251,8 +254,36 @@ class ObjTable:
         if tuple(adj.shape) != (self.n, self.N, self.N) or adj.dtype != torch.float32 or adj.device != self.device:
             raise ValueError("ObjTable.set_adjacency: %s %s on %s, (%d, %d, %d) float32 on %s expected"
                              % (tuple(adj.shape), adj.dtype, adj.device, self.n, self.N, self.N, self.device))
+        if self.pair_table is not None:
+            raise ValueError("ObjTable.set_adjacency: the table makes its adjacency from labels (set_label_adjacency); one source only")
         self.adj = adj.contiguous()
         return self
+
+    def set_label_adjacency(self, pair_table):
+        """``pair_table`` [Vc, Va] fp32 on the table's device (``preprocess.compute_adjacency.label_pair_table``): ``adj``
+        stays None -- no [n, N, N] table exists -- and a ``ResidentDataset`` makes ``adj_true`` from ``obj_labels`` /
+        ``attr_labels`` inside the batch gather, bit-equal to the rows ``build_adjacency`` would have stored.  The ids are
+        range-checked here, once (one device min/max, one read-back): ValueError naming the range."""
+        from ..preprocess.compute_adjacency import check_label_range
+        if pair_table.dim() != 2 or pair_table.dtype != torch.float32 or pair_table.device != self.device:
+            raise ValueError("ObjTable.set_label_adjacency: %s %s on %s, [Vc, Va] float32 on %s expected"
+                             % (tuple(pair_table.shape), pair_table.dtype, pair_table.device, self.device))
+        if self.adj is not None:
+            raise ValueError("ObjTable.set_label_adjacency: the table holds a materialised adjacency (set_adjacency); one source only")
+        if not 1 <= self.N <= 128:
+            raise ValueError("ObjTable.set_label_adjacency: %d objects, the label adjacency serves 1 .. 128" % self.N)
+        check_label_range(pair_table, self.obj_labels, self.attr_labels, "ObjTable.set_label_adjacency")
+        self.pair_table = pair_table.contiguous()
+        return self
+
+    def adj_of(self, row):
+        """adjacency of one image, fp32 numpy [N, N], read back: the stored row, or the one the gather would make"""
+        if self.adj is not None:
+            return self.adj[row].cpu().numpy()
+        if self.pair_table is None:
+            raise ValueError("ObjTable: the table holds no adjacency (set_adjacency / set_label_adjacency)")
+        from ..preprocess.compute_adjacency import build_adjacency_from_labels
+        return build_adjacency_from_labels(self.pair_table, self.obj_labels[row:row + 1], self.attr_labels[row:row + 1], check=False)[0].cpu().numpy()
 
     def feats_f32(self, row):
         """features of one image as fp32 numpy (the stored values), read back: for inspection"""

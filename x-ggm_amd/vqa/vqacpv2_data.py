@@ -60,7 +60,7 @@ class VQATorchDataset(Dataset):
     benchmark dtype), so ``__getitem__`` returns the bf16-ROUNDED values as fp32 -- a parity run in fp32 execution
     that wants the reference's exact fp32 inputs writes its shard with ``ShardWriter(..., feat_dtype="float32")``.
     ``shard`` may also be a ``tools.tsv.ObjTable``: a feature file decoded on the device (with ``set_adjacency`` for the
-    adjacency).  ``ResidentDataset`` then adopts its tensors; ``__getitem__`` reads one row back, for inspection; ``collate``
+    adjacency, or ``set_label_adjacency`` for one made from the labels).  ``ResidentDataset`` then adopts its tensors; ``__getitem__`` reads one row back, for inspection; ``collate``
     is refused: a device table does not feed the host loader."""
 
     def __init__(self, dataset, shard=None, imgfeat_root=MSCOCO_IMGFEAT_ROOT, tiny=False, fast=False):
@@ -96,7 +96,7 @@ class VQATorchDataset(Dataset):
         boxes = self.shard.boxes_of(row) if on_device else np.array(self.shard.boxes[row])
         ques_id, ques = datum['question_id'], datum[self.raw_dataset.sent_key]
         if 'label' in datum:
-            adj = self.shard.adj[row].cpu().numpy() if on_device else np.array(self.shard.adj[row])
+            adj = self.shard.adj_of(row) if on_device else np.array(self.shard.adj[row])
             return ques_id, feats, boxes, ques, self.target_of(datum), adj
         return ques_id, feats, boxes, ques
 
