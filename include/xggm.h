@@ -165,7 +165,7 @@ int xggm_gemm_grouped_fp8e4m3(const xggm_gemm_problem* probs, int n, int tile, x
  *   m == 0, shrink != 0, history just wrapped: qscale[i] *= 2   (nothing near the range for hist_len calls)
  *   dscale[i] = 1 / qscale[i];   bump != 0: *pos += 1.
  * Activation sites: once per pass, margin 1.25, shrink, bump.  Weight operands: for the parameter groups a pass
- * updates, BEFORE xggm_bertadam_ex writes their e4m3 copies with the new scale (margin 4/3, no shrink, no bump).
+ * updates, BEFORE xggm_optim_multi writes their e4m3 copies with the new scale (margin 4/3, no shrink, no bump).
  * Everything is device-resident (graph replay); n <= 1024.  `amax_slots` (power of two <= 64, 0 = 1): entry i's maximum
  * is the largest of amax[i * amax_slots .. + amax_slots - 1] (all cleared). */
 int xggm_fp8_scale_update(float* amax, float* hist, float* qscale, float* dscale, int64_t* pos, int n, int hist_len,
@@ -1124,12 +1124,18 @@ int xggm_sqnorm_f32(const float* g, int64_t n, float* out, float* ws, xggm_strea
  * accumulate = !overwrite. */
 int xggm_sqnorm_multi_f32(const float* base, const int64_t* offsets, const int64_t* lengths, int n, float* out, float* norm,
                           float* ws, int overwrite, int square, float mul, xggm_stream_t stream);
-/* BertAdam.step (src/lxrt/optimization.py:159-193) fused with the clip scale
- * min(1, max_norm/(sqrt(*sqnorm)+1e-6)) and the bf16 shadow-weight write. */
-int xggm_bertadam_f32(float* p, const float* g, float* m, float* v, void* shadow_bf16, int64_t n, const float* sqnorm,
-                      float max_norm, float lr, const float* lr_scale, float b1, float b2, float eps, float weight_decay,
-                      xggm_stream_t stream);
-/* The same update with everything a deployment variant needs, as one argument block (HOST struct, copied):
+/* xggm_sqnorm_f32 over a bf16 buffer (the data-parallel wire arena) */
+int xggm_sqnorm_bf16(const void* g, int64_t n, float* out, float* ws, xggm_stream_t stream);
+/* *lr_scale = warmup_linear(*step / t_total, warmup); *step += 1 (optimization.py:42-48) */
+int xggm_sched_step(int64_t* step, float* lr_scale, int64_t t_total, float warmup, xggm_stream_t stream);
+/* the same for n <= 16 distinct counters steps[index[i]] / lr_scale[index[i]] of one table in one launch (all
+ * parameter groups of one optimiser step); index, t_total, warmup: HOST arrays of n entries */
+int xggm_sched_step_multi(int64_t* steps, float* lr_scale, const int* index, const int64_t* t_total, const float* warmup,
+                          int n, xggm_stream_t stream);
+
+/* The fused optimiser update: ONE entry for every rule.  A span is BertAdam.step (src/lxrt/optimization.py:159-193) or a
+ * torch.optim rule on a contiguous range, fused with the clip scale min(1, max_norm / (sqrt(*sqnorm) + 1e-6)) and the
+ * bf16 shadow-weight write, with everything a deployment variant needs in one argument block (HOST struct, copied):
  *  - g_bf16 != 0: `g` holds bf16 gradients (the data-parallel wire arena the weight-gradient GEMMs write and
  *    RCCL reduces in place: no fp32 copy of the matrix gradients exists);
  *  - lr_dev (or NULL): device scalar that replaces `lr` (edits of param_groups[i]['lr'] reach replayed graphs);
@@ -1137,7 +1143,8 @@ int xggm_bertadam_f32(float* p, const float* g, float* m, float* v, void* shadow
  *    Per-tensor scales: w8_id[(elem0 + i) >> 8] (uint16 per 256-element chunk of the arena, 0 = this chunk has no
  *    e4m3 copy) selects the entry of w8_qscale the value is multiplied by, and w8_amax[id] is raised to max |p_new|
  *    for the next scale update (xggm_fp8_scale_update).  `elem0`: arena offset of p[0], a multiple of 256 when
- *    shadow8 is given. */
+ *    shadow8 is given.
+ * p, m, v are 16-byte aligned, g too (bf16: 8), the shadow 8. */
 typedef struct xggm_adam_args {
     float* p;
     const void* g;
@@ -1161,20 +1168,6 @@ typedef struct xggm_adam_args {
                       and the average is taken here); <= 0 reads as 1 */
     int w8_amax_slots; /* entry id of w8_amax starts at w8_amax[id * max(1, w8_amax_slots)]; see xggm_gemm_problem.amax_slots */
 } xggm_adam_args;
-int xggm_bertadam_ex(const xggm_adam_args* args, xggm_stream_t stream);
-/* the same update for n spans (HOST array; every arena group a pass updates, or a rank's slices of them under the sharded
- * update) in ONE launch: src/lxrt/optimization.py:159-193 loops over param_groups, each span carries its own group's
- * lr / schedule value / weight decay.  All spans of a call share the gradient type (g_bf16). */
-int xggm_bertadam_multi(const xggm_adam_args* args, int n, xggm_stream_t stream);
-/* xggm_sqnorm_f32 over a bf16 buffer (the data-parallel wire arena) */
-int xggm_sqnorm_bf16(const void* g, int64_t n, float* out, float* ws, xggm_stream_t stream);
-/* *lr_scale = warmup_linear(*step / t_total, warmup); *step += 1 (optimization.py:42-48) */
-int xggm_sched_step(int64_t* step, float* lr_scale, int64_t t_total, float warmup, xggm_stream_t stream);
-/* the same for n <= 16 distinct counters steps[index[i]] / lr_scale[index[i]] of one table in one launch (all
- * parameter groups of one optimiser step); index, t_total, warmup: HOST arrays of n entries */
-int xggm_sched_step_multi(int64_t* steps, float* lr_scale, const int* index, const int64_t* t_total, const float* warmup,
-                          int n, xggm_stream_t stream);
-
 /* The reference's other optimisers (src/param.py:9-31 binds --optim rms|adam|adamw|adamax|sgd to torch.optim classes,
  * src/vqa/vqacpv2.py:141 builds args.optimizer(self.model.parameters(), args.lr)) on the same fused pass as BertAdam:
  * clip scale, update, bf16 shadow, n & 3 tail, spans through a prefix table.  torch's single-tensor semantics with
@@ -1186,12 +1179,12 @@ int xggm_sched_step_multi(int64_t* steps, float* lr_scale, const int* index, con
  *            momentum * m + (1 - dampening) g' after it; p -= lr * (nesterov ? g' + momentum * m : m)
  *   RMSPROP  v = alpha v + (1 - alpha) g'^2; d = g' / (sqrt(v) + eps); momentum == 0: p -= lr d (m untouched), else
  *            m = momentum * m + d; p -= lr m
- * `a` holds the span as for xggm_bertadam_multi (a.b1 / a.b2 are ignored for these rules, a.shadow8 must be NULL; a.eps
- * and a.weight_decay are used).  The complements 1 - b1, 1 - b2, 1 - dampening, 1 - alpha are taken in DOUBLE on the host
+ * `a` holds the span (for the torch rules a.b1 / a.b2 are ignored, a.shadow8 must be NULL; a.eps and a.weight_decay are
+ * used).  The complements 1 - b1, 1 - b2, 1 - dampening, 1 - alpha are taken in DOUBLE on the host
  * (fp32 1 - 0.999f is off by 1.3e-5 relative).  bc = 1 - b^t comes from `step_scalars`: three device floats {1 / bc1,
  * 1 / sqrt(bc2), first-step flag} that xggm_sched_step_ex computed in double from the device-resident step counter
  * (required for ADAM / ADAMW / ADAMAX and for SGD with momentum; NULL elsewhere).
- * XGGM_RULE_BERTADAM runs xggm_bertadam_multi's kernel on `a` alone. */
+ * XGGM_RULE_BERTADAM is BertAdam on `a` alone: the rule fields are zero and not read. */
 #define XGGM_RULE_BERTADAM 0
 #define XGGM_RULE_ADAM 1
 #define XGGM_RULE_ADAMW 2
@@ -1208,30 +1201,29 @@ typedef struct xggm_optim_args {
     double alpha;              /* RMSPROP */
     int nesterov;              /* SGD */
 } xggm_optim_args;
-/* n spans (HOST array) in one launch per 8 spans; all spans share rule, gradient type and whether momentum is zero
- * (src/param.py:9-31, src/vqa/vqacpv2.py:141) */
-int xggm_optim_multi(const xggm_optim_args* args, int n, xggm_stream_t stream);
 
-/* Split param_groups: the two multi-span updates with lr and weight decay PER TENSOR, for an optimiser whose param_groups cut
+/* Split param_groups (`map`, or NULL): lr and weight decay PER TENSOR, for an optimiser whose param_groups cut
  * through a contiguous range (the BERT "no decay for bias / LayerNorm" grouping, layer-wise lr decay, parameters left out).
  *   ids    DEVICE, one uint8 per 8 elements of the arena: element i of a span reads ids[(elem0 + i) >> 3].  Tensors start on
  *          multiples of 8 elements, so 8 elements never mix two tensors: 1/8 byte of map per parameter.
  *   table  DEVICE, n_table pairs {lr, weight_decay}, 8-byte aligned; entry 0 is not read.
  * Per element: lr = table[id].lr * *lr_scale and weight_decay = table[id].weight_decay take the place of the span's lr /
  * lr_dev / weight_decay (which are not read); the schedule value, the clip scale, g_scale, the rule's arguments, the bf16
- * shadow and the e4m3 copy are the span's, and the arithmetic is xggm_bertadam_multi's / xggm_optim_multi's bit for bit.
+ * shadow and the e4m3 copy are the span's, and the arithmetic is the unmapped update's bit for bit.
  * Id 0 (and any id >= n_table) means "not in this optimiser": p, m, v, the shadow and the e4m3 copy of such an element are
- * not written.  Alignment gaps hold zeros and may carry any id.  Checked before any launch: map, ids and table non-NULL,
- * 1 <= n_table <= 256, every span's elem0 a multiple of 8 and [elem0, elem0 + n) inside the n_ids * 8 elements the map covers.
- * One launch per 8 spans, no atomics beyond the e4m3 maxima, no allocation, no synchronisation. */
+ * not written.  Alignment gaps hold zeros and may carry any id.  Checked with a map: ids and table non-NULL,
+ * 1 <= n_table <= 256, every span's elem0 a multiple of 8 and [elem0, elem0 + n) inside the n_ids * 8 elements the map covers. */
 typedef struct xggm_hyper_map {
     const uint8_t* ids;
     int64_t n_ids;
     const float* table;
     int n_table;
 } xggm_hyper_map;
-int xggm_bertadam_multi_mapped(const xggm_adam_args* args, int n, const xggm_hyper_map* map, xggm_stream_t stream);
-int xggm_optim_multi_mapped(const xggm_optim_args* args, int n, const xggm_hyper_map* map, xggm_stream_t stream);
+/* n spans (HOST array: every arena group a pass updates, or a rank's slices of them under the sharded update), one launch
+ * per 8 spans; all spans share rule, gradient type and whether momentum is zero (src/param.py:9-31,
+ * src/vqa/vqacpv2.py:141).  The map and every span are checked before any launch.  No atomics beyond the e4m3 maxima, no
+ * allocation, no synchronisation. */
+int xggm_optim_multi(const xggm_optim_args* args, int n, const xggm_hyper_map* map /* or NULL */, xggm_stream_t stream);
 
 /* xggm_sched_step_multi with a schedule kind per entry (src/lxrt/optimization.py:27-48: warmup_cosine, warmup_constant,
  * warmup_linear; the xggm_sched_step* calls keep meaning warmup_linear) and the per-step scalars of xggm_optim_multi:

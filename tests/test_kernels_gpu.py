@@ -776,7 +776,8 @@ def test_bertadam_against_golden(ops):
             G[:n] = torch.from_numpy(g["adam_g%s" % key][s]).view(-1)
             ops.sched_step(step, lr_scale, 10, 0.1)
             assert abs(float(lr_scale) - O.warmup_linear(s / 10, 0.1)) < 1e-6
-            ops.bertadam(P[:n], G[:n], M[:n], V[:n], shadow[:n], None, 5.0, lr, lr_scale, 0.9, 0.999, 1e-6, 0.01)
+            ops.optim_multi("bertadam", [((P[:n], G[:n], M[:n], V[:n], shadow[:n], None, 5.0, lr, lr_scale, 0.9, 0.999, 1e-6, 0.01),
+                                          {}, {})])
             assert rel_err(P[:n], torch.from_numpy(g["adam_p%s" % key][s]).view(-1)) < 1e-6
             assert rel_err(shadow[:n].float(), P[:n]) < 4e-3
         assert int(step) == 6
@@ -805,7 +806,7 @@ def test_sqnorm_and_clip(ops):
     sq = torch.zeros(1, device=DEV)
     ops.sqnorm(G, sq)
     m, v = torch.zeros(8, device=DEV), torch.zeros(8, device=DEV)
-    ops.bertadam(p, G, m, v, None, sq, 5.0, 0.1, None, 0.9, 0.999, 1e-6, 0.0)
+    ops.optim_multi("bertadam", [((p, G, m, v, None, sq, 5.0, 0.1, None, 0.9, 0.999, 1e-6, 0.0), {}, {})])
     gc = 100.0 * 5.0 / (math.sqrt(8 * 100.0 ** 2) + 1e-6)
     mm, vv = 0.1 * gc, 0.001 * gc * gc
     assert abs(float(p[0]) - (1 - 0.1 * mm / (math.sqrt(vv) + 1e-6))) < 1e-5
@@ -1376,8 +1377,9 @@ def test_producers_emit_e4m3_copies(ops):
     assert (float(amax) > 0) == (m > 0.5 * 448 / 100) and (float(amax) == 0 or float(amax) == m)
 
 
-def test_bertadam_ex_writes_e4m3_shadow_and_reads_bf16_gradients(ops):
-    """xggm_bertadam_ex against xggm_bertadam_f32 on the same state: identical p / m / v / bf16 shadow; the e4m3 copy
+def test_bertadam_writes_e4m3_shadow_and_reads_bf16_gradients(ops):
+    """one BertAdam span of xggm_optim_multi with lr_dev / the e4m3 copy / bf16 gradients against the plain span on the
+    same state: identical p / m / v / bf16 shadow; the e4m3 copy
     equals the quantised new weights chunk by chunk with the table's scales, chunks with id 0 stay untouched, maxima
     beyond 3/4 of an entry's range are recorded; bf16 gradients give the update of their fp32 values; the learning
     rate can come from a device scalar."""
@@ -1393,8 +1395,11 @@ def test_bertadam_ex_writes_e4m3_shadow_and_reads_bf16_gradients(ops):
     def state():
         return p0.clone(), m0.clone(), v0.clone(), torch.zeros(n, device=DEV, dtype=torch.bfloat16)
 
+    def bertadam(*a, **kw):
+        ops.optim_multi("bertadam", [(a, kw, {})])
+
     pa, ma, va, sa = state()
-    ops.bertadam(pa, gr, ma, va, sa, sq, 5.0, 1e-2, lr_scale, 0.9, 0.999, 1e-6, 0.01)
+    bertadam(pa, gr, ma, va, sa, sq, 5.0, 1e-2, lr_scale, 0.9, 0.999, 1e-6, 0.01)
     # e4m3 copy: chunks 0-9 entry 1, 10-19 none, 20-39 entry 2; the range starts at arena element 256 * 7
     ids = torch.zeros(64, dtype=torch.int16, device=DEV)
     ids[7:17] = 1
@@ -1404,8 +1409,8 @@ def test_bertadam_ex_writes_e4m3_shadow_and_reads_bf16_gradients(ops):
     amax = torch.zeros(3, device=DEV)
     s8 = torch.full((n,), 0x55, dtype=torch.uint8, device=DEV)
     pb, mb, vb, sb = state()
-    ops.bertadam_ex(pb, gr, mb, vb, sb, sq, 5.0, 123.0, lr_scale, 0.9, 0.999, 1e-6, 0.01,
-                    lr_dev=torch.tensor([1e-2], device=DEV), w8=(s8, ids, qtab, amax), elem0=256 * 7)
+    bertadam(pb, gr, mb, vb, sb, sq, 5.0, 123.0, lr_scale, 0.9, 0.999, 1e-6, 0.01,
+             lr_dev=torch.tensor([1e-2], device=DEV), w8=(s8, ids, qtab, amax), elem0=256 * 7)
     assert torch.equal(pa, pb) and torch.equal(ma, mb) and torch.equal(va, vb) and torch.equal(sa, sb)
     assert torch.equal(s8[:2560].cpu(), _e4m3(pb[:2560], float(qtab[1])).cpu())
     assert bool((s8[2560:5120] == 0x55).all())
@@ -1415,9 +1420,9 @@ def test_bertadam_ex_writes_e4m3_shadow_and_reads_bf16_gradients(ops):
     # bf16 gradients
     gb = gr.to(torch.bfloat16)
     pc, mc, vc, sc = state()
-    ops.bertadam(pc, gb.float(), mc, vc, sc, sq, 5.0, 1e-2, lr_scale, 0.9, 0.999, 1e-6, 0.01)
+    bertadam(pc, gb.float(), mc, vc, sc, sq, 5.0, 1e-2, lr_scale, 0.9, 0.999, 1e-6, 0.01)
     pd, md, vd, sd = state()
-    ops.bertadam_ex(pd, gb, md, vd, sd, sq, 5.0, 1e-2, lr_scale, 0.9, 0.999, 1e-6, 0.01)
+    bertadam(pd, gb, md, vd, sd, sq, 5.0, 1e-2, lr_scale, 0.9, 0.999, 1e-6, 0.01)
     assert torch.equal(pc, pd) and torch.equal(mc, md) and torch.equal(vc, vd) and torch.equal(sc, sd)
     # squared norm of a bf16 buffer
     out = torch.zeros(1, device=DEV)

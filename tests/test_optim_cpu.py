@@ -85,13 +85,13 @@ def test_struct_mirrors_have_the_c_layout():
 def test_null_or_empty_argument_block_is_rejected_before_any_launch():
     from xggm_amd import ops
     lib = _lib.lib
-    assert lib.xggm_optim_multi(None, 1, None) != 0 and "no spans" in _lib.last_error()
+    assert lib.xggm_optim_multi(None, 1, None, None) != 0 and "no spans" in _lib.last_error()
     arr = (ops.OptimArgs * 1)()
-    assert lib.xggm_optim_multi(ctypes.cast(arr, ctypes.c_void_p), 0, None) != 0
-    assert lib.xggm_optim_multi(ctypes.cast(arr, ctypes.c_void_p), 1, None) != 0  # null p / g / m / v, n = 0
+    assert lib.xggm_optim_multi(ctypes.cast(arr, ctypes.c_void_p), 0, None, None) != 0
+    assert lib.xggm_optim_multi(ctypes.cast(arr, ctypes.c_void_p), 1, None, None) != 0  # null p / g / m / v, n = 0
     assert "bad arguments" in _lib.last_error()
     arr[0].rule = 17
-    assert lib.xggm_optim_multi(ctypes.cast(arr, ctypes.c_void_p), 1, None) != 0 and "unknown rule" in _lib.last_error()
+    assert lib.xggm_optim_multi(ctypes.cast(arr, ctypes.c_void_p), 1, None, None) != 0 and "unknown rule" in _lib.last_error()
     ent = (ops.SchedEntry * 1)()
     assert lib.xggm_sched_step_ex(None, None, None, ctypes.cast(ent, ctypes.c_void_p), 1, None) != 0
     assert "bad arguments" in _lib.last_error()

@@ -273,6 +273,34 @@ def test_zeros_stay_zeros(name):
             assert torch.equal(f.v, zero)
 
 
+# ------------------------------------------------------------------------------------------- bits of a recorded commit
+def _golden():
+    import importlib.util
+    import json
+    import os
+    here = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+    spec = importlib.util.spec_from_file_location("make_optim_update_golden", os.path.join(here, "make_optim_update_golden.py"))
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    with open(os.path.join(here, "optim_update_bits.json")) as f:
+        return gen, json.load(f)
+
+
+GOLDEN_GEN, GOLDEN = _golden()
+
+
+@pytest.mark.parametrize("case", GOLDEN_GEN.cases(), ids=lambda c: c[0])
+def test_update_bits_equal_the_recorded_commit(case):
+    """three steps over nine spans (two launches) per rule, gradient type, with and without a hyper map, BertAdam also with
+    the e4m3 copy + lr_dev + g_scale: SHA-256 of p, m, v, the bf16 shadow, the e4m3 copy and the amax table after every
+    step equal the digests tests/golden/make_optim_update_golden.py recorded with the library of GOLDEN["commit"]"""
+    from xggm_amd import ops
+    cid, key, gdt, mapped, extra = case
+    assert sorted(GOLDEN["cases"]) == sorted(c[0] for c in GOLDEN_GEN.cases())
+    got = GOLDEN_GEN.run_case(ops, key, gdt, mapped, extra)
+    assert got == GOLDEN["cases"][cid], (cid, [k for k in got if got[k] != GOLDEN["cases"][cid][k]])
+
+
 # ------------------------------------------------------------------------------------------------------------- schedules
 @pytest.mark.parametrize("warmup", [0.1, 0.35])
 @pytest.mark.parametrize("kind", ["warmup_cosine", "warmup_constant", "warmup_linear"])

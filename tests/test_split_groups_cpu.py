@@ -152,8 +152,8 @@ def _fake_map(ids=0x1000, n_ids=4, table=0x2000, n_table=2):
 
 def test_new_symbols_are_declared_and_exported():
     decl = _lib.parse_header()
-    for name in ("xggm_bertadam_multi_mapped", "xggm_optim_multi_mapped"):
-        assert name in decl and hasattr(_lib.lib, name) and len(decl[name]) == 4
+    name = "xggm_optim_multi"  # the map is an argument of the one update entry
+    assert name in decl and hasattr(_lib.lib, name) and len(decl[name]) == 4
     assert "xggm_hyper_map" in open(_lib.HEADER_PATH).read()
     assert _lib.lib.xggm_version() == 100
 
@@ -165,15 +165,17 @@ def test_struct_mirrors_keep_their_layout():
     assert ops.HYPER_MAP_ELEMS == arena.ALIGN and ops.HYPER_MAP_MAX_ID == arena.HYPER_MAX_ID
 
 
-@pytest.mark.parametrize("sym", ["xggm_bertadam_multi_mapped", "xggm_optim_multi_mapped"])
-def test_argument_checks_come_before_any_launch(sym):
+@pytest.mark.parametrize("rule", ["bertadam", "adam"])
+def test_argument_checks_come_before_any_launch(rule):
     """no GPU here: every call below has to return non-zero with a message from the host-side checks"""
     from xggm_amd import ops
-    fn = getattr(_lib.lib, sym)
-    arr = ((ops.AdamArgs if "bertadam" in sym else ops.OptimArgs) * 1)()
-    span = arr[0] if "bertadam" in sym else arr[0].a
+    fn = _lib.lib.xggm_optim_multi
+    arr = (ops.OptimArgs * 1)()
+    arr[0].rule = ops.RULES[rule]
+    span = arr[0].a
     pa, ok = ctypes.cast(arr, ctypes.c_void_p), _fake_map()
-    assert fn(pa, 1, None, None) != 0 and "no hyper map" in _lib.last_error()
+    # (no map is the unmapped update: the span itself is looked at)
+    assert fn(pa, 1, None, None) != 0 and "bad arguments" in _lib.last_error()
     assert fn(None, 1, ctypes.byref(ok), None) != 0 and "no spans" in _lib.last_error()
     assert fn(pa, 1, ctypes.byref(_fake_map(ids=None)), None) != 0 and "id map" in _lib.last_error()
     assert fn(pa, 1, ctypes.byref(_fake_map(table=None)), None) != 0 and "table" in _lib.last_error()

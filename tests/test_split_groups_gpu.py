@@ -104,10 +104,7 @@ class Flat:
 
     def launch(self, rule, jobs, hyper_map=None):
         from xggm_amd import ops
-        if rule == "bertadam":
-            ops.bertadam_multi([(a, kw) for a, kw, _ in jobs], hyper_map=hyper_map)
-        else:
-            ops.optim_multi(rule, jobs, hyper_map=hyper_map)
+        ops.optim_multi(rule, jobs, hyper_map=hyper_map)
 
 
 def _start(seed=7):
@@ -146,12 +143,7 @@ def test_one_mapped_launch_equals_per_tensor_launches(key, gdtype):
             f.sched(hp)
         fa.launch(rule, [fa.job(OFFS[0], END, hp, 123.0, 456.0)], hyper_map=(ids, table))  # (the span's own lr / wd: not read)
         for i in owned:
-            j = fb.job(OFFS[i], OFFS[i] + SIZES[i], hp, LRS[OWNER[i]], WDS[OWNER[i]])
-            if rule == "bertadam":
-                from xggm_amd import ops
-                ops.bertadam_ex(*j[0])
-            else:
-                fb.launch(rule, [j])
+            fb.launch(rule, [fb.job(OFFS[i], OFFS[i] + SIZES[i], hp, LRS[OWNER[i]], WDS[OWNER[i]])])
         for k in ("p", "m", "v", "shadow"):
             for i, (x, y) in zip(owned, zip(fa.views(getattr(fa, k), owned), fb.views(getattr(fb, k), owned))):
                 assert torch.equal(x, y), (key, k, "step %d" % s, "tensor %d (%d elements)" % (i, SIZES[i]))

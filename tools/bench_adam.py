@@ -13,7 +13,8 @@ def main():
     v.abs_()
     sh = torch.empty(n, device="cuda", dtype=torch.bfloat16)
     sqn = torch.ones(1, device="cuda")
-    t = timeit(lambda: ops.bertadam(p, g, m, v, sh, sqn, 5.0, 1e-5, None, 0.9, 0.999, 1e-6, 0.01), n=5)
+    job = ((p, g, m, v, sh, sqn, 5.0, 1e-5, None, 0.9, 0.999, 1e-6, 0.01), {}, {})
+    t = timeit(lambda: ops.optim_multi("bertadam", [job]), n=5)
     print("variant %s grid %s: %.1f us, %.0f GB/s" % (os.environ.get("XGGM_ADAM_VARIANT", "0"), os.environ.get("XGGM_ADAM_GRID", "4096"),
                                                   t * 1e6, 30.0 * n / t / 1e9), flush=True)
     t = timeit(lambda: ops.sqnorm(g, sqn) if hasattr(ops, "sqnorm") else None, n=5)

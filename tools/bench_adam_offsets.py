@@ -23,7 +23,8 @@ def main():
         for t in (p, g, m):
             t.normal_(0, 0.01)
         v.uniform_(0, 1e-4)
-        t = timeit(lambda: ops.bertadam(p, g, m, v, sh, sqn, 5.0, 1e-5, None, 0.9, 0.999, 1e-6, 0.01), n=4)
+        job = ((p, g, m, v, sh, sqn, 5.0, 1e-5, None, 0.9, 0.999, 1e-6, 0.01), {}, {})
+        t = timeit(lambda: ops.optim_multi("bertadam", [job]), n=4)
         print("stagger %9d B: %.1f us, %.0f GB/s" % (stagger, t * 1e6, 30.0 * n / t / 1e9), flush=True)
 
 

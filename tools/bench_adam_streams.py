@@ -37,7 +37,7 @@ def main():
     sc = torch.ones(1, device="cuda")
     lr = torch.full((1,), 1e-5, device="cuda")
     for name, g, bytes_ in (("fp32 gradients", g32, 30.0), ("bf16 gradients", g16, 28.0)):
-        t = timeit(lambda: ops.bertadam_multi([((p, g, m, v, sh, sqn, 5.0, 1e-5, sc, 0.9, 0.999, 1e-6, 0.01), dict(lr_dev=lr))]))
+        t = timeit(lambda: ops.optim_multi("bertadam", [((p, g, m, v, sh, sqn, 5.0, 1e-5, sc, 0.9, 0.999, 1e-6, 0.01), dict(lr_dev=lr), {})]))
         print("%s: %.1f us, %.2f TB/s (%d B per parameter)" % (name, t * 1e6, bytes_ * n / t / 1e12, bytes_), flush=True)
     # the same with the gradient stream alone / without it: what each stream costs
     t = timeit(lambda: ops.sqnorm_multi(g32, [(0, n)], sqn))

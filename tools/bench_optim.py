@@ -1,4 +1,4 @@
-"""Launch time of every update rule of ``xggm_optim_multi`` beside BertAdam's on an arena-sized vector (110 M
+"""Launch time of every update rule of ``xggm_optim_multi``, BertAdam first, on an arena-sized vector (110 M
 parameters, as tools/bench_adam.py): warm-up, then ROUNDS rounds that alternate the rules, each timed with events over
 REPS launches; the median over the rounds is printed with the rule's bytes per parameter."""
 import os
@@ -29,10 +29,7 @@ def main():
 
     def launch(rule, kw):
         a = (p, g, m, v, sh, sqn, 5.0, 1e-5, sc, 0.9, 0.999, 1e-6 if rule == "bertadam" else 1e-8, 0.01)
-        if rule == "bertadam":
-            ops.bertadam_multi([(a, {})])
-        else:
-            ops.optim_multi(rule, [(a, {}, dict(kw, step_scalars=hs))])
+        ops.optim_multi(rule, [(a, {}, {} if rule == "bertadam" else dict(kw, step_scalars=hs))])
 
     times = {i: [] for i in range(len(RULES))}
     for r in range(ROUNDS + 1):

@@ -48,8 +48,9 @@ def main():
         i += 1
     ids = torch.from_numpy(arena.hyper_id_map(info, owner, n)).to(dev)
     table = torch.tensor([[0.0, 0.0]] + [[1e-5 * (1 + j), 0.01 * (j % 2)] for j in range(a.groups)], device=dev)
-    job = ((p, g, m, v, sh, sq, 5.0, 1e-5, scale, 0.9, 0.999, 1e-6, 0.01), dict(elem0=0))
-    run = {"unmapped": lambda: ops.bertadam_multi([job]), "mapped": lambda: ops.bertadam_multi([job], hyper_map=(ids, table))}
+    job = ((p, g, m, v, sh, sq, 5.0, 1e-5, scale, 0.9, 0.999, 1e-6, 0.01), dict(elem0=0), {})
+    run = {"unmapped": lambda: ops.optim_multi("bertadam", [job]),
+           "mapped": lambda: ops.optim_multi("bertadam", [job], hyper_map=(ids, table))}
     for f in run.values():  # warm-up: code objects, clocks
         for _ in range(3):
             f()

@@ -3,11 +3,11 @@
 //   xggm_symkl_fwd/bwd      symmetric KL of row softmaxes (src/vqa/vqacpv2.py:54-61)
 //   xggm_bce_fwd/bwd        BCEWithLogits(mean) * A   (src/vqa/vqacpv2.py:131,173)
 //   xggm_sqnorm_* / xggm_clip_norm_*  sum of squares of gradient ranges in a fixed order (clip_grad_norm_, vqacpv2.py:175)
-//   xggm_bertadam_f32       clip-scale + BertAdam update + bf16 shadow weight, ONE pass over
+//   xggm_optim_multi        clip-scale + BertAdam update + bf16 shadow weight, ONE pass over
 //                           p/g/m/v (src/lxrt/optimization.py:159-193): 16 B read + 12(+2) B
-//                           written per parameter, the HBM floor of the update.
+//                           written per parameter, the HBM floor of the update; the same pass for
+//                           torch.optim's Adam / AdamW / Adamax / SGD / RMSprop rules (src/param.py:9-31)
 //   xggm_sched_step         warmup_linear(step/t_total) on the device-resident step counter
-//   xggm_optim_multi        the same pass for torch.optim's Adam / AdamW / Adamax / SGD / RMSprop rules (src/param.py:9-31)
 //   xggm_sched_step_ex      schedule kinds per entry + bias corrections in double from the device counter
 //                           (optimization.py:42-48,177-181) so a captured graph replays correctly
 // Scalars (losses, norms, schedule values, upstream gradients) live in device memory: nothing
@@ -391,9 +391,11 @@ __device__ __forceinline__ void rule_update(float& p, float& m, float& v, float 
     }
 }
 
-// One float4 of each of p, g, m, v per step; UNR independent float4 quadruples per thread and
+// One float4 of each of p, g, m, v per step; UNR = 2 independent float4 quadruples per thread and
 // iteration (loads issued before any use).  g is read once and m, v, shadow are not re-read before the
 // next step: non-temporal accesses keep them from displacing the weights' bf16 shadow in L2/MALL.
+// Measured on MI355X (tools/bench_adam.py, 110 M parameters): 4.7 TB/s with plain accesses and a 4096-block
+// grid-stride loop, 6.3 TB/s with non-temporal g/m/v and one or two float4 quadruples per thread.
 //
 // MAP (split param_groups): lr and weight decay are the element's own -- hm.ids holds one id per 8 elements of the arena
 // (tensors start on multiples of 8, so a float4 never mixes two tensors; a wave does, in the vector region: the values are
@@ -405,9 +407,10 @@ struct HyperMap {
     const float2* table = nullptr;
     unsigned n_table = 0;
 };
-template <int UNR, bool NTMP, bool GB16, int RULE = R_BERT, bool MAP = false>
-__device__ __forceinline__ void bertadam_body(const AdamArgs& a, const int blk, const int nblk, const RuleArgs& ra = RuleArgs(),
-                                              const HyperMap& hm = HyperMap()) {
+template <bool GB16, int RULE, bool MAP>
+__device__ __forceinline__ void bertadam_body(const AdamArgs& a, const int blk, const int nblk, const RuleArgs& ra,
+                                              const HyperMap& hm) {
+    constexpr int UNR = 2;
     constexpr bool USE_M = RuleTraits<RULE>::use_m, USE_V = RuleTraits<RULE>::use_v;
     float coef = 1.f;
     if (a.sqnorm) {
@@ -455,23 +458,16 @@ __device__ __forceinline__ void bertadam_body(const AdamArgs& a, const int blk, 
         for (int u = 0; u < UNR; ++u) {
             const int64_t i = i0 + u * stride;
             if (i < n4 && (!MAP || hid[u])) {
-                p[u] = NTMP ? __builtin_nontemporal_load(reinterpret_cast<const f4*>(a.p) + i) : reinterpret_cast<const f4*>(a.p)[i];
+                p[u] = __builtin_nontemporal_load(reinterpret_cast<const f4*>(a.p) + i);
                 if (GB16) {
                     const s4 gb = __builtin_nontemporal_load(reinterpret_cast<const s4*>(a.g) + i);
 #pragma unroll
                     for (int k = 0; k < 4; ++k) g[u][k] = __bfloat162float(__builtin_bit_cast(bf16, (short)gb[k]));
-                } else if (NTMP) {
+                } else {
                     g[u] = __builtin_nontemporal_load(reinterpret_cast<const f4*>(a.g) + i);
-                } else {
-                    g[u] = reinterpret_cast<const f4*>(a.g)[i];
                 }
-                if (NTMP) {
-                    if (USE_M) m[u] = __builtin_nontemporal_load(reinterpret_cast<const f4*>(a.m) + i);
-                    if (USE_V) v[u] = __builtin_nontemporal_load(reinterpret_cast<const f4*>(a.v) + i);
-                } else {
-                    if (USE_M) m[u] = reinterpret_cast<const f4*>(a.m)[i];
-                    if (USE_V) v[u] = reinterpret_cast<const f4*>(a.v)[i];
-                }
+                if (USE_M) m[u] = __builtin_nontemporal_load(reinterpret_cast<const f4*>(a.m) + i);
+                if (USE_V) v[u] = __builtin_nontemporal_load(reinterpret_cast<const f4*>(a.v) + i);
                 if (!USE_M) m[u] = f4{0.f, 0.f, 0.f, 0.f};
                 if (!USE_V) v[u] = f4{0.f, 0.f, 0.f, 0.f};
             }
@@ -500,15 +496,9 @@ __device__ __forceinline__ void bertadam_body(const AdamArgs& a, const int blk, 
                     m[u][k] = mk;
                     v[u][k] = vk;
                 }
-                if (NTMP) __builtin_nontemporal_store(p[u], reinterpret_cast<f4*>(a.p) + i);
-                else reinterpret_cast<f4*>(a.p)[i] = p[u];
-                if (NTMP) {
-                    if (USE_M) __builtin_nontemporal_store(m[u], reinterpret_cast<f4*>(a.m) + i);
-                    if (USE_V) __builtin_nontemporal_store(v[u], reinterpret_cast<f4*>(a.v) + i);
-                } else {
-                    if (USE_M) reinterpret_cast<f4*>(a.m)[i] = m[u];
-                    if (USE_V) reinterpret_cast<f4*>(a.v)[i] = v[u];
-                }
+                __builtin_nontemporal_store(p[u], reinterpret_cast<f4*>(a.p) + i);
+                if (USE_M) __builtin_nontemporal_store(m[u], reinterpret_cast<f4*>(a.m) + i);
+                if (USE_V) __builtin_nontemporal_store(v[u], reinterpret_cast<f4*>(a.v) + i);
                 if (a.shadow) {
                     s4 sh;
 #pragma unroll
@@ -555,61 +545,26 @@ __device__ __forceinline__ void bertadam_body(const AdamArgs& a, const int blk, 
     }
 }
 
-template <int UNR, bool NTMP, bool GB16>
-__global__ __launch_bounds__(NT) void bertadam_kernel(AdamArgs a) {
-    bertadam_body<UNR, NTMP, GB16>(a, (int)blockIdx.x, (int)gridDim.x);
-}
-
 // several spans (the arena groups a pass updates, or a rank's slices of them) in ONE launch: a workgroup finds its span
 // in the prefix table and runs the same body on its share of that span's grid.  Four launches per pass before; every
 // launch boundary leaves the chip draining one update's tail while the next one's first loads have not been issued.
+// r[] stands behind blk0 and n: BertAdam reads no rule arguments, and what it does read keeps the kernel-argument
+// offsets of a table without them.
 constexpr int ADAM_MULTI = 8;
-struct AdamMulti {
+struct OptimSpans {
     AdamArgs a[ADAM_MULTI];
     int blk0[ADAM_MULTI + 1];
     int n;
-};
-template <int UNR, bool NTMP, bool GB16>
-__global__ __launch_bounds__(NT) void bertadam_multi_kernel(AdamMulti am) {
-    int j = 0;
-#pragma unroll
-    for (int k = 1; k < ADAM_MULTI; ++k)
-        if (k < am.n && (int)blockIdx.x >= am.blk0[k]) j = k;
-    bertadam_body<UNR, NTMP, GB16>(am.a[j], (int)blockIdx.x - am.blk0[j], am.blk0[j + 1] - am.blk0[j]);
-}
-
-// the same launch for a rule of xggm_optim_multi: every span carries its rule arguments beside the update's
-struct OptimMulti {
-    AdamArgs a[ADAM_MULTI];
     RuleArgs r[ADAM_MULTI];
-    int blk0[ADAM_MULTI + 1];
-    int n;
 };
-template <int UNR, bool NTMP, bool GB16, int RULE>
-__global__ __launch_bounds__(NT) void optim_multi_kernel(OptimMulti om) {
+// the kernel of every rule (the trace tools find the end of a pass by this name); hm is read under MAP only
+template <bool GB16, int RULE, bool MAP>
+__global__ __launch_bounds__(NT) void bertadam_multi_kernel(OptimSpans sp, HyperMap hm) {
     int j = 0;
 #pragma unroll
     for (int k = 1; k < ADAM_MULTI; ++k)
-        if (k < om.n && (int)blockIdx.x >= om.blk0[k]) j = k;
-    bertadam_body<UNR, NTMP, GB16, RULE>(om.a[j], (int)blockIdx.x - om.blk0[j], om.blk0[j + 1] - om.blk0[j], om.r[j]);
-}
-
-// the two launches above under a hyper map; the map is an argument of these kernels only
-template <int UNR, bool NTMP, bool GB16>
-__global__ __launch_bounds__(NT) void bertadam_multi_mapped_kernel(AdamMulti am, HyperMap hm) {
-    int j = 0;
-#pragma unroll
-    for (int k = 1; k < ADAM_MULTI; ++k)
-        if (k < am.n && (int)blockIdx.x >= am.blk0[k]) j = k;
-    bertadam_body<UNR, NTMP, GB16, R_BERT, true>(am.a[j], (int)blockIdx.x - am.blk0[j], am.blk0[j + 1] - am.blk0[j], RuleArgs(), hm);
-}
-template <int UNR, bool NTMP, bool GB16, int RULE>
-__global__ __launch_bounds__(NT) void optim_multi_mapped_kernel(OptimMulti om, HyperMap hm) {
-    int j = 0;
-#pragma unroll
-    for (int k = 1; k < ADAM_MULTI; ++k)
-        if (k < om.n && (int)blockIdx.x >= om.blk0[k]) j = k;
-    bertadam_body<UNR, NTMP, GB16, RULE, true>(om.a[j], (int)blockIdx.x - om.blk0[j], om.blk0[j + 1] - om.blk0[j], om.r[j], hm);
+        if (k < sp.n && (int)blockIdx.x >= sp.blk0[k]) j = k;
+    bertadam_body<GB16, RULE, MAP>(sp.a[j], (int)blockIdx.x - sp.blk0[j], sp.blk0[j + 1] - sp.blk0[j], sp.r[j], hm);
 }
 
 // Delayed scaling of the e4m3 operands (weights and activation sites share one table).  Producers record the
@@ -896,30 +851,6 @@ extern "C" int xggm_sqnorm_f32(const float* g, int64_t n, float* out, float* ws,
     return norm_of_ranges("xggm_sqnorm_f32", &r, 1, out, nullptr, ws, 1, 1.f, nullptr, st);
 }
 
-namespace {
-int launch_adam(const AdamArgs& a, bool g_bf16, hipStream_t st) {
-    // measured on MI355X (tools/bench_adam.py, 110 M parameters): 4.7 TB/s with plain accesses and a 4096-block
-    // grid-stride loop, 6.3 TB/s with non-temporal g/m/v and one or two float4 quadruples per thread
-    const dim3 grid(grid1d(a.n / 8 + 1, 65536));
-    if (g_bf16) hipLaunchKernelGGL((bertadam_kernel<2, true, true>), grid, dim3(NT), 0, st, a);
-    else hipLaunchKernelGGL((bertadam_kernel<2, true, false>), grid, dim3(NT), 0, st, a);
-    return xggm_check_launch("xggm_bertadam");
-}
-}  // namespace
-
-extern "C" int xggm_bertadam_f32(float* p, const float* g, float* m, float* v, void* shadow_bf16, int64_t n,
-                                 const float* sqnorm, float max_norm, float lr, const float* lr_scale, float b1, float b2,
-                                 float eps, float weight_decay, hipStream_t st) {
-    XGGM_REQUIRE(p && g && m && v && n > 0, "xggm_bertadam_f32: bad arguments");
-    XGGM_REQUIRE((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) |
-                  reinterpret_cast<uintptr_t>(v)) % 16 == 0,
-                 "xggm_bertadam_f32: pointers must be 16-byte aligned");
-    XGGM_REQUIRE(!shadow_bf16 || reinterpret_cast<uintptr_t>(shadow_bf16) % 8 == 0, "xggm_bertadam_f32: shadow misaligned");
-    AdamArgs a{p, g, m, v, (bf16*)shadow_bf16, n, sqnorm, max_norm, lr, nullptr, lr_scale, b1, b2, eps, weight_decay,
-               nullptr, nullptr, nullptr, nullptr, 0, 1.f, 1};
-    return launch_adam(a, false, st);
-}
-
 extern "C" int xggm_sqnorm_multi_f32(const float* base, const int64_t* offsets, const int64_t* lengths, int n, float* out,
                                      float* norm, float* ws, int overwrite, int square, float mul, hipStream_t st) {
     // 16 and not MAX_NORM_SPANS: how callers chunk their ranges decides the workgroups each gets, and so the bits
@@ -930,32 +861,16 @@ extern "C" int xggm_sqnorm_multi_f32(const float* base, const int64_t* offsets, 
     return norm_of_ranges("xggm_sqnorm_multi_f32", r, n, out, norm, ws, !overwrite, mul, nullptr, st);
 }
 
-extern "C" int xggm_bertadam_ex(const xggm_adam_args* x, hipStream_t st) {
-    XGGM_REQUIRE(x && x->p && x->g && x->m && x->v && x->n > 0, "xggm_bertadam_ex: bad arguments");
-    XGGM_REQUIRE((reinterpret_cast<uintptr_t>(x->p) | reinterpret_cast<uintptr_t>(x->m) | reinterpret_cast<uintptr_t>(x->v)) % 16 == 0 &&
-                     reinterpret_cast<uintptr_t>(x->g) % (x->g_bf16 ? 8 : 16) == 0,
-                 "xggm_bertadam_ex: pointers must be 16-byte aligned (bf16 gradients: 8)");
-    XGGM_REQUIRE(!x->shadow_bf16 || reinterpret_cast<uintptr_t>(x->shadow_bf16) % 8 == 0, "xggm_bertadam_ex: shadow misaligned");
-    XGGM_REQUIRE(!x->shadow8 || (x->w8_id && x->w8_qscale && x->w8_amax && x->elem0 % 256 == 0 && x->n % 4 == 0 &&
-                                 reinterpret_cast<uintptr_t>(x->shadow8) % 4 == 0),
-                 "xggm_bertadam_ex: the e4m3 copy needs the chunk table, the scale table and a range that starts on a "
-                 "256-element chunk of the arena");
-    AdamArgs a{x->p, x->g, x->m, x->v, (bf16*)x->shadow_bf16, x->n, x->sqnorm, x->max_norm, x->lr, x->lr_dev, x->lr_scale,
-               x->b1, x->b2, x->eps, x->weight_decay, (unsigned char*)x->shadow8, x->w8_id, x->w8_qscale, x->w8_amax, x->elem0,
-               x->g_scale > 0.f ? x->g_scale : 1.f, x->w8_amax_slots > 1 ? x->w8_amax_slots : 1};
-    return launch_adam(a, x->g_bf16 != 0, st);
-}
-
 namespace {
 int adam_args_of(const xggm_adam_args* x, AdamArgs& a) {
-    XGGM_REQUIRE(x && x->p && x->g && x->m && x->v && x->n > 0, "xggm_bertadam: bad arguments");
+    XGGM_REQUIRE(x && x->p && x->g && x->m && x->v && x->n > 0, "xggm_optim_multi: bad arguments");
     XGGM_REQUIRE((reinterpret_cast<uintptr_t>(x->p) | reinterpret_cast<uintptr_t>(x->m) | reinterpret_cast<uintptr_t>(x->v)) % 16 == 0 &&
                      reinterpret_cast<uintptr_t>(x->g) % (x->g_bf16 ? 8 : 16) == 0,
-                 "xggm_bertadam: pointers must be 16-byte aligned (bf16 gradients: 8)");
-    XGGM_REQUIRE(!x->shadow_bf16 || reinterpret_cast<uintptr_t>(x->shadow_bf16) % 8 == 0, "xggm_bertadam: shadow misaligned");
+                 "xggm_optim_multi: pointers must be 16-byte aligned (bf16 gradients: 8)");
+    XGGM_REQUIRE(!x->shadow_bf16 || reinterpret_cast<uintptr_t>(x->shadow_bf16) % 8 == 0, "xggm_optim_multi: shadow misaligned");
     XGGM_REQUIRE(!x->shadow8 || (x->w8_id && x->w8_qscale && x->w8_amax && x->elem0 % 256 == 0 && x->n % 4 == 0 &&
                                  reinterpret_cast<uintptr_t>(x->shadow8) % 4 == 0),
-                 "xggm_bertadam: the e4m3 copy needs the chunk table, the scale table and a range that starts on a "
+                 "xggm_optim_multi: the e4m3 copy needs the chunk table, the scale table and a range that starts on a "
                  "256-element chunk of the arena");
     a = AdamArgs{x->p, x->g, x->m, x->v, (bf16*)x->shadow_bf16, x->n, x->sqnorm, x->max_norm, x->lr, x->lr_dev, x->lr_scale,
                  x->b1, x->b2, x->eps, x->weight_decay, (unsigned char*)x->shadow8, x->w8_id, x->w8_qscale, x->w8_amax, x->elem0,
@@ -963,7 +878,7 @@ int adam_args_of(const xggm_adam_args* x, AdamArgs& a) {
     return XGGM_OK;
 }
 
-// the checks of the mapped entry points, all before any launch: the map covers every span, and a span starts on a whole
+// the checks of a call with a hyper map, all before any launch: the map covers every span, and a span starts on a whole
 // id (then no float4 of it straddles two)
 int hyper_map_of(const xggm_hyper_map* map, const char* who, HyperMap& hm) {
     XGGM_REQUIRE(map && map->ids && map->table, "%s: the hyper map needs its id map and its {lr, weight_decay} table", who);
@@ -983,58 +898,48 @@ int span_in_map(const xggm_adam_args& x, const xggm_hyper_map* map, const char* 
     return XGGM_OK;
 }
 
-int bertadam_multi(const xggm_adam_args* args, int n, const xggm_hyper_map* map, hipStream_t st, const char* who) {
-    XGGM_REQUIRE(args && n > 0, "%s: no spans", who);
-    HyperMap hm;
-    if (map) {
-        if (int e = hyper_map_of(map, who, hm)) return e;
-        for (int i = 0; i < n; ++i)
-            if (int e = span_in_map(args[i], map, who, i)) return e;
-    }
-    for (int i0 = 0; i0 < n; i0 += ADAM_MULTI) {
-        AdamMulti am;
-        am.n = std::min(ADAM_MULTI, n - i0);
-        int nblk = 0;
-        for (int i = 0; i < am.n; ++i) {
-            if (int e = adam_args_of(args + i0 + i, am.a[i])) return e;
-            XGGM_REQUIRE(args[i0 + i].g_bf16 == args[i0].g_bf16, "xggm_bertadam_multi: the spans of one call share the gradient type");
-            am.blk0[i] = nblk;
-            nblk += grid1d(am.a[i].n / 8 + 1, 65536);
-        }
-        am.blk0[am.n] = nblk;
-        if (map) {
-            if (args[i0].g_bf16) hipLaunchKernelGGL((bertadam_multi_mapped_kernel<2, true, true>), dim3(nblk), dim3(NT), 0, st, am, hm);
-            else hipLaunchKernelGGL((bertadam_multi_mapped_kernel<2, true, false>), dim3(nblk), dim3(NT), 0, st, am, hm);
-        } else if (args[i0].g_bf16) {
-            hipLaunchKernelGGL((bertadam_multi_kernel<2, true, true>), dim3(nblk), dim3(NT), 0, st, am);
-        } else {
-            hipLaunchKernelGGL((bertadam_multi_kernel<2, true, false>), dim3(nblk), dim3(NT), 0, st, am);
-        }
-        if (int e = xggm_check_launch(who)) return e;
+// a span's rule arguments (the complements in double) and the values a rule keeps in the span itself
+int rule_args_of(const xggm_optim_args& x, int inst, const char* who, AdamArgs& a, RuleArgs& r) {
+    r = RuleArgs();
+    if (inst == R_BERT) return XGGM_OK;
+    XGGM_REQUIRE(!x.a.shadow8, "%s: the e4m3 weight copy is written by the BertAdam rule only", who);
+    XGGM_REQUIRE(x.step_scalars || !(inst == R_ADAM || inst == R_ADAMAX || inst == R_SGDM),
+                 "%s: rule %d needs step_scalars (xggm_sched_step_ex)", who, x.rule);
+    r.hs = x.step_scalars;
+    r.decoupled = x.rule == XGGM_RULE_ADAMW;
+    r.mom = (float)x.momentum;
+    r.nesterov = x.nesterov != 0;
+    r.omd = (float)(1.0 - x.dampening);
+    if (inst == R_ADAM || inst == R_ADAMAX) {
+        XGGM_REQUIRE(x.b1 >= 0.0 && x.b1 < 1.0 && x.b2 >= 0.0 && x.b2 < 1.0, "%s: betas outside [0, 1)", who);
+        a.b1 = (float)x.b1;
+        a.b2 = (float)x.b2;
+        r.omb1 = (float)(1.0 - x.b1);
+        r.omb2 = (float)(1.0 - x.b2);
+    } else if (inst == R_RMS0 || inst == R_RMSM) {
+        a.b2 = (float)x.alpha;
+        r.omb2 = (float)(1.0 - x.alpha);
     }
     return XGGM_OK;
 }
 
-int optim_multi(const xggm_optim_args* args, int n, const xggm_hyper_map* map, hipStream_t st, const char* who);
+template <int RULE>
+void launch_spans(const OptimSpans& sp, const HyperMap* hm, bool gb, int nblk, hipStream_t st) {
+    const HyperMap none;
+    if (hm) {
+        if (gb) hipLaunchKernelGGL((bertadam_multi_kernel<true, RULE, true>), dim3(nblk), dim3(NT), 0, st, sp, *hm);
+        else hipLaunchKernelGGL((bertadam_multi_kernel<false, RULE, true>), dim3(nblk), dim3(NT), 0, st, sp, *hm);
+    } else if (gb) {
+        hipLaunchKernelGGL((bertadam_multi_kernel<true, RULE, false>), dim3(nblk), dim3(NT), 0, st, sp, none);
+    } else {
+        hipLaunchKernelGGL((bertadam_multi_kernel<false, RULE, false>), dim3(nblk), dim3(NT), 0, st, sp, none);
+    }
+}
 }  // namespace
 
-extern "C" int xggm_bertadam_multi(const xggm_adam_args* args, int n, hipStream_t st) {
-    return bertadam_multi(args, n, nullptr, st, "xggm_bertadam_multi");
-}
-extern "C" int xggm_bertadam_multi_mapped(const xggm_adam_args* args, int n, const xggm_hyper_map* map, hipStream_t st) {
-    XGGM_REQUIRE(map, "xggm_bertadam_multi_mapped: no hyper map");
-    return bertadam_multi(args, n, map, st, "xggm_bertadam_multi_mapped");
-}
-extern "C" int xggm_optim_multi(const xggm_optim_args* args, int n, hipStream_t st) {
-    return optim_multi(args, n, nullptr, st, "xggm_optim_multi");
-}
-extern "C" int xggm_optim_multi_mapped(const xggm_optim_args* args, int n, const xggm_hyper_map* map, hipStream_t st) {
-    XGGM_REQUIRE(map, "xggm_optim_multi_mapped: no hyper map");
-    return optim_multi(args, n, map, st, "xggm_optim_multi_mapped");
-}
-
-namespace {
-int optim_multi(const xggm_optim_args* args, int n, const xggm_hyper_map* map, hipStream_t st, const char* who) {
+// the planner of the update: the map and every span are checked first, then one launch per ADAM_MULTI spans
+extern "C" int xggm_optim_multi(const xggm_optim_args* args, int n, const xggm_hyper_map* map, hipStream_t st) {
+    const char* who = "xggm_optim_multi";
     XGGM_REQUIRE(args && n > 0, "%s: no spans", who);
     HyperMap hm;
     if (map) {
@@ -1044,87 +949,45 @@ int optim_multi(const xggm_optim_args* args, int n, const xggm_hyper_map* map, h
     }
     const int rule = args[0].rule;
     XGGM_REQUIRE(rule >= XGGM_RULE_BERTADAM && rule <= XGGM_RULE_RMSPROP, "%s: unknown rule %d", who, rule);
-    const bool mom0 = args[0].momentum == 0.0;
+    const bool mom0 = args[0].momentum == 0.0, gb = args[0].a.g_bf16 != 0;
     int inst = R_BERT;
     if (rule == XGGM_RULE_ADAM || rule == XGGM_RULE_ADAMW) inst = R_ADAM;
     else if (rule == XGGM_RULE_ADAMAX) inst = R_ADAMAX;
     else if (rule == XGGM_RULE_SGD) inst = mom0 ? R_SGD0 : R_SGDM;
     else if (rule == XGGM_RULE_RMSPROP) inst = mom0 ? R_RMS0 : R_RMSM;
+    AdamArgs a;
+    RuleArgs r;
+    for (int i = 0; i < n; ++i) {
+        if (int e = adam_args_of(&args[i].a, a)) return e;
+        XGGM_REQUIRE(args[i].rule == rule && (args[i].momentum == 0.0) == mom0 && (args[i].a.g_bf16 != 0) == gb,
+                     "%s: the spans of one call share the rule, the gradient type and whether momentum is zero", who);
+        if (int e = rule_args_of(args[i], inst, who, a, r)) return e;
+    }
     for (int i0 = 0; i0 < n; i0 += ADAM_MULTI) {
-        OptimMulti om;
-        om.n = std::min(ADAM_MULTI, n - i0);
+        OptimSpans sp;
+        sp.n = std::min(ADAM_MULTI, n - i0);
         int nblk = 0;
-        for (int i = 0; i < om.n; ++i) {
-            const xggm_optim_args& x = args[i0 + i];
-            if (int e = adam_args_of(&x.a, om.a[i])) return e;
-            XGGM_REQUIRE(x.rule == rule && (x.momentum == 0.0) == mom0 && x.a.g_bf16 == args[0].a.g_bf16,
-                         "%s: the spans of one call share the rule, the gradient type and whether momentum is zero", who);
-            RuleArgs& r = om.r[i];
-            r = RuleArgs();
-            if (inst != R_BERT) {
-                XGGM_REQUIRE(!x.a.shadow8, "%s: the e4m3 weight copy is written by the BertAdam rule only", who);
-                XGGM_REQUIRE(x.step_scalars || !(inst == R_ADAM || inst == R_ADAMAX || inst == R_SGDM),
-                             "%s: rule %d needs step_scalars (xggm_sched_step_ex)", who, rule);
-                r.hs = x.step_scalars;
-                r.decoupled = rule == XGGM_RULE_ADAMW;
-                r.mom = (float)x.momentum;
-                r.nesterov = x.nesterov != 0;
-                r.omd = (float)(1.0 - x.dampening);
-                if (inst == R_ADAM || inst == R_ADAMAX) {
-                    XGGM_REQUIRE(x.b1 >= 0.0 && x.b1 < 1.0 && x.b2 >= 0.0 && x.b2 < 1.0, "%s: betas outside [0, 1)", who);
-                    om.a[i].b1 = (float)x.b1;
-                    om.a[i].b2 = (float)x.b2;
-                    r.omb1 = (float)(1.0 - x.b1);
-                    r.omb2 = (float)(1.0 - x.b2);
-                } else if (inst == R_RMS0 || inst == R_RMSM) {
-                    om.a[i].b2 = (float)x.alpha;
-                    r.omb2 = (float)(1.0 - x.alpha);
-                }
-            }
-            om.blk0[i] = nblk;
-            nblk += grid1d(om.a[i].n / 8 + 1, 65536);
+        for (int i = 0; i < sp.n; ++i) {
+            adam_args_of(&args[i0 + i].a, sp.a[i]);
+            rule_args_of(args[i0 + i], inst, who, sp.a[i], sp.r[i]);
+            sp.blk0[i] = nblk;
+            nblk += grid1d(sp.a[i].n / 8 + 1, 65536);
         }
-        om.blk0[om.n] = nblk;
-        const bool gb = args[0].a.g_bf16 != 0;
-#define OPTIM_LAUNCH(R)                                                                                                    \
-    case R:                                                                                                                \
-        if (map) {                                                                                                         \
-            if (gb) hipLaunchKernelGGL((optim_multi_mapped_kernel<2, true, true, R>), dim3(nblk), dim3(NT), 0, st, om, hm);  \
-            else hipLaunchKernelGGL((optim_multi_mapped_kernel<2, true, false, R>), dim3(nblk), dim3(NT), 0, st, om, hm);    \
-        } else if (gb) {                                                                                                   \
-            hipLaunchKernelGGL((optim_multi_kernel<2, true, true, R>), dim3(nblk), dim3(NT), 0, st, om);                  \
-        } else {                                                                                                           \
-            hipLaunchKernelGGL((optim_multi_kernel<2, true, false, R>), dim3(nblk), dim3(NT), 0, st, om);                 \
-        }                                                                                                                  \
-        break;
+        sp.blk0[sp.n] = nblk;
+        const HyperMap* h = map ? &hm : nullptr;
         switch (inst) {
-            OPTIM_LAUNCH(R_ADAM)
-            OPTIM_LAUNCH(R_ADAMAX)
-            OPTIM_LAUNCH(R_SGD0)
-            OPTIM_LAUNCH(R_SGDM)
-            OPTIM_LAUNCH(R_RMS0)
-            OPTIM_LAUNCH(R_RMSM)
-            default: {  // XGGM_RULE_BERTADAM: xggm_bertadam_multi's kernel
-                AdamMulti am;
-                am.n = om.n;
-                for (int i = 0; i < om.n; ++i) am.a[i] = om.a[i];
-                for (int i = 0; i <= om.n; ++i) am.blk0[i] = om.blk0[i];
-                if (map) {
-                    if (gb) hipLaunchKernelGGL((bertadam_multi_mapped_kernel<2, true, true>), dim3(nblk), dim3(NT), 0, st, am, hm);
-                    else hipLaunchKernelGGL((bertadam_multi_mapped_kernel<2, true, false>), dim3(nblk), dim3(NT), 0, st, am, hm);
-                } else if (gb) {
-                    hipLaunchKernelGGL((bertadam_multi_kernel<2, true, true>), dim3(nblk), dim3(NT), 0, st, am);
-                } else {
-                    hipLaunchKernelGGL((bertadam_multi_kernel<2, true, false>), dim3(nblk), dim3(NT), 0, st, am);
-                }
-            }
+            case R_BERT: launch_spans<R_BERT>(sp, h, gb, nblk, st); break;
+            case R_ADAM: launch_spans<R_ADAM>(sp, h, gb, nblk, st); break;
+            case R_ADAMAX: launch_spans<R_ADAMAX>(sp, h, gb, nblk, st); break;
+            case R_SGD0: launch_spans<R_SGD0>(sp, h, gb, nblk, st); break;
+            case R_SGDM: launch_spans<R_SGDM>(sp, h, gb, nblk, st); break;
+            case R_RMS0: launch_spans<R_RMS0>(sp, h, gb, nblk, st); break;
+            default: launch_spans<R_RMSM>(sp, h, gb, nblk, st);
         }
-#undef OPTIM_LAUNCH
         if (int e = xggm_check_launch(who)) return e;
     }
     return XGGM_OK;
 }
-}  // namespace
 
 extern "C" int xggm_sqnorm_bf16(const void* g, int64_t n, float* out, float* ws, hipStream_t st) {
     XGGM_REQUIRE(g && n > 0, "xggm_sqnorm_bf16: bad arguments");

@@ -11,7 +11,7 @@ No quantisation pass exists in the step:
     (``xggm_ln_fwd_problem.out8``), the GELU epilogue of the intermediate product (``xggm_gemm_problem.c8``) and the
     attention core (``xggm_attn_problem.out8``); only the two encoder inputs (embedding output, visual-feature
     encoder output) go through ``xggm_quantize_fp8e4m3``;
-  * weights get their e4m3 copy from the optimiser pass that updates them (``xggm_bertadam_ex.shadow8``).
+  * weights get their e4m3 copy from the optimiser pass that updates them (``xggm_adam_args.shadow8`` of ``xggm_optim_multi``).
 Scaling is per tensor and delayed: one device-resident table (``xggm_fp8_scale_update``) holds, per weight operand
 and per activation site, the recorded maximum, a short history, the quantisation scale and its reciprocal (which the
 GEMM epilogue multiplies back in).  The first forward after ``enable_fp8`` is a calibration pass: products run in

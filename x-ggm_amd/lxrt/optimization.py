@@ -192,9 +192,10 @@ class ArenaOptimizer(Optimizer):
     rule: its kernel hyper-parameters, its schedule step and its state layout."""
 
     # ``split_groups=True`` (constructor keyword of every class): param_groups may cut through an arena group and differ
-    # there in lr and weight_decay; the update then reads both per tensor from a device map (ops.bertadam_multi /
-    # ops.optim_multi with ``hyper_map``).  Off: one lr / weight_decay per arena group, a split is refused.
+    # there in lr and weight_decay; the update then reads both per tensor from a device map (ops.optim_multi with
+    # ``hyper_map``).  Off: one lr / weight_decay per arena group, a split is refused.
     split_groups = False
+    rule = None  # key of ops.RULES
     SPLIT_KEYS = ('lr', 'weight_decay')  # what param_groups inside one arena group may differ in
 
     @property
@@ -221,10 +222,26 @@ class ArenaOptimizer(Optimizer):
         """the stand-alone schedule step: counters, ``lr_scale`` and whatever the rule needs per step"""
         raise NotImplementedError
 
+    def _variant(self, pg):
+        """(rule name of ops.RULES, anything else that selects another kernel instantiation): spans of one launch share it"""
+        return (self.rule,)
+
+    def _rule_args(self, pg):
+        """the rule's keyword arguments of ops.optim_multi for this param_group (the group's step scalars are added), or
+        None: the rule takes neither"""
+        return None
+
     def _launch(self, arena, jobs, hyper_map=None):
-        """``jobs``: [(positional arguments of ops.bertadam_ex, its keyword arguments, param_group)]; ``hyper_map``:
-        (ids, table) under split_groups, to be handed to the ops call"""
-        raise NotImplementedError
+        """``jobs``: [(positional arguments of a span of ops.optim_multi, its keyword arguments, param_group, group index)];
+        ``hyper_map``: (ids, table) under split_groups"""
+        by = {}
+        for a, kw, pg, gi in jobs:
+            r = self._rule_args(pg)
+            if r is not None:
+                r = dict(r, step_scalars=arena.step_scalars[4 * gi:4 * gi + 4])
+            by.setdefault(self._variant(pg), []).append((a, kw, r or {}))
+        for key in sorted(by):
+            ops.optim_multi(key[0], by[key], hyper_map=hyper_map)
 
     # ---- shared plumbing
     def _arena(self):
@@ -278,7 +295,7 @@ class ArenaOptimizer(Optimizer):
         return None if i is None else self.param_groups[i]
 
     def _hyper_map(self, arena, upload=True):
-        """split_groups: (ids, table) of ops.bertadam_multi / ops.optim_multi -- the id map of this optimiser over
+        """split_groups: (ids, table) of ops.optim_multi -- the id map of this optimiser over
         ``arena`` (arena.hyper_id_map: one uint8 per 8 elements, 1 + index of the owning param_group, 0 = not ours),
         built and uploaded once, and the {lr, weight_decay} table with one row per param_group behind row 0, rewritten
         when a value changed.  Both outside of captures only."""
@@ -373,7 +390,7 @@ class ArenaOptimizer(Optimizer):
         gbuf = arena.wire if arena.wire is not None else arena.grads  # bf16 wire arena: the update reads it directly
         gscale = arena.grad_scale if arena.wire is not None else 1.0     # ... and holds sums over the ranks
         z = arena.zero1
-        jobs = []  # every span of this step: ONE launch (xggm_bertadam_multi / xggm_optim_multi)
+        jobs = []  # every span of this step: ONE launch (xggm_optim_multi)
         if f8 is not None:
             # new scales of the weight operands of every group, before the update rewrites their e4m3 copies
             f8.update_weight_scales_of([G.name for G, _, _ in todo])
@@ -415,6 +432,7 @@ class ArenaOptimizer(Optimizer):
 class BertAdam(ArenaOptimizer):
     """ref: src/lxrt/optimization.py:58-203 (no bias correction; decoupled weight decay on
     every parameter; gradient clipping is done outside, as LXMERT does)."""
+    rule = "bertadam"
 
     def __init__(self, params, lr, warmup=-1, t_total=-1, schedule='warmup_linear', b1=0.9, b2=0.999, e=1e-6,
                  weight_decay=0.01, max_grad_norm=1.0, split_groups=False):
@@ -529,6 +547,3 @@ class BertAdam(ArenaOptimizer):
         else:  # warmup_cosine / warmup_constant (ref :27-39): a schedule kind per entry
             ops.sched_step_ex(arena.steps, arena.lr_scale, None,
                               [(gi, pg['t_total'], pg['warmup'], pg['schedule'], 0.0, 0.0) for _, pg, gi in todo])
-
-    def _launch(self, arena, jobs, hyper_map=None):
-        ops.bertadam_multi([(a, kw) for a, kw, _, _ in jobs], hyper_map=hyper_map)

@@ -2108,17 +2108,6 @@ def add_scalars(terms):
     return out
 
 
-def bertadam(p, g, m, v, shadow, sqn, max_norm, lr, lr_scale, b1, b2, eps, wd):
-    for t in (p, g, m, v):
-        _c(t, F32)
-        assert t.numel() == p.numel()
-    if shadow is not None:
-        _c(shadow, BF16)
-        assert shadow.numel() == p.numel()
-    call("xggm_bertadam_f32", ptr(p), ptr(g), ptr(m), ptr(v), ptr(shadow), p.numel(), ptr(sqn), float(max_norm),
-         float(lr), ptr(lr_scale), float(b1), float(b2), float(eps), float(wd), stream())
-
-
 class AdamArgs(_ct.Structure):
     """mirror of ``xggm_adam_args`` (include/xggm.h)"""
     _fields_ = [("p", _ct.c_void_p), ("g", _ct.c_void_p), ("m", _ct.c_void_p), ("v", _ct.c_void_p),
@@ -2147,24 +2136,6 @@ def _hyper_map(hyper_map):
     return HyperMap(ptr(ids), ids.numel(), ptr(table), table.shape[0])
 
 
-def bertadam_multi(jobs, hyper_map=None):
-    """``jobs``: argument tuples of ``bertadam_ex`` (positional, then a dict of its keyword arguments): ONE launch for all
-    of them (xggm_bertadam_multi), in chunks by gradient type.  With ``hyper_map`` (see ``_hyper_map``) lr and weight decay
-    are read per tensor from the map (xggm_bertadam_multi_mapped); the jobs' own are then not used."""
-    if not jobs:
-        return
-    structs = [_adam_args(*a, **kw) for a, kw in jobs]
-    hm = None if hyper_map is None else _hyper_map(hyper_map)
-    for bf in (0, 1):
-        chunk = [a for a in structs if a.g_bf16 == bf]
-        if chunk:
-            arr = (AdamArgs * len(chunk))(*chunk)
-            if hm is None:
-                call("xggm_bertadam_multi", _ct.cast(arr, _ct.c_void_p), len(chunk), stream())
-            else:
-                call("xggm_bertadam_multi_mapped", _ct.cast(arr, _ct.c_void_p), len(chunk), _ct.byref(hm), stream())
-
-
 RULES = {"bertadam": 0, "adam": 1, "adamw": 2, "adamax": 3, "sgd": 4, "rmsprop": 5}  # XGGM_RULE_* (include/xggm.h)
 SCHED_KINDS = {"warmup_linear": 0, "warmup_cosine": 1, "warmup_constant": 2}            # XGGM_SCHED_*
 
@@ -2183,13 +2154,14 @@ class SchedEntry(_ct.Structure):
 
 
 def optim_multi(rule, jobs, hyper_map=None):
-    """the fused update under a torch.optim rule (src/param.py:9-31): ``rule`` a key of ``RULES``; ``jobs``: (argument
-    tuple of ``bertadam_ex``, dict of its keyword arguments, dict of the rule's: step_scalars (3 device floats of the span's
-    group, ``sched_step_ex``), b1, b2, momentum, dampening, alpha, nesterov) per span.  ONE launch per 8 spans
-    (xggm_optim_multi), in chunks by gradient type.  ``hyper_map``: as for ``bertadam_multi`` (xggm_optim_multi_mapped)."""
+    """the fused update (xggm_optim_multi): ``rule`` a key of ``RULES`` -- "bertadam" (src/lxrt/optimization.py:159-193) or
+    a torch.optim rule (src/param.py:9-31); ``jobs``: per span (argument tuple of ``_adam_args``, dict of its keyword
+    arguments, dict of the rule's: step_scalars (3 device floats of the span's group, ``sched_step_ex``), b1, b2, momentum,
+    dampening, alpha, nesterov -- ``{}`` for bertadam).  ONE launch per 8 spans, in chunks by gradient type.  With
+    ``hyper_map`` (see ``_hyper_map``) lr and weight decay are read per tensor from the map; the jobs' own are then not used."""
     if not jobs:
         return
-    hm = None if hyper_map is None else _hyper_map(hyper_map)
+    hm = None if hyper_map is None else _ct.byref(_hyper_map(hyper_map))
     structs = []
     for a, kw, r in jobs:
         hs = r.get("step_scalars")
@@ -2203,10 +2175,7 @@ def optim_multi(rule, jobs, hyper_map=None):
         chunk = [x for x in structs if x.a.g_bf16 == bf]
         if chunk:
             arr = (OptimArgs * len(chunk))(*chunk)
-            if hm is None:
-                call("xggm_optim_multi", _ct.cast(arr, _ct.c_void_p), len(chunk), stream())
-            else:
-                call("xggm_optim_multi_mapped", _ct.cast(arr, _ct.c_void_p), len(chunk), _ct.byref(hm), stream())
+            call("xggm_optim_multi", _ct.cast(arr, _ct.c_void_p), len(chunk), hm, stream())
 
 
 def sched_step_ex(steps, lr_scale, step_scalars, entries):
@@ -2224,15 +2193,9 @@ def sched_step_ex(steps, lr_scale, step_scalars, entries):
         call("xggm_sched_step_ex", ptr(steps), ptr(lr_scale), ptr(step_scalars), _ct.cast(arr, _ct.c_void_p), len(ch), stream())
 
 
-def bertadam_ex(p, g, m, v, shadow, sqn, max_norm, lr, lr_scale, b1, b2, eps, wd, lr_dev=None, w8=None, elem0=0, g_scale=1.0):
-    """the update with device-resident lr (``lr_dev``), bf16 gradients (``g.dtype``) and/or the e4m3 weight copy
-    ``w8`` = (shadow8 slice, id table, qscale table, amax table); ``elem0``: arena offset of p[0]."""
-    a = _adam_args(p, g, m, v, shadow, sqn, max_norm, lr, lr_scale, b1, b2, eps, wd, lr_dev=lr_dev, w8=w8, elem0=elem0,
-                   g_scale=g_scale)
-    call("xggm_bertadam_ex", _ct.byref(a), stream())
-
-
 def _adam_args(p, g, m, v, shadow, sqn, max_norm, lr, lr_scale, b1, b2, eps, wd, lr_dev=None, w8=None, elem0=0, g_scale=1.0):
+    """one span of ``optim_multi`` as ``xggm_adam_args``: device-resident lr (``lr_dev``), bf16 gradients (``g.dtype``) and/or
+    the e4m3 weight copy ``w8`` = (shadow8 slice, id table, qscale table, amax table[, slots]); ``elem0``: arena offset of p[0]."""
     for t in (p, m, v):
         _c(t, F32)
         assert t.numel() == p.numel()

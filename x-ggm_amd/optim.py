@@ -31,7 +31,6 @@ def _refuse(cls, **flags):
 
 
 class _TorchRule(ArenaOptimizer):
-    rule = None          # key of ops.RULES
     _m_name = _v_name = None  # torch's names of the buffers kept in arena.m / arena.v
     _has_step = True     # torch keeps state['step'] for this rule
 
@@ -57,18 +56,6 @@ class _TorchRule(ArenaOptimizer):
     def _sched_launch(self, arena, todo):
         ops.sched_step_ex(arena.steps, arena.lr_scale, arena.step_scalars,
                           [(gi, -1, 0.0, 'warmup_linear') + tuple(self._betas(pg)) for _, pg, gi in todo])
-
-    def _variant(self, pg):
-        """(rule name of ops.RULES, anything else that selects another kernel instantiation): spans of one launch share it"""
-        return (self.rule,)
-
-    def _launch(self, arena, jobs, hyper_map=None):
-        by = {}
-        for a, kw, pg, gi in jobs:
-            by.setdefault(self._variant(pg), []).append(
-                (a, kw, dict(self._rule_args(pg), step_scalars=arena.step_scalars[4 * gi:4 * gi + 4])))
-        for key in sorted(by):
-            ops.optim_multi(key[0], by[key], hyper_map=hyper_map)
 
     # ---- checkpointing: torch's per-parameter layout, read from / written into the flat arena
     def state_dict(self):
