@@ -1225,6 +1225,54 @@ typedef struct xggm_hyper_map {
  * allocation, no synchronisation. */
 int xggm_optim_multi(const xggm_optim_args* args, int n, const xggm_hyper_map* map /* or NULL */, xggm_stream_t stream);
 
+/* BertLamb: BertAdam.step (src/lxrt/optimization.py:159-193) with a layer-wise trust ratio between its lines 171 and 192 --
+ * LAMB, the large-batch remedy of the BERT code base, for the optimiser that src/vqa/vqacpv2.py:125-128 builds.  Per
+ * parameter tensor T, with g' = g * coef and coef the clip scale times g_scale as in xggm_adam_args:
+ *     m = b1 m + (1 - b1) g'        v = b2 v + (1 - b2) g'^2
+ *     u = m / (sqrt(v) + eps) + weight_decay * p
+ *     r_T = (float)(sqrt(Sp) / sqrt(Su))  if T is adapted and Sp > 0 and Su > 0,  else 1
+ *           Sp = sum over T of (double)p^2 (the values BEFORE the step), Su = sum over T of (double)u^2
+ *     p  -= (lr * lr_scale * r_T) * u, then the bf16 shadow
+ * with every fp32 operation shaped as in xggm_optim_multi's BertAdam rule, so that r_T = 1 gives that rule's bits in p, m,
+ * v and the shadow.
+ *   spans    HOST array of n xggm_adam_args (shadow8 NULL), in arena order, not overlapping, elem0 a multiple of 8; all share
+ *            the gradient type.  elem0 is always read here: it places the span against the tensor table.
+ *   tensors  DEVICE table of n_tensors entries {elem0, n, adapted}, sorted by elem0, disjoint, every elem0 a multiple of 8
+ *            (tensors start on multiples of 8 elements, as the hyper map assumes).  A tensor takes part when its first element
+ *            lies in a span; it must then end inside that span.  Elements of a span that belong to no tensor (alignment gaps)
+ *            are neither read nor written: they hold zeros and keep them.  The table may list tensors outside every span.
+ *   map      the xggm_hyper_map of xggm_optim_multi, or NULL: lr and weight_decay of a tensor are those of the id of its first
+ *            element.  Id 0 (or >= n_table): no byte of the tensor is written, its ratio reads 1.
+ *   ratios_out  DEVICE float [n_tensors]: r_T of every tensor that took part; the others keep what they held.
+ *   ws       DEVICE scratch of xggm_lamb_workspace_bytes(arena_elems, n_tensors) bytes, 16-byte aligned, arena_elems >= the end
+ *            of the last span; needs no initialisation, undefined after.
+ * ORDER OF THE SUMS (of Sp over x = p^2 and of Su over x = u^2; it depends on the tensor's length alone: not on the grid, the
+ * timing, where the tensor lies or which other tensors the call updates).  All squares and additions are fp64 (the square of
+ * an fp32 value is exact there); there is no floating-point atomic.  The tensor is cut into chunks of XGGM_LAMB_CHUNK = 2048
+ * elements from its first element on, the last one padded with +0.0.  Within a chunk, element e belongs to thread
+ * t = (e / 4) % 256:
+ *     a[t] = (((((((+0.0 + x[4t]) + x[4t+1]) + x[4t+2]) + x[4t+3]) + x[1024+4t]) + x[1025+4t]) + x[1026+4t]) + x[1027+4t]
+ *     then inside each run of 64 threads (l = t % 64), for h = 32, 16, 8, 4, 2, 1:   a[l] = a[l] + a[l + h]   for l in [0, h)
+ *     partial = (a[0] + a[64]) + (a[128] + a[192])
+ * and over the chunks c = 0 .. C - 1 of the tensor:  b[t] = ((+0.0 + partial[t]) + partial[t + 256]) + ... for t in [0, 256)
+ * (+0.0 where t >= C), reduced by the same two lines.  numpy: xggm_amd.lxrt.optimization.lamb_sum_host.
+ * Three launches per 8 spans, behind each other on the stream: phase A reads g, m, v, p, writes m and v and leaves the chunks'
+ * sums in ws; a finish with one workgroup per table entry writes ratios_out; phase B recomputes u from m, v, p with the same
+ * device function (the norm describes what is applied) and writes p and the shadow.  Every argument is checked before the
+ * first launch: null spans / tensors / ratios_out / ws, n or n_tensors < 1, a span with a null pointer, no elements, a
+ * misaligned pointer, an e4m3 copy, another gradient type, an elem0 that is no multiple of 8 or lies in front of the previous
+ * span's end, or (with a map) beyond the id map; a bad map; ws_bytes below the declared size.  No allocation, no
+ * synchronisation: legal inside a stream capture. */
+#define XGGM_LAMB_CHUNK 2048
+typedef struct xggm_lamb_tensor {
+    int64_t elem0;   /* arena offset of the tensor's first element */
+    int64_t n;       /* its elements */
+    int64_t adapted; /* 0: r_T = 1 */
+} xggm_lamb_tensor;
+size_t xggm_lamb_workspace_bytes(int64_t arena_elems, int n_tensors);
+int xggm_lamb_multi(const xggm_adam_args* spans, int n, const xggm_lamb_tensor* tensors, int n_tensors,
+                    const xggm_hyper_map* map /* or NULL */, float* ratios_out, void* ws, size_t ws_bytes, xggm_stream_t stream);
+
 /* xggm_sched_step_multi with a schedule kind per entry (src/lxrt/optimization.py:27-48: warmup_cosine, warmup_constant,
  * warmup_linear; the xggm_sched_step* calls keep meaning warmup_linear) and the per-step scalars of xggm_optim_multi:
  * for entry i with k = index, s = steps[k]: lr_scale[k] = kind(s / t_total, warmup) in double (1 when t_total <= 0),

@@ -481,7 +481,10 @@ class BertAdam(ArenaOptimizer):
         """hyper-parameters through torch's loader, moments and step counters IN PLACE into the arena (captured
         graphs keep pointing at the same buffers).  Before the arena exists (no forward yet) the state is kept and
         applied at the first use."""
-        super().load_state_dict({'state': {}, 'param_groups': state_dict['param_groups']})
+        groups = state_dict['param_groups']
+        if 'layer_adaptation' not in self.defaults:  # a BertLamb checkpoint: the moments are the same, its flag is not ours
+            groups = [{k: v for k, v in g.items() if k != 'layer_adaptation'} for g in groups]
+        super().load_state_dict({'state': {}, 'param_groups': groups})
         self._pending_state = dict(state_dict.get('state', {}))
         self._arena()
 
@@ -547,3 +550,130 @@ class BertAdam(ArenaOptimizer):
         else:  # warmup_cosine / warmup_constant (ref :27-39): a schedule kind per entry
             ops.sched_step_ex(arena.steps, arena.lr_scale, None,
                               [(gi, pg['t_total'], pg['warmup'], pg['schedule'], 0.0, 0.0) for _, pg, gi in todo])
+
+
+# ---------------------------------------------------------------------------------------------------------------- BertLamb
+def lamb_sum_host(x):
+    """the fp64 sum of a 1-D array in the order ``xggm_lamb_multi`` sums a tensor's p^2 and u^2 (include/xggm.h, "ORDER OF
+    THE SUMS"): chunks of 2048 from the first element on, 256 threads with two runs of four values each, a tree inside
+    every 64 threads, the four results pairwise; then the chunks' partials strided over 256 threads and the same
+    reduction.  numpy, no device."""
+    import numpy as np
+
+    def reduce256(a):  # [rows, 256] -> [rows]
+        a = a.reshape(-1, 4, 64).copy()
+        h = 32
+        while h >= 1:
+            a[:, :, :h] = a[:, :, :h] + a[:, :, h:2 * h]
+            h //= 2
+        return (a[:, 0, 0] + a[:, 1, 0]) + (a[:, 2, 0] + a[:, 3, 0])
+
+    x = np.asarray(x, dtype=np.float64).reshape(-1)
+    chunk = ops.LAMB_CHUNK
+    C = max(1, -(-x.size // chunk))
+    x = np.concatenate([x, np.zeros(C * chunk - x.size)]).reshape(C, 2, 256, 4)
+    a = np.zeros((C, 256))
+    for u in range(2):
+        for k in range(4):
+            a = a + x[:, u, :, k]
+    part = reduce256(a)
+    R = -(-C // 256)
+    part = np.concatenate([part, np.zeros(R * 256 - C)]).reshape(R, 256)
+    b = np.zeros(256)
+    for r in range(R):
+        b = b + part[r]
+    return float(reduce256(b[None])[0])
+
+
+def lamb_step_host(p, g, m, v, lr, b1=0.9, b2=0.999, e=1e-6, weight_decay=0.01, adapted=True):
+    """``BertLamb``'s step of ONE tensor restated in fp64 (numpy): ``g`` is the clipped gradient, ``lr`` the scheduled
+    learning rate.  -> (p, m, v, ratio); the ratio is rounded to fp32 as the kernel's is."""
+    import numpy as np
+    p, g, m, v = (np.asarray(t, dtype=np.float64).reshape(-1) for t in (p, g, m, v))
+    m = b1 * m + (1.0 - b1) * g
+    v = b2 * v + (1.0 - b2) * g * g
+    u = m / (np.sqrt(v) + e)
+    if weight_decay > 0.0:
+        u = u + weight_decay * p
+    sp, su = lamb_sum_host(p * p), lamb_sum_host(u * u)
+    r = float(np.float32(math.sqrt(sp) / math.sqrt(su))) if (adapted and sp > 0.0 and su > 0.0) else 1.0
+    return p - lr * r * u, m, v, r
+
+
+class BertLamb(BertAdam):
+    """LAMB over BertAdam: the same moments, schedules, constructor and ``state_dict`` layout (ref:
+    src/lxrt/optimization.py:58-203), and the step of every parameter tensor T multiplied by the trust ratio
+    ||p_T|| / ||u_T|| of that tensor (1 where a norm is zero) -- the layer-wise adaptation the BERT code base shipped for
+    large batches.  One new param_group key, ``layer_adaptation`` (default True): False leaves the group's tensors at
+    ratio 1, which is BertAdam bit for bit.  The update is two passes and a finish (``ops.lamb_multi``); a tensor's norms
+    are summed in double in an order that depends on its length alone, so replicas that hold the same bits keep the same
+    bits and nothing new is exchanged under replicated data parallelism."""
+    rule = "bertlamb"
+    SPLIT_KEYS = ArenaOptimizer.SPLIT_KEYS + ('layer_adaptation',)
+
+    def __init__(self, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        self.defaults['layer_adaptation'] = True
+
+    def add_param_group(self, param_group):
+        param_group.setdefault('layer_adaptation', True)
+        super().add_param_group(param_group)
+        self._lamb = None  # (the tensor table carries the groups' flags)
+
+    def load_state_dict(self, state_dict):
+        """as BertAdam; a BertAdam checkpoint has no ``layer_adaptation``: the groups keep the flags they have"""
+        flags = [pg['layer_adaptation'] for pg in self.param_groups]
+        super().load_state_dict(state_dict)
+        for pg, f in zip(self.param_groups, flags):
+            pg.setdefault('layer_adaptation', f)
+
+    def _check_arena(self, arena):
+        if arena.zero1 is not None:
+            raise RuntimeError("BertLamb does not run under the sharded update (zero1): a tensor's norm would cross the ranks' "
+                               "slices; build the data parallelism without zero1 (the replicated update needs no exchange: "
+                               "every rank sums the same bits in the same order)")
+        if arena.fp8 is not None:
+            raise RuntimeError("BertLamb does not run with the fp8 forward: the e4m3 weight copies are written by BertAdam's "
+                               "one-pass update only")
+
+    def _lamb_state(self, arena):
+        """the device tensor table {elem0, n, adapted}, the ratio table and the scratch of ``ops.lamb_multi``: built and
+        uploaded outside of captures, the table again when a ``layer_adaptation`` flag has changed"""
+        owned = {}
+        for pg in self.param_groups:
+            for p in pg['params']:
+                xg = getattr(p, "_xg", None)
+                if xg is not None and xg[0] is arena:
+                    owned[xg[5]] = bool(pg['layer_adaptation'])
+        st = getattr(self, "_lamb", None)
+        if st is None or st['arena'] is not arena or st['owned'] != owned:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("BertLamb.step is being captured before any eager step, or a layer_adaptation flag changed "
+                                   "during graph capture: run one pass eagerly first (the tensor table is uploaded to the device "
+                                   "outside of captures)")
+            from ..arena import lamb_tensor_table
+            table, names = lamb_tensor_table(arena.info, owned, arena.total)
+            if st is not None and st['arena'] is arena:  # captured graphs keep pointing at the same buffers
+                st['tensors'].copy_(torch.from_numpy(table))
+                st['owned'] = owned
+            else:
+                st = self._lamb = dict(arena=arena, owned=owned, names=names, tensors=torch.from_numpy(table).to(arena.device),
+                                       ratios=torch.ones(len(names), device=arena.device),
+                                       ws=ops.lamb_workspace(arena.total, len(names), arena.device))
+        return st
+
+    def _launch(self, arena, jobs, hyper_map=None):
+        if not jobs:
+            return
+        st = self._lamb_state(arena)
+        spans = sorted(jobs, key=lambda j: j[1]['elem0'])  # arena order
+        ops.lamb_multi([(a, kw, {}) for a, kw, _, _ in spans], st['tensors'], st['ratios'], st['ws'], hyper_map)
+
+    def trust_ratios(self):
+        """{parameter name: trust ratio} of the last step that updated the parameter (1.0 before its first), for the
+        parameters this optimiser holds: ONE read of the device table"""
+        st = getattr(self, "_lamb", None)
+        if st is None:
+            return {}
+        r = st['ratios'].tolist()
+        return {n: r[i] for i, n in enumerate(st['names']) if n in st['owned']}

@@ -2178,6 +2178,33 @@ def optim_multi(rule, jobs, hyper_map=None):
             call("xggm_optim_multi", _ct.cast(arr, _ct.c_void_p), len(chunk), hm, stream())
 
 
+LAMB_CHUNK = 2048  # XGGM_LAMB_CHUNK (include/xggm.h)
+
+
+def lamb_workspace(arena_elems, n_tensors, device):
+    """the scratch of ``lamb_multi`` for spans that end at or below ``arena_elems`` and a table of ``n_tensors`` entries"""
+    nbytes = _lib.lib.xggm_lamb_workspace_bytes(int(arena_elems), int(n_tensors))
+    return torch.empty((nbytes + 15) // 16 * 2, device=device, dtype=torch.float64)
+
+
+def lamb_multi(jobs, tensors, ratios, ws, hyper_map=None):
+    """BertLamb's update (xggm_lamb_multi): ``jobs`` as ``optim_multi`` takes them for "bertadam" (no e4m3 copy; ``elem0``
+    is required: it places a span against the table), in arena order.  ``tensors``: int64 [n, 3] device table {elem0, n,
+    adapted}, sorted (``arena.lamb_tensor_table``); ``ratios``: fp32 [n], receives the trust ratio of every tensor that took
+    part; ``ws``: ``lamb_workspace``.  Phase A, a finish and phase B per 8 spans; nothing is allocated or read back."""
+    if not jobs:
+        return
+    _c(tensors, torch.int64), _c(ratios, F32), _c(ws, torch.float64)
+    if tensors.dim() != 2 or tensors.shape[1] != 3 or ratios.numel() != tensors.shape[0]:
+        raise ValueError("xggm_amd: the tensor table is int64 [n, 3] with one ratio per row, got %s and %d ratios"
+                         % (tuple(tensors.shape), ratios.numel()))
+    hm = None if hyper_map is None else _ct.byref(_hyper_map(hyper_map))
+    structs = [_adam_args(*a, **kw) for a, kw, _ in jobs]
+    arr = (AdamArgs * len(structs))(*structs)
+    call("xggm_lamb_multi", _ct.cast(arr, _ct.c_void_p), len(structs), ptr(tensors), tensors.shape[0], hm, ptr(ratios), ptr(ws),
+         ws.numel() * 8, stream())
+
+
 def sched_step_ex(steps, lr_scale, step_scalars, entries):
     """``entries``: [(index, t_total, warmup, kind, b1, b2)] with ``kind`` a key of ``SCHED_KINDS``: schedule value and
     counter as ``sched_step_multi``, evaluated in double, plus -- with ``step_scalars`` (fp32 [groups * 4]) -- the bias

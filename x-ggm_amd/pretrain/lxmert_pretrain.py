@@ -642,6 +642,8 @@ class LXMERT:
         print("Batch per epoch: %d" % batch_per_epoch)
         print("Total Iters: %d" % t_total)
         print("Warm up Iters: %d" % warmup_iters)
+        if 'lamb' in str(getattr(args, 'optim', 'bert')):  # --optim bertlamb: layer-wise trust ratios for large global batches
+            from ..lxrt.optimization import BertLamb as BertAdam
         optim = BertAdam(list(self.model.parameters()), lr=args.lr, warmup=warmup_ratio, t_total=t_total)
         best_eval_loss = 9595.
         for epoch in range(args.epochs):

@@ -439,7 +439,10 @@ def make_optimizer(model, lr, t_total, warmup=0.1, optim='bert', no_decay=None, 
     (src/vqa/vqacpv2.py:141): one group, all parameters, ``lr`` -- the arena-aware class of ``xggm_amd.optim``.
     ``no_decay`` (name substrings, e.g. ``NO_DECAY``) and / or ``layer_decay`` (a factor d per layer of depth, see
     ``split_param_names``) build finer param_groups and turn ``split_groups`` on, so that groups which cut through the
-    arena's ranges are honoured; the else-branch's base lr is ``lr`` for every parameter, as without them."""
+    arena's ranges are honoured; the else-branch's base lr is ``lr`` for every parameter, as without them.
+    ``optim='bertlamb'``: ``BertLamb`` in BertAdam's place (layer-wise trust ratios, for large global batches); with
+    ``no_decay`` the no-decay groups also get ``layer_adaptation=False``."""
+    lamb = isinstance(optim, str) and 'lamb' in optim  # 'bertlamb': param.get_optimizer answers 'bert' for it, as for any bert*
     if isinstance(optim, str):
         from ..param import get_optimizer
         optim = get_optimizer(optim)
@@ -453,6 +456,14 @@ def make_optimizer(model, lr, t_total, warmup=0.1, optim='bert', no_decay=None, 
     if optim != 'bert':
         return optim(groups, lr, split_groups=True) if split else optim(model.parameters(), lr)
     from ..lxrt.optimization import BertAdam
+    if lamb:
+        # the BERT recipe: with ``no_decay`` the biases and LayerNorm weights (the groups split_param_names gave
+        # weight_decay 0.0) are not adapted either
+        from ..lxrt.optimization import BertLamb as BertAdam
+        if split:
+            for g in groups:
+                if g.get("weight_decay") == 0.0:
+                    g["layer_adaptation"] = False
     if split:
         return BertAdam(groups, lr=lr, warmup=warmup, t_total=t_total, split_groups=True)
     lxrt_ids = set(map(id, model.lxrt_encoder.parameters()))
