@@ -203,3 +203,124 @@ def attn_bwd_excess(dq, dk, dv, R, out_dtype, mfma):
         ref, bound = R.bound(name, out_dtype, mfma)
         out[name] = bound_excess(g.detach().double().cpu(), ref, bound)
     return out
+
+
+# ---- element-wise row-kernel bounds --------------------------------------------------------------------------------
+# The row kernels (csrc/rowops.hip: the LayerNorm family, the two embeddings, the column sums) are compared element by
+# element with an fp64 reference of the SAME stored operands.  As above, every term follows from the arithmetic and none
+# is fitted to a kernel's result.  u = 2^-24, UB = 2^-8, c = 2 the margin for an unknown summation order (lanes, wave
+# shuffles, LDS and workspace stages), H the row width, M the number of rows.
+#   z              e_z = (n + 3) u S        S = (sum |in slab| + |bias|) keep_pre + |residual|: n - 1 slab additions (n <= 8),
+#                  the bias, the keep-scale product and the residual, fp32 each; + UB |z| where z is stored as bf16.
+#                  The kernel normalises the ROUNDED z it stores and so does the reference: then e_z = 0 below.
+#   mean           e_mean = c (H + 3) u mean|z| + mean(e_z)           H - 1 additions in any order and the division
+#   centred        e_t = e_z + e_mean + u |t|,  t = z - mean          the centred values carry the error of the mean
+#   variance       e_var = mean(2 |t| e_t + e_t^2) + c (H + 3) u var  the squares of the perturbed t, the H-term sum
+#   rstd           v = var + eps, e_v = e_var + 3 u v (addition, division by H, eps as fp32); the computed variance is
+#                  a sum of squares, so the computed v is never below eps (1 - 2 u): lo = max(v - e_v, eps (1 - 2 u)) and
+#                  rho = max(sqrt(v / lo) - 1, 1 - sqrt(v / (v + e_v))) + 4 * 2^-23      the RELATIVE error of rstd.
+#                  The interval form is first order e_v / (2 v) = e_v / (2 (var + eps)) for a well-conditioned row and
+#                  stays finite at var = 0.  It is MEANINGFUL (rho below bf16's round-off at H = 2048) only for rows with
+#                  var >= ROW_TAU * mean|z|^2; row_cases asserts that of every input row but the one named constant-row
+#                  case, which is checked for finite results and for the exact out = beta instead.
+#                  4 * 2^-23: rsqrtf 2 ulp, the addition of eps and the division by H one rounding each.  The 2 ulp is a
+#                  DOCUMENTED figure, not a derivation: the ROCm device library's rsqrt follows the OpenCL full-profile
+#                  accuracy table (2 ulp; the native v_rsq_f32 is 1 ulp).  The HIP math API's own accuracy table was
+#                  not at hand when this was written, so the count rests on that specification.
+#   out            e_y = |g| (|t| rstd rho + rstd (1 + rho) e_t) + 4 u (|y| + |beta|),  y = t rstd g + beta;
+#                  bound = e_y keep_post |out_scale| + 2 u |y keep_post out_scale| (+ u (|old| + |ref|) when
+#                  accumulating) + UB |ref| for a bf16 store (round-to-nearest, no margin on this term)
+#   ln_sum_fwd     the sum over the n <= 4 terms of their out bounds without store, n u sum|term| for the additions,
+#                  then ONE store
+#   ln_bwd         from the stored dy, z, stats (mean, rstd as the forward left them: operands, no error), gamma:
+#                  dyn = dy keep_post out_scale (2 u), xh = (z - mean) rstd (2 u), tt = dyn g (3 u in all)
+#                  s1 = mean(tt), s2 = mean(tt xh):  e_s = c (H + 3) u mean|term| + mean(term roundings)
+#                  dz = rstd (tt - s1 - xh s2):  e_dz = rstd (3 u |tt| + e_s1 + |xh| e_s2 + 2 u |xh s2| + 4 u (|tt| + |s1| + |xh s2|))
+#                  d_res = dz (+ old: one more rounding, u (|old| + |ref|)) + store
+#                  d_in = dz keep_pre gelu'(aux):  e_dz keep |gelu'| + |dz| keep 4 u (1 + |gelu'|) (the fp32 evaluation of
+#                  gelu_grad_f, as gemm_excess's `extra` takes it) + 2 u |d_in| + store
+#   column sums    dgamma = sum_m dyn xh (5 u per term), dbeta = sum_m dyn (2 u), dbias = sum_m d_in (UNROUNDED: the d_in
+#                  bound without store), the ten vectors of visn_embed_bwd, colsum, the embedding scatter:
+#                  sum_m (per-row bound) + c (M + 3) u sum_m |term| + u (|old| + |ref|) for the `+=` into the gradient
+# A zero bound admits only the exact value; a non-finite result has excess +inf (bound_excess).
+ROW_TAU = 2.0 ** -8
+ROW_RSQRT_ULPS = 4
+
+
+def store_term(ref, dtype):
+    if dtype == torch.bfloat16:
+        return U_BF16 * ref.abs()
+    if dtype != torch.float32:
+        raise TypeError("row bound: fp32 or bf16 storage, got %s" % dtype)
+    return torch.zeros_like(ref)
+
+
+def row_z_bound(S, n_slabs, dtype, ref):
+    """bound of the stored pre-normalisation sum against the unrounded fp64 sum ``ref``; S as in the block above"""
+    return (max(n_slabs, 1) + 3) * U32 * S + store_term(ref, dtype)
+
+
+def ln_terms(z, gamma, beta, eps, e_z=None, c=2.0):
+    """fp64 LayerNorm of the rows z [M, H] (as the kernel normalises them) and the error terms of the block above:
+    dict(mean, rstd, t, y, e_mean, rho, e_t, e_y, var)"""
+    H = z.shape[-1]
+    ez = torch.zeros_like(z) if e_z is None else e_z
+    mean = z.mean(-1, keepdim=True)
+    t = z - mean
+    var = (t * t).mean(-1, keepdim=True)
+    e_mean = c * (H + 3) * U32 * z.abs().mean(-1, keepdim=True) + ez.mean(-1, keepdim=True)
+    e_t = ez + e_mean + U32 * t.abs()
+    e_var = (2 * t.abs() * e_t + e_t * e_t).mean(-1, keepdim=True) + c * (H + 3) * U32 * var
+    v = var + eps
+    e_v = e_var + 3 * U32 * v
+    lo = torch.maximum(v - e_v, torch.full_like(v, eps * (1 - 2 * U32)))
+    rho = torch.maximum(torch.sqrt(v / lo) - 1, 1 - torch.sqrt(v / (v + e_v))) + ROW_RSQRT_ULPS * 2.0 ** -23
+    rstd = v.rsqrt()
+    y = t * rstd * gamma + beta
+    e_y = gamma.abs() * (t.abs() * rstd * rho + rstd * (1 + rho) * e_t) + 4 * U32 * (y.abs() + beta.abs())
+    return dict(mean=mean, rstd=rstd, t=t, y=y, var=var, e_mean=e_mean, rho=rho, e_t=e_t, e_y=e_y)
+
+
+def ln_out_bound(L, keep_post, out_scale, old, dtype, store=True):
+    """(reference, bound) of out = [old +] out_scale keep_post y from ln_terms' dict ``L``"""
+    f = keep_post * abs(out_scale)
+    ref = L["y"] * keep_post * out_scale
+    bound = L["e_y"] * f + 2 * U32 * ref.abs()
+    if old is not None:
+        ref = ref + old
+        bound = bound + U32 * (old.abs() + ref.abs())
+    return ref, bound + (store_term(ref, dtype) if store else 0.0)
+
+
+def ln_bwd_terms(dy, z, mean, rstd, gamma, keep_post, out_scale, keep_pre, gp, c=2.0):
+    """fp64 LayerNorm backward of the stored operands and the error terms of the block above.  ``gp`` = gelu'(aux) or
+    None.  dict(dz, e_dz, din, e_din, and the per-row column-sum terms tg, e_tg (dgamma), tb, e_tb (dbeta))"""
+    u, H = U32, z.shape[-1]
+    m = lambda x: x.mean(-1, keepdim=True)
+    dyn = dy * keep_post * out_scale
+    xh = (z - mean) * rstd
+    tt = dyn * gamma
+    s1, s2 = m(tt), m(tt * xh)
+    e_s1 = c * (H + 3) * u * m(tt.abs()) + 3 * u * m(tt.abs())
+    e_s2 = c * (H + 3) * u * m((tt * xh).abs()) + 6 * u * m((tt * xh).abs())
+    dz = rstd * (tt - s1 - xh * s2)
+    e_dz = rstd * (3 * u * tt.abs() + e_s1 + xh.abs() * e_s2 + 2 * u * (xh * s2).abs()
+                   + 4 * u * (tt.abs() + s1.abs() + (xh * s2).abs()))
+    din, e_din = dz * keep_pre, e_dz * keep_pre
+    if gp is not None:
+        e_din = e_din * gp.abs() + din.abs() * 4 * u * (1 + gp.abs())
+        din = din * gp
+    e_din = e_din + 2 * u * din.abs()
+    return dict(dz=dz, e_dz=e_dz, din=din, e_din=e_din, tg=dyn * xh, e_tg=5 * u * (dyn * xh).abs(), tb=dyn,
+                e_tb=2 * u * dyn.abs(), xh=xh, dyn=dyn)
+
+
+def colsum_bound(term, e_term, old, c=2.0):
+    """(reference, bound) of old + sum_m term[m, :] for fp32 additions in any order; e_term: the per-row bounds"""
+    M = term.shape[0]
+    ref = term.sum(0)
+    bound = e_term.sum(0) + c * (M + 3) * U32 * term.abs().sum(0)
+    if old is not None:
+        ref = ref + old
+        bound = bound + U32 * (old.abs() + ref.abs())
+    return ref, bound
